@@ -11,16 +11,22 @@ batch of synthetic documents already resident in HBM:
   N = 1 : BASELINE.json configs[1] = 1 M x 512-byte ASCII documents (G-ascii)
   N > 1 : configs[3] shape = 1 M x 512-byte documents PER GPU (weak scaling: 8 M over 8 GPUs),
           contiguous shards, plus the single RCCL gather of the id buffers to rank 0 inside the step.
-One JSON line is printed by rank 0 (contract in the task statement) with two extra objects:
+One JSON line is printed by rank 0 (contract in the task statement) with, among others:
   roofline     -- the dominant kernel (tk_flat_kernel: split + lookup + merge, one wave per 2048-byte region)
                   against the HBM roofline:
                   algorithmic bytes (N_in + 8(D+1) + 4 T_out + 8(D+1)) per launch divided by
-                  its mean duration measured live with HIP events on the launch stream
+                  its mean duration measured live with HIP events on the launch stream (the timed steps' own events)
+  node         -- gather-inclusive and kernels-only MB/s, per-GPU kernel time; build (git commit of the library).
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: nothing else.
+--full adds every leg that takes runs or checks of its own:
   cpu_baseline -- the CPU oracle (a restatement, "port": the reference is Rust and cannot be built
-                  here) timed single-thread on this box's host cores on the same documents; cpu_baseline_nt: the same on
-                  all host cores (count stated)
-Other objects: decode (row f-1), host_to_host (row f-4, PCIe inclusive), single_doc (the reference's one-&str-per-call shape,
-BASELINE configs[0]), node (gather-inclusive and kernels-only MB/s, per-GPU kernel time), build (git commit of the library).
+                  here) timed single-thread on this box's host cores on the same documents, and the bit-exact comparison
+                  of the GPU ids with it; cpu_baseline_nt: the same on all host cores (count stated)
+  decode (row f-1), host_to_host (row f-4, PCIe inclusive), single_doc (the reference's one-&str-per-call shape,
+  BASELINE configs[0]), two_in_flight, and on the default shape the compact legs for configs[2], configs[4] and the
+  held-out vocabulary (--extra-legs).  --entry node: the oracle parity check of a sample.
+--dump-outputs DIR: after the timed steps, what the last step computed (ids and output offsets, as a caller receives them)
+  as DIR/*.npy, float32 / float64, at most 64 MB (64 x 10^6 bytes) of files in all (see dump_outputs).
 --kind mixed = configs[2], --kind zipf = configs[4] (N > 1: documents sharded by BYTES).
 """
 import argparse
@@ -98,6 +104,53 @@ def self_launch(args):
     raise SystemExit(0)
 
 
+DUMP_BYTES = 64_000_000 - 4096   # --dump-outputs: the arrays' bytes; the rest of 64 MB holds the five .npy headers (128 B each)
+DUMP_SEED = 0x7E44E2             # its samples depend on this seed and the array lengths alone
+
+
+def _spread(n, k, rng):
+    """k distinct indices below n in increasing order: all of them when k == n, else one every n / k (>= 1) from a seeded offset
+    within the first stride -- O(k) memory, the same for the same (n, k)."""
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    step = n / k
+    return np.minimum((rng.random() * step + np.arange(k) * step).astype(np.int64), n - 1)
+
+
+def dump_outputs(path, ids, offs):
+    """--dump-outputs: what the timed path hands its caller after the last step -- ids (u32, every document's back to back) and the
+    output offsets (u64[D + 1]) -- as .npy files, so that two builds can be compared output for output; DUMP_BYTES of arrays, 64 MB of files at most:
+      doc_index.npy     the documents covered: all of them when D <= 2^20, else 2^20 of them spread evenly from a seeded offset (float64)
+      token_counts.npy  ids per covered document, offs[d + 1] - offs[d] (float64)
+      id_sums.npy       the sum of each covered document's ids (float64, exact): every id of those documents counts
+      ids_index.npy     positions in the id array, spread evenly from a seeded offset, as many as the rest of the budget holds (float64)
+      ids.npy           the ids at those positions (float32 when every id is below 2^24, which float32 holds exactly, else float64)"""
+    os.makedirs(path, exist_ok=True)
+    n_docs, n_ids = len(offs) - 1, int(offs[-1])
+    ids = ids[:n_ids]
+    o = offs.astype(np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    k = min(n_docs, 1 << 20)
+    docs = _spread(n_docs, k, rng)
+    lo, hi = o[docs], o[docs + 1]
+    sums = np.zeros(k, np.int64)
+    for c in range(0, k, 8192):            # (chunks of documents: a prefix sum over one chunk's span at a time bounds the memory)
+        clo, chi = lo[c:c + 8192], hi[c:c + 8192]
+        base = int(clo[0])
+        ps = np.concatenate((np.zeros(1, np.int64), np.cumsum(ids[base:int(chi[-1])], dtype=np.int64)))
+        sums[c:c + 8192] = ps[chi - base] - ps[clo - base]
+    wide = n_ids > 0 and int(ids.max()) >= 1 << 24
+    p = min(n_ids, (DUMP_BYTES - 3 * 8 * k) // (8 + (8 if wide else 4)))
+    pos = _spread(n_ids, p, rng)
+    arrays = {"doc_index": docs.astype(np.float64), "token_counts": (hi - lo).astype(np.float64), "id_sums": sums.astype(np.float64),
+              "ids_index": pos.astype(np.float64), "ids": ids[pos].astype(np.float64 if wide else np.float32)}
+    files = [os.path.join(path, name + ".npy") for name in arrays]
+    for f, a in zip(files, arrays.values()):
+        np.save(f, a)
+    return {"dir": path, "files": sorted(os.path.basename(f) for f in files), "bytes": int(sum(os.path.getsize(f) for f in files)),
+            "docs_covered": int(k), "ids_sampled": int(p)}
+
+
 def build_info():
     """git commit the library was built at (written by __graft_entry__.build(); the GPU box has no .git)."""
     try:
@@ -110,13 +163,13 @@ def build_info():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=0, help="timed steps (0 = default: 400 for ascii = 0.5 s of kernels, 30 otherwise)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 400 for ascii = 0.5 s of kernels, 30 otherwise)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--docs", type=int, default=1_000_000, help="documents per GPU")
     ap.add_argument("--doc-len", type=int, default=512)
     ap.add_argument("--kind", default="ascii", choices=["ascii", "mixed", "zipf"])
-    ap.add_argument("--cpu-passes", type=int, default=3, help="oracle passes over the CPU sample (0 = skip)")
-    ap.add_argument("--cpu-sample-docs", type=int, default=1_000_000)
+    ap.add_argument("--cpu-passes", type=int, default=3, help="with --full: oracle passes over the CPU sample (0 = skip)")
+    ap.add_argument("--cpu-sample-docs", type=int, default=1_000_000, help="with --full: documents of the CPU sample")
     ap.add_argument("--vocab", default=os.environ.get("TEKKEN_JSON", ""))
     ap.add_argument("--entry", choices=["ranks", "node"], default="ranks",
                     help="ranks: one process per GPU (torch.distributed, what the driver launches); node: ONE process, the C ABI's "
@@ -126,20 +179,33 @@ def main():
     ap.add_argument("--gather", choices=["overlap", "sync"], default="overlap",
                     help="N > 1: gather of batch k beside the kernels of batch k + 1 (default) or inside the step, blocking")
     ap.add_argument("--wire", type=int, choices=[18, 32], default=18, help="N > 1: bits per id on the wire")
-    ap.add_argument("--host-steps", type=int, default=3, help="host-to-host leg (row f-4): timed passes, 0 = skip")
-    ap.add_argument("--decode-steps", type=int, default=5, help="extra leg: GPU batch decode of the produced ids (0 = skip)")
+    ap.add_argument("--host-steps", type=int, default=3, help="with --full: host-to-host leg (row f-4): timed passes, 0 = skip")
+    ap.add_argument("--decode-steps", type=int, default=5, help="with --full: GPU batch decode of the produced ids (0 = skip)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = dry run of the N>1 code path with several ranks sharing one GPU (ids staged through host)")
-    ap.add_argument("--single-docs", type=int, default=1000, help="single_doc leg: sequential one-document calls (C1 shape: 64-byte strings), 0 = skip")
+    ap.add_argument("--single-docs", type=int, default=1000, help="with --full: single_doc leg: sequential one-document calls (C1 shape: 64-byte strings), 0 = skip")
     ap.add_argument("--fresh-batches", type=int, default=0,
                     help="B >= warmup + steps distinct seeded batches resident in HBM, step k runs on batch k, and the memo of merged pieces "
                          "(tk_ctx_set_memo) is ON: the only protocol under which a persistent cache may be timed.  0 (default): one batch repeated, memo OFF")
-    ap.add_argument("--extra-legs", default="auto", help="auto: at N = 1 on the default shape also run compact legs for configs[2], one GPU's share of "
+    ap.add_argument("--extra-legs", default="auto", help="with --full: auto: at N = 1 on the default shape also run compact legs for configs[2], one GPU's share of "
                                                            "configs[4] and the held-out vocabulary (fresh batches, memo on and off); none: skip")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="cpu_baseline_nt: oracle threads (0 = all host cores, capped at 256; 1 = skip)")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="with --full: cpu_baseline_nt: oracle threads (0 = all host cores, capped at 256; 1 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs or checks of their own (CPU baseline and bit-exact check, decode, host-to-host, "
+                         "single_doc, two_in_flight, --extra-legs); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (ids, output offsets; a fixed seeded sample) as DIR/*.npy")
     args = ap.parse_args()
-    if args.steps <= 0:
+    if args.steps is None:
         args.steps = 400 if args.kind == "ascii" else 30
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # the legs' options act only with --full: say so when one of them asks for a leg that this run will not do
+        asked = ["--" + k.replace("_", "-") for k in ("cpu_passes", "cpu_sample_docs", "cpu_threads", "host_steps", "decode_steps", "single_docs", "extra_legs")
+                 if getattr(args, k) != ap.get_default(k) and getattr(args, k) not in (0, "none")]
+        if asked and int(os.environ.get("RANK", "0")) == 0 and not (args.gpus > 1 and "WORLD_SIZE" not in os.environ):   # (once: not in a self-launching parent)
+            sys.stderr.write("[bench] %s: no effect without --full\n" % ", ".join(asked))
     if args.entry == "node":
         return node_entry(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("TK_BENCH_FORCE_DIST") != "1":
@@ -409,20 +475,25 @@ def main():
                      "per_gpu_input_bytes": [int(p[1]) for p in per_rank]},
             "build": build_info(),
         }
-        if not distributed:
+        if not distributed and (args.full or args.dump_outputs):
             # the ids of the last timed step, on the host (the device views die with the next call on the context)
             h_ids = torch.as_tensor(v_ids, device="cuda").cpu().numpy().view(np.uint32)
             h_oo = torch.as_tensor(v_oo, device="cuda").cpu().numpy().astype(np.uint64)
-        if not distributed and args.decode_steps > 0:
+        if args.dump_outputs:
+            # (N > 1: what rank 0 receives, the gathered ids of the whole node in document order)
+            d_ids, d_oo = (h_ids, h_oo) if not distributed else \
+                (gathered[0].cpu().numpy().astype(np.uint32), gathered[1].cpu().numpy().astype(np.uint64))
+            sys.stderr.write("[bench] outputs: %s\n" % json.dumps(dump_outputs(args.dump_outputs, d_ids, d_oo)))
+        if not distributed and args.full and args.decode_steps > 0:
             out["decode"] = decode_leg(args, tk, eng, v_ids, v_oo, n_docs, n_bytes, d_bytes, stream)
-        if not distributed and args.host_steps > 0:
+        if not distributed and args.full and args.host_steps > 0:
             out["host_to_host"] = host_leg(args, tk, eng, data, offs, h_ids, h_oo)
-        if not distributed and args.single_docs > 0:
+        if not distributed and args.full and args.single_docs > 0:
             out["single_doc"] = single_doc_leg(args, tk, eng, vocab_path)
         out["memo"] = dict(eng.memo_stats(), protocol=protocol)
-        if not distributed and args.cpu_passes > 0:
+        if not distributed and args.full and args.cpu_passes > 0:
             out.update(cpu_baseline(args, data, offs, vocab_path, h_ids, h_oo, n_bytes))
-        if distributed and args.cpu_passes > 0:
+        if distributed and args.full and args.cpu_passes > 0:
             # rank 0's shard on rank 0's host cores, bounded (the contract: N = 1 only needs it; the line keeps it for every N)
             v_i = torch.as_tensor(v_ids, device="cuda").cpu().numpy().view(np.uint32)
             v_o = torch.as_tensor(v_oo, device="cuda").cpu().numpy().astype(np.uint64)
@@ -431,9 +502,9 @@ def main():
             out.update(cpu_baseline(a2, data, offs, vocab_path, v_i, v_o, n_bytes))
         if distributed:
             out["link_model"] = link_model(world, per_rank, total_ids, total_docs, 18 if codec else 32, ms_per_step)
-        if not distributed and args.extra_legs == "auto" and args.kind == "ascii" and not args.vocab and args.vocab_fit == "same" and not fresh:
+        if not distributed and args.full and args.extra_legs == "auto" and args.kind == "ascii" and not args.vocab and args.vocab_fit == "same" and not fresh:
             out["two_in_flight"] = in_flight_leg(tk, vocab_path, eng, d_bytes, d_offs, n_docs, n_bytes, ms_per_step, calls=100 if n_docs >= 500_000 else 10)
-        if not distributed and args.extra_legs == "auto" and args.kind == "ascii" and not args.vocab and args.vocab_fit == "same" \
+        if not distributed and args.full and args.extra_legs == "auto" and args.kind == "ascii" and not args.vocab and args.vocab_fit == "same" \
                 and n_docs == 1_000_000 and args.doc_len == 512 and not fresh:
             tokz.close()
             tokz = None
@@ -608,22 +679,27 @@ def node_entry(args):
         k_ms.append(t["kernels_ms_max"])
         g_ms.append(t["gather_ms"])
     elapsed = time.perf_counter() - t0
-    # parity on a sample through the oracle (the checker), ids in document order as from one GPU
-    sample = min(n_docs, 20000)
-    orc = tk_oracle.Oracle(toks, ns, bos, eos)
-    eids, eoo = orc.encode_batch(data[:int(offs[sample])], offs[:sample + 1], True, True, threads=16)
-    exact = bool(np.array_equal(h_ids[:int(h_oo[sample])], eids) and np.array_equal(h_oo[:sample + 1], eoo))
+    if args.dump_outputs:
+        sys.stderr.write("[bench] outputs: %s\n" % json.dumps(dump_outputs(args.dump_outputs, h_ids, h_oo)))
+    check = {}
+    if args.full:
+        # parity on a sample through the oracle (the checker), ids in document order as from one GPU
+        sample = min(n_docs, 20000)
+        orc = tk_oracle.Oracle(toks, ns, bos, eos)
+        eids, eoo = orc.encode_batch(data[:int(offs[sample])], offs[:sample + 1], True, True, threads=16)
+        exact = bool(np.array_equal(h_ids[:int(h_oo[sample])], eids) and np.array_equal(h_oo[:sample + 1], eoo))
+        check = {"bit_exact_vs_cpu_sample_docs": sample, "bit_exact_vs_cpu": exact}
     ms = elapsed / args.steps * 1e3
-    print(json.dumps({
+    print(json.dumps(dict({
         "metric": "input MB/s tokenized (whole node), host buffers in -> ids in host buffers (PCIe and gather inclusive; tk_node_encode_batch_pinned)",
         "value": round(len(data) / 1e6 / (ms * 1e-3), 1), "unit": "MB/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
         "config": {"workload": "%d x %s documents per GPU, one process, tk_node_* over GPUs 0..%d, pinned caller buffers" % (args.docs, args.kind, n - 1),
                    "entry": "node", "docs_total": n_docs, "input_bytes_total": int(len(data)), "ids_total": int(n_ids)},
         "node": {"kernels_ms_max": round(float(np.mean(k_ms)), 4), "gather_ms": round(float(np.mean(g_ms)), 4)},
-        "bit_exact_vs_cpu_sample_docs": sample, "bit_exact_vs_cpu": exact, "build": build_info()}), flush=True)
+        "build": build_info()}, **check)), flush=True)
     node.close()
-    if not exact:
+    if check and not check["bit_exact_vs_cpu"]:
         raise SystemExit(1)
 
 

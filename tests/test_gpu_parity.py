@@ -358,13 +358,13 @@ def test_invalid_utf8_without_validation_is_safe(eng_small):
 
 
 def test_bench_contract_small(tk):
-    """bench.py prints exactly one JSON line with the contract's keys (small workload)."""
+    """bench.py --full prints exactly one JSON line with the contract's keys and every leg's (small workload)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--docs", "20000", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--docs", "20000", "--steps", "2", "--warmup", "1", "--full",
                         "--cpu-sample-docs", "5000", "--cpu-passes", "1", "--decode-steps", "1"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -380,6 +380,32 @@ def test_bench_contract_small(tk):
     assert j["decode"]["round_trip_exact"] is True
     # two contexts fed by two host threads (the leg that shows what a second batch in flight buys): both give the same ids
     assert j["two_in_flight"]["both_contexts_same_ids"] is True and j["two_in_flight"]["calls_timed"] == 20
+
+
+def test_bench_plain_run_dumps_outputs(tk, bench_vocab, tmp_path):
+    """A plain bench.py run prints the headline line only (no leg of --full), and --dump-outputs writes what its last timed step
+    computed: on 20 000 documents every document and every id fit the dump, so it is compared id for id with the oracle."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--docs", "20000", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["unit"] == "MB/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+    for k in ("cpu_baseline", "bit_exact_vs_cpu", "decode", "host_to_host", "single_doc", "two_in_flight", "configs[2]"):
+        assert k not in j, k
+    a = {n: np.load(str(out / (n + ".npy"))) for n in ("doc_index", "token_counts", "id_sums", "ids_index", "ids")}
+    assert sum(os.path.getsize(str(out / (n + ".npy"))) for n in a) <= 64_000_000 and all(x.dtype in (np.float32, np.float64) for x in a.values())
+    data, offs = corpus.generate("ascii", 20000, 512, seed=corpus.BASE_SEED + 1)
+    eids, eoo = helpers.oracle_for(bench_vocab).encode_batch(data, offs, True, True, threads=8)
+    assert np.array_equal(a["doc_index"], np.arange(20000)) and np.array_equal(a["ids_index"], np.arange(len(eids)))
+    assert np.array_equal(a["token_counts"], np.diff(eoo.astype(np.int64))) and np.array_equal(a["ids"], eids)
+    assert np.array_equal(a["id_sums"], np.add.reduceat(eids.astype(np.int64), eoo[:-1].astype(np.int64)))
 
 
 def test_table_cache_context(tk, bench_vocab, tmp_path, monkeypatch):
