@@ -167,6 +167,49 @@ int tk_encode_batch_device_ex(tk_ctx* ctx, const void* d_bytes, const void* d_do
                               int add_bos, int add_eos, int checks, void* hip_stream, void** d_ids, void** d_out_offsets,
                               uint64_t* n_ids);
 
+/* ---- per-token byte spans (HF tokenizers' offset_mapping; no reference equivalent -- decode_all, src/tekkenizer.rs:463-560,
+ * gives per-segment strings, not positions in the input) ----
+ * For each output id i of document d, the span is spans[2i], spans[2i+1] = (start, end).  Both are uint32 byte offsets
+ * relative to the start of document d.
+ *   - A non-special id covers end - start = len(token bytes), and bytes[doc_start+start : doc_start+end] equals those token
+ *     bytes.
+ *   - BOS is (0, 0).  EOS is (doc_len, doc_len).  In general a special id gets a zero-length span at the current position.
+ *   - A document of 2^32 bytes or more makes the spans entries fail with TK_ERR_INVALID_ARG.  The encode entries are not
+ *     affected.
+ *   - Offsets are in BYTES, not characters: a token can end inside a UTF-8 character (the byte-fallback tokens of an emoji or a
+ *     rare CJK character do).  Character offsets are not provided.
+ * Encode is lossless (byte-level BPE tiles the text; the only specials it emits are BOS / EOS), so the spans of encode's ids
+ * are a per-document exclusive prefix sum of the ids' byte lengths (a special id: 0) -- a separate pass behind the encode
+ * pipeline (csrc/tk_spans.hip), which can check the ids against the text in the same pass.  `checks` is a bit field that sits
+ * above TK_CHECK_OFFSETS / TK_CHECK_UTF8, so one word can carry all four:
+ *   TK_SPANS_CHECK_COVER  the last end of every document equals doc_offsets[d+1] - doc_offsets[d] (a document without ids:
+ *                         doc_len == 0)
+ *   TK_SPANS_CHECK_BYTES  implies COVER; the token bytes of every non-special id equal the text under its span -- the round
+ *                         trip decode(encode(x)) == x, id by id
+ * A failed check returns TK_ERR_RUNTIME (the message names the document and the two lengths) and writes the first failing
+ * document to *bad_doc (optional); an id outside the vocabulary is TK_ERR_RUNTIME too. */
+#define TK_SPANS_CHECK_COVER 4
+#define TK_SPANS_CHECK_BYTES 8
+/* Spans of ids already on the device (any ids: encode's own outputs, or the caller's).  d_doc_offsets (n_docs + 1 uint64,
+ * well-formed) is needed only for a check, d_bytes only for TK_SPANS_CHECK_BYTES (NULL otherwise).  *d_spans (2 * n_ids uint32)
+ * is a device buffer owned by the context, valid until the next spans call on it, and SEPARATE from the encode outputs: the
+ * d_ids / d_out_offsets the previous encode call on the same context returned stay valid through this call.  The work is
+ * enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_token_spans_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                          const void* d_doc_offsets, const void* d_bytes, int checks, void* hip_stream, void** d_spans,
+                          uint64_t* bad_doc);
+/* tk_encode_batch_device_ex + the spans pass on the same stream.  checks may combine TK_CHECK_OFFSETS / TK_CHECK_UTF8 (encode's
+ * input checks) with TK_SPANS_CHECK_COVER / TK_SPANS_CHECK_BYTES.  *d_ids / *d_out_offsets as tk_encode_batch_device, *d_spans
+ * as tk_token_spans_device. */
+int tk_encode_batch_device_spans(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 int add_bos, int add_eos, int checks, void* hip_stream, void** d_ids, void** d_out_offsets,
+                                 void** d_spans, uint64_t* n_ids, uint64_t* bad_doc);
+/* Host in / host out: tk_encode_batch + spans (batches of the one-launch small path included).  *spans is pinned, 2 * n_ids
+ * entries, free with tk_free_spans; out as tk_encode_batch (tk_free_result). */
+int tk_encode_batch_spans(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
+                          int add_eos, int validate_utf8, int checks, tk_result* out, uint32_t** spans, uint64_t* bad_doc);
+void tk_free_spans(uint32_t* spans);
+
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token
  * at POSITION i of the reference's all_special_tokens vector (src/tekkenizer.rs:108-116, 536-540);
@@ -276,6 +319,11 @@ int tk_tokenizer_encode(tk_tokenizer* t, const char* text, size_t len, int add_b
 int tk_tokenizer_encode_batch(tk_tokenizer* t, const uint8_t* bytes, const uint64_t* doc_offsets,
                               uint64_t n_docs, int add_bos, int add_eos, tk_result* out);
 void tk_free_ids(uint32_t* ids);
+/* Tekkenizer::encode + the byte span of every id (see tk_token_spans_device for the definition); *ids and *spans (2 * n_ids
+ * entries) are malloc'ed, free both with tk_free_ids.  The spans are computed on the host from the ids and the rank table (no
+ * second launch); they equal what the spans kernel gives for the same ids. */
+int tk_tokenizer_encode_with_spans(tk_tokenizer* t, const char* text, size_t len, int add_bos, int add_eos,
+                                   uint32_t** ids, uint32_t** spans, size_t* n_ids);
 /* Opt-in (row f-3): honour the `pattern` of the loaded tekken.json instead of ignoring it like the reference does
  * (src/tekkenizer.rs:74).  Only Mistral's pattern string is known; any other is refused with TK_ERR_INVALID_CONFIG.
  * See tk_ctx_set_pattern. */

@@ -10,6 +10,10 @@ pub struct TkNode {
     _p: [u8; 0],
 }
 #[repr(C)]
+pub struct TkTokenizer {
+    _p: [u8; 0],
+}
+#[repr(C)]
 pub struct TkResult {
     pub ids: *mut u32,
     pub offsets: *mut u64,
@@ -33,6 +37,10 @@ pub const TK_ERR_INVALID_ARG: c_int = -5;
 pub const TK_ERR_TOKEN_NOT_FOUND: c_int = -9;
 pub const TK_ERR_SPECIAL_POLICY: c_int = -10;
 
+// the checks of the spans entries (above TK_CHECK_OFFSETS = 1 / TK_CHECK_UTF8 = 2: one word can carry all four)
+pub const TK_SPANS_CHECK_COVER: c_int = 4;
+pub const TK_SPANS_CHECK_BYTES: c_int = 8;
+
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
     pub fn tk_ctx_create(token_bytes: *const u8, token_offsets: *const u32, n_ranks: u32, num_special_tokens: u32, bos_id: u32,
@@ -52,6 +60,20 @@ extern "C" {
     pub fn tk_encode_batch_device_ex(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
                                      add_bos: c_int, add_eos: c_int, checks: c_int, hip_stream: *mut c_void, d_ids: *mut *mut c_void,
                                      d_out_offsets: *mut *mut c_void, n_ids: *mut u64) -> c_int;
+    // per-token byte spans: (start, end) of every id, u32 byte offsets relative to the start of its document
+    pub fn tk_token_spans_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                 d_doc_offsets: *const c_void, d_bytes: *const c_void, checks: c_int, hip_stream: *mut c_void,
+                                 d_spans: *mut *mut c_void, bad_doc: *mut u64) -> c_int;
+    pub fn tk_encode_batch_device_spans(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                        add_bos: c_int, add_eos: c_int, checks: c_int, hip_stream: *mut c_void, d_ids: *mut *mut c_void,
+                                        d_out_offsets: *mut *mut c_void, d_spans: *mut *mut c_void, n_ids: *mut u64, bad_doc: *mut u64) -> c_int;
+    pub fn tk_encode_batch_spans(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                 validate_utf8: c_int, checks: c_int, out: *mut TkResult, spans: *mut *mut u32, bad_doc: *mut u64) -> c_int;
+    pub fn tk_free_spans(spans: *mut u32);
+    // tokenizer level, one string: Tekkenizer::encode + offsets (*ids and *spans malloc'ed, both freed with tk_free_ids)
+    pub fn tk_tokenizer_encode_with_spans(t: *mut TkTokenizer, text: *const c_char, len: usize, add_bos: c_int, add_eos: c_int,
+                                          ids: *mut *mut u32, spans: *mut *mut u32, n_ids: *mut usize) -> c_int;
+    pub fn tk_free_ids(ids: *mut u32);
     // memo of merged pieces (round 4): a device table {unknown piece of 2..16 bytes -> its <= 4 ids}; never changes an id
     pub fn tk_ctx_set_memo(ctx: *mut TkCtx, log2_entries: c_int, policy: c_int) -> c_int;
     pub fn tk_ctx_memo_clear(ctx: *mut TkCtx) -> c_int;

@@ -116,6 +116,37 @@ impl HipEngine {
         }
         Ok(unsafe { take(&mut res, docs.len()) })
     }
+
+    /// `encode` + where every id came from: `(start, end)` byte offsets into `text` (HF tokenizers' `offset_mapping`, in bytes of
+    /// the UTF-8 text -- a byte-fallback token can end inside a char; BOS is `(0, 0)`, EOS `(len, len)`).
+    pub fn encode_with_offsets(&self, text: &str, add_bos: bool, add_eos: bool) -> Result<(Vec<u32>, Vec<(u32, u32)>), HipError> {
+        Ok(self.encode_batch_with_offsets(&[text], add_bos, add_eos)?.pop().unwrap_or_default())
+    }
+
+    /// The batch form: per document `(ids, spans)`, spans relative to the start of the document (tk_encode_batch_spans).
+    pub fn encode_batch_with_offsets(&self, docs: &[&str], add_bos: bool, add_eos: bool)
+                                     -> Result<Vec<(Vec<u32>, Vec<(u32, u32)>)>, HipError> {
+        let (bytes, offs) = pack_docs(docs);
+        let mut res = TkResult { ids: std::ptr::null_mut(), offsets: std::ptr::null_mut(), n_ids: 0, n_docs: 0 };
+        let mut spans: *mut u32 = std::ptr::null_mut();
+        let mut bad_doc = 0u64;
+        let rc = unsafe {
+            tk_encode_batch_spans(self.ctx, bytes.as_ptr(), offs.as_ptr(), docs.len() as u64, add_bos as c_int, add_eos as c_int, 0, 0,
+                                  &mut res, &mut spans, &mut bad_doc)
+        };
+        if rc != TK_OK {
+            return Err(map_err(rc, unsafe { tk_last_error(self.ctx) }));
+        }
+        let out = unsafe {
+            let sp = std::slice::from_raw_parts(spans, 2 * res.n_ids as usize);
+            let o = std::slice::from_raw_parts(res.offsets, docs.len() + 1);
+            let per_doc: Vec<Vec<(u32, u32)>> =
+                (0..docs.len()).map(|d| (o[d] as usize..o[d + 1] as usize).map(|i| (sp[2 * i], sp[2 * i + 1])).collect()).collect();
+            tk_free_spans(spans);
+            take(&mut res, docs.len()).into_iter().zip(per_doc).collect()
+        };
+        Ok(out)
+    }
 }
 impl Drop for HipEngine {
     fn drop(&mut self) {

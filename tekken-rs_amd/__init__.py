@@ -28,6 +28,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 TK_OK = 0
 CHECK_OFFSETS, CHECK_UTF8 = 1, 2   # tk_encode_batch_device_ex
+SPANS_CHECK_COVER, SPANS_CHECK_BYTES = 4, 8   # the spans entries (tk_token_spans_device, tk_encode_batch_*spans)
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
 TK_ERR_INVALID_UTF8 = -3
@@ -235,6 +236,20 @@ def lib():
     L.tk_tokenizer_json_pattern.argtypes = [vp]
     L.tk_tokenizer_from_cache.restype = ctypes.c_int
     L.tk_tokenizer_from_cache.argtypes = [vp]
+    if hasattr(L, "tk_token_spans_device"):   # (per-token byte spans: libraries built before them still load through TK_HIP_LIB)
+        L.tk_token_spans_device.restype = ctypes.c_int
+        L.tk_token_spans_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, ctypes.c_int, vp, ctypes.POINTER(vp), u64p]
+        L.tk_encode_batch_device_spans.restype = ctypes.c_int
+        L.tk_encode_batch_device_spans.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, u64p]
+        L.tk_encode_batch_spans.restype = ctypes.c_int
+        L.tk_encode_batch_spans.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(_Result), ctypes.POINTER(u32p), u64p]
+        L.tk_free_spans.restype = None
+        L.tk_free_spans.argtypes = [u32p]
+        L.tk_tokenizer_encode_with_spans.restype = ctypes.c_int
+        L.tk_tokenizer_encode_with_spans.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u32p),
+                                                     ctypes.POINTER(u32p), ctypes.POINTER(ctypes.c_size_t)]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -253,6 +268,14 @@ def pack_docs(docs):
     joined = b"".join(docs)
     data = np.frombuffer(joined, dtype=np.uint8).copy() if joined else np.zeros(0, np.uint8)
     return data, offs
+
+
+def _need(name):
+    """The bound C symbol `name`; a library built before it existed raises instead of failing on a missing attribute."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise TokenizerError(TK_ERR_RUNTIME, "%s: the loaded library (%s) predates this entry" % (name, LIB_PATH))
+    return fn
 
 
 def _take_result(res):
@@ -411,6 +434,54 @@ class Engine:
         if rc != TK_OK:
             raise self._err(rc)
         return d_ids.value, d_oo.value, int(n.value)
+
+    def encode_batch_spans(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, checks=0):
+        """tk_encode_batch_spans: (ids uint32[T], out_offsets uint64[D+1], spans uint32[T, 2]) -- spans[i] = (start, end) of id i in
+        BYTES relative to the start of its document (include/tekken_hip.h).  checks: SPANS_CHECK_COVER | SPANS_CHECK_BYTES; a failed
+        check raises TokenizerError with .bad_doc set."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        res = _Result()
+        sp = ctypes.POINTER(ctypes.c_uint32)()
+        bad = ctypes.c_uint64(0)
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        rc = _need("tk_encode_batch_spans")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                                            int(add_eos), int(validate_utf8), int(checks), ctypes.byref(res), ctypes.byref(sp), ctypes.byref(bad))
+        if rc != TK_OK:
+            e = self._err(rc)
+            e.bad_doc = int(bad.value)
+            raise e
+        n = int(res.n_ids)
+        spans = np.ctypeslib.as_array(sp, shape=(max(2 * n, 1),))[:2 * n].copy().reshape(n, 2)
+        lib().tk_free_spans(sp)
+        ids, oo = _take_result(res)
+        return ids, oo, spans
+
+    def token_spans_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_doc_offs_ptr=0, d_bytes_ptr=0, checks=0, stream=0):
+        """tk_token_spans_device: spans of ids resident in HBM (raw device pointers; the document offsets / the text only for
+        the checks).  Returns the context-owned d_spans pointer (uint32[2 * n_ids]); raises with .bad_doc on a failed check."""
+        d_sp, bad = ctypes.c_void_p(), ctypes.c_uint64(0)
+        rc = _need("tk_token_spans_device")(self._h, ctypes.c_void_p(d_ids_ptr), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                                            ctypes.c_void_p(d_doc_offs_ptr or None), ctypes.c_void_p(d_bytes_ptr or None), int(checks),
+                                            ctypes.c_void_p(stream), ctypes.byref(d_sp), ctypes.byref(bad))
+        if rc != TK_OK:
+            e = self._err(rc)
+            e.bad_doc = int(bad.value)
+            raise e
+        return d_sp.value
+
+    def encode_batch_device_spans(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, checks=0, stream=0):
+        """tk_encode_batch_device_spans: encode_batch_device + the spans pass.  checks may mix CHECK_OFFSETS / CHECK_UTF8 with
+        SPANS_CHECK_COVER / SPANS_CHECK_BYTES.  Returns (d_ids_ptr, d_out_offs_ptr, d_spans_ptr, n_ids), context-owned."""
+        d_ids, d_oo, d_sp, n, bad = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = _need("tk_encode_batch_device_spans")(self._h, ctypes.c_void_p(d_bytes_ptr), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                                                   int(add_bos), int(add_eos), int(checks), ctypes.c_void_p(stream), ctypes.byref(d_ids),
+                                                   ctypes.byref(d_oo), ctypes.byref(d_sp), ctypes.byref(n), ctypes.byref(bad))
+        if rc != TK_OK:
+            e = self._err(rc)
+            e.bad_doc = int(bad.value)
+            raise e
+        return d_ids.value, d_oo.value, d_sp.value, int(n.value)
 
     def encode_batch_device_views(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, stream=0):
         """Same, returning (ids view as int32[n_ids], offsets view as int64[n_docs+1])."""
@@ -667,6 +738,37 @@ class Tekkenizer:
         out = [ids[i] for i in range(n.value)]
         lib().tk_free_ids(ids)
         return out
+
+    def encode_with_offsets(self, text, add_bos=False, add_eos=False):
+        """Tekkenizer::encode + the byte span of every id: (ids, [(start, end), ...]) -- offsets in BYTES of the UTF-8 text
+        (a byte-fallback token can end inside a character; BOS / EOS get zero-length spans at 0 / len)."""
+        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        ids = ctypes.POINTER(ctypes.c_uint32)()
+        sp = ctypes.POINTER(ctypes.c_uint32)()
+        n = ctypes.c_size_t(0)
+        rc = _need("tk_tokenizer_encode_with_spans")(self._h, raw, len(raw), int(add_bos), int(add_eos), ctypes.byref(ids),
+                                                     ctypes.byref(sp), ctypes.byref(n))
+        if rc != TK_OK:
+            raise self._err(rc)
+        out = [ids[i] for i in range(n.value)]
+        spans = [(sp[2 * i], sp[2 * i + 1]) for i in range(n.value)]
+        lib().tk_free_ids(ids)
+        lib().tk_free_ids(sp)
+        return out, spans
+
+    def encode_batch_with_offsets(self, docs, add_bos=False, add_eos=False, checks=0):
+        """Batch form on the tokenizer's engine context (tk_encode_batch_spans): [(ids, [(start, end), ...]) per document]."""
+        eng = self.engine()
+        if eng is None:
+            raise TokenizerError(TK_ERR_NO_DEVICE, "tokenizer was created without a device (host-only object)")
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        ids, oo, spans = eng.encode_batch_spans(data, offs, add_bos, add_eos, checks=checks)
+        return [(ids[int(oo[d]):int(oo[d + 1])].tolist(), [tuple(x) for x in spans[int(oo[d]):int(oo[d + 1])].tolist()])
+                for d in range(len(docs))]
 
     def encode_batch(self, docs, add_bos=False, add_eos=False):
         data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])

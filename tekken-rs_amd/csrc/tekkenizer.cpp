@@ -928,6 +928,34 @@ extern "C" int tk_tokenizer_encode(tk_tokenizer* h, const char* text, size_t len
     return TK_OK;
 }
 
+// The spans of one document on the host: an exclusive prefix sum of the ids' byte lengths from the rank table (a special id:
+// 0) -- what tk_spans_kernel computes, without a second launch.
+extern "C" int tk_tokenizer_encode_with_spans(tk_tokenizer* h, const char* text, size_t len, int add_bos, int add_eos,
+                                              uint32_t** ids, uint32_t** spans, size_t* n_ids) {
+    if (!h || !ids || !spans || !n_ids || (!text && len)) return TK_ERR_INVALID_ARG;
+    std::vector<uint32_t> v;
+    tekken::TokenizerError e = h->t->encode(text ? text : "", len, add_bos != 0, add_eos != 0, v);
+    if (!e.ok()) return finish(h, e);
+    if ((uint64_t)len > 0xFFFFFFFFull) { h->err = "spans: the document reaches 2^32 bytes (spans are uint32 offsets)"; return TK_ERR_INVALID_ARG; }
+    const std::vector<uint32_t>& offs = h->t->rank_offsets();
+    const uint32_t nsp = h->t->num_special_tokens();
+    uint32_t* out_ids = (uint32_t*)malloc((v.size() ? v.size() : 1) * sizeof(uint32_t));
+    uint32_t* out_spans = (uint32_t*)malloc((v.size() ? v.size() : 1) * 2 * sizeof(uint32_t));
+    if (!out_ids || !out_spans) { free(out_ids); free(out_spans); h->err = "out of memory"; return TK_ERR_RUNTIME; }
+    uint32_t pos = 0;
+    for (size_t k = 0; k < v.size(); ++k) {
+        const uint32_t id = v[k];
+        out_ids[k] = id;
+        out_spans[2 * k] = pos;
+        if (id >= nsp) pos += offs[id - nsp + 1] - offs[id - nsp];   // (encode's ids are always in the vocabulary)
+        out_spans[2 * k + 1] = pos;
+    }
+    *ids = out_ids;
+    *spans = out_spans;
+    *n_ids = v.size();
+    return TK_OK;
+}
+
 extern "C" int tk_tokenizer_encode_batch(tk_tokenizer* h, const uint8_t* bytes, const uint64_t* doc_offsets,
                                          uint64_t n_docs, int add_bos, int add_eos, tk_result* out) {
     if (!h || !doc_offsets || !out) return TK_ERR_INVALID_ARG;

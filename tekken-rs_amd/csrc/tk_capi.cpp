@@ -122,7 +122,8 @@ struct tk_ctx {
     DevBuf dec_lens, dec_bytes, dec_offs, dec_bits, dec_err, dec_in_ids, dec_in_offs, dec_hi, dec_glens, dec_goffs;
     bool no_decode_groups = false;   // TK_DECODE_GROUPS=0: the per-document length pass (A / B and tests of the fall-back)
     uint32_t decode_group_limit = 0x7FFFFF00u;   // ids / text bytes of a group from which the call falls back (TK_DECODE_GROUP_LIMIT: tests)
-    DevBuf t_inline, t_len8;   // decode: 16-byte inline entries and one-byte lengths by rank (built at the first decode call)
+    DevBuf t_inline, t_len8;   // decode: 16-byte inline entries and one-byte lengths by rank (built at the first decode / spans call)
+    DevBuf sp_spans, sp_err;   // tk_token_spans_device: (start, end) per id, the error words (apart from every encode / decode buffer)
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, counters, in_bytes, in_offs, dbg;
     DevBuf f_long;             // flat path: records of the pieces of 65..TKF_LONGCAP bytes
     DevBuf long_jobs;              // tk_long.hip: the long pieces of the long-list documents
@@ -341,6 +342,8 @@ extern "C" void tk_ctx_destroy(tk_ctx* c) {
     if (c->hs_in) (void)hipHostFree(c->hs_in);
     if (c->hs_out) (void)hipHostFree(c->hs_out);
     c->s_offs.release();
+    c->sp_spans.release();
+    c->sp_err.release();
     delete c;
 }
 
@@ -982,11 +985,13 @@ static int run_pipeline(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* d_off
     return run_pipeline_doc(c, d_bytes, d_offs, n_docs, n_bytes, add_bos, add_eos, s, n_ids);
 }
 
-extern "C" int tk_encode_batch_device(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs,
-                                      uint64_t n_bytes, int add_bos, int add_eos, void* hip_stream, void** d_ids,
-                                      void** d_out_offsets, uint64_t* n_ids) {
-    if (!c) return TK_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
+static int encode_device_checked(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 int add_bos, int add_eos, int checks, void* hip_stream, void** d_ids, void** d_out_offsets,
+                                 uint64_t* n_ids);
+
+// (the body of tk_encode_batch_device; the caller holds c->mu)
+static int encode_device(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, int add_bos,
+                         int add_eos, void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids) {
     if (!d_doc_offsets || (!d_bytes && n_bytes) || !d_ids || !d_out_offsets || !n_ids) {
         c->err = "null argument";
         return TK_ERR_INVALID_ARG;
@@ -1002,6 +1007,14 @@ extern "C" int tk_encode_batch_device(tk_ctx* c, const void* d_bytes, const void
     return TK_OK;
 }
 
+extern "C" int tk_encode_batch_device(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs,
+                                      uint64_t n_bytes, int add_bos, int add_eos, void* hip_stream, void** d_ids,
+                                      void** d_out_offsets, uint64_t* n_ids) {
+    if (!c) return TK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    return encode_device(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, hip_stream, d_ids, d_out_offsets, n_ids);
+}
+
 // The same entry with the checks a host caller gets from tk_encode_batch ("C callers get a `validate` flag"):
 // TK_CHECK_OFFSETS -- d_doc_offsets[0] == 0, non-decreasing, [n_docs] == n_bytes, or TK_ERR_INVALID_ARG (without it a bad offset
 // array is out-of-bounds indexing on the device); TK_CHECK_UTF8 -- every document is well-formed UTF-8 on its own (which includes:
@@ -1011,9 +1024,16 @@ extern "C" int tk_encode_batch_device_ex(tk_ctx* c, const void* d_bytes, const v
                                          uint64_t n_bytes, int add_bos, int add_eos, int checks, void* hip_stream, void** d_ids,
                                          void** d_out_offsets, uint64_t* n_ids) {
     if (!c) return TK_ERR_INVALID_ARG;
-    if (checks & ~(TK_CHECK_OFFSETS | TK_CHECK_UTF8)) { std::lock_guard<std::mutex> lock(c->mu); c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (checks & ~(TK_CHECK_OFFSETS | TK_CHECK_UTF8)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    return encode_device_checked(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, hip_stream, d_ids, d_out_offsets, n_ids);
+}
+
+// (the body of tk_encode_batch_device_ex; the caller holds c->mu and has refused unknown flags)
+static int encode_device_checked(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 int add_bos, int add_eos, int checks, void* hip_stream, void** d_ids, void** d_out_offsets,
+                                 uint64_t* n_ids) {
     if (checks) {
-        std::lock_guard<std::mutex> lock(c->mu);
         if (!d_doc_offsets || (!d_bytes && n_bytes)) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
         if (n_docs >= 0xFFFFFFF0ull) { c->err = "too many documents in one batch"; return TK_ERR_INVALID_ARG; }
         TK_HIP(c, hipSetDevice(c->device));
@@ -1033,7 +1053,7 @@ extern "C" int tk_encode_batch_device_ex(tk_ctx* c, const void* d_bytes, const v
             if (bad) { c->err = std::to_string(bad) + " document(s) are not valid UTF-8"; return TK_ERR_INVALID_UTF8; }
         }
     }
-    return tk_encode_batch_device(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, hip_stream, d_ids, d_out_offsets, n_ids);
+    return encode_device(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, hip_stream, d_ids, d_out_offsets, n_ids);
 }
 
 static int check_offsets(tk_ctx* c, const uint64_t* doc_offsets, uint64_t n_docs) {
@@ -1154,10 +1174,18 @@ extern "C" int tk_encode_one(tk_ctx* c, const uint8_t* text, uint64_t len, int a
     return TK_OK;
 }
 
-extern "C" int tk_encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs,
-                               int add_bos, int add_eos, int validate_utf8, tk_result* out) {
-    if (!c) return TK_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> lock(c->mu);
+// Where the device copy of a host batch and of its result lives once encode_batch returns (the spans pass reads them): the
+// context's staging buffers, or -- one-launch small path -- the mapped pinned buffers the small kernel read and wrote.
+struct DevBatch {
+    const uint8_t* bytes = nullptr;
+    const uint64_t* doc_offs = nullptr;
+    const uint32_t* ids = nullptr;
+    const uint64_t* id_offs = nullptr;
+};
+
+// (the body of tk_encode_batch; the caller holds c->mu.  dev: optional)
+static int encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                        int validate_utf8, tk_result* out, DevBatch* dev) {
     if (!doc_offsets || !out || (!bytes && doc_offsets[n_docs])) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
     if (n_docs >= 0xFFFFFFF0ull) { c->err = "too many documents in one batch"; return TK_ERR_INVALID_ARG; }
     memset(out, 0, sizeof(*out));
@@ -1186,6 +1214,12 @@ extern "C" int tk_encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* 
             if (n_ids) memcpy(h_ids, c->hs_out, n_ids * 4);
             memcpy(h_offs, c->hs_out + TK_SMALL_OUT_OFFS_WORD, (n_docs + 1) * 8);
             out->ids = h_ids; out->offsets = h_offs; out->n_ids = n_ids; out->n_docs = n_docs;
+            if (dev) {
+                dev->bytes = (const uint8_t*)c->ds_in;
+                dev->doc_offs = (const uint64_t*)((const uint8_t*)c->ds_in + TK_SMALL_MAX_BYTES);
+                dev->ids = (const uint32_t*)c->ds_out;
+                dev->id_offs = (const uint64_t*)((const uint32_t*)c->ds_out + TK_SMALL_OUT_OFFS_WORD);
+            }
             return TK_OK;
         }
     }
@@ -1223,7 +1257,20 @@ extern "C" int tk_encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* 
     out->offsets = h_offs;
     out->n_ids = n_ids;
     out->n_docs = n_docs;
+    if (dev) {
+        dev->bytes = (const uint8_t*)c->in_bytes.p;
+        dev->doc_offs = (const uint64_t*)c->in_offs.p;
+        dev->ids = (const uint32_t*)c->out_ids.p;
+        dev->id_offs = (const uint64_t*)c->out_offs.p;
+    }
     return TK_OK;
+}
+
+extern "C" int tk_encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs,
+                               int add_bos, int add_eos, int validate_utf8, tk_result* out) {
+    if (!c) return TK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    return encode_batch(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, out, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1512,6 +1559,27 @@ extern "C" int tk_ctx_set_special_tokens(tk_ctx* c, const uint8_t* blob, const u
     return TK_OK;
 }
 
+// The decode kernels' tables, built at the first decode or spans call on the context: by rank, the token's bytes and length in
+// ONE 16-byte entry (tokens of up to 15 bytes), and the length alone in a byte
+static int token_tables(tk_ctx* c) {
+    if (c->t_inline.p) return TK_OK;
+    const TkHostTables& h = c->host;
+    std::vector<uint8_t> inl((size_t)h.n_ranks * 16 + 16, 0), l8((size_t)h.n_ranks + 16, 0);
+    for (uint32_t r = 0; r < h.n_ranks; ++r) {
+        const uint32_t len = h.offs[r + 1] - h.offs[r];
+        l8[r] = (uint8_t)(len < 255u ? len : 255u);
+        if (len <= 15u) {
+            memcpy(&inl[(size_t)r * 16], h.blob.data() + h.offs[r], len);
+            inl[(size_t)r * 16 + 15] = (uint8_t)len;
+        } else {
+            inl[(size_t)r * 16 + 15] = 0xFFu;
+        }
+    }
+    int rcu;
+    if ((rcu = upload(c, c->t_inline, inl.data(), inl.size())) || (rcu = upload(c, c->t_len8, l8.data(), l8.size()))) return rcu;
+    return TK_OK;
+}
+
 static int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, int policy,
                       hipStream_t s, uint64_t* n_bytes, uint64_t* bad_doc) {
     if (policy < TK_POLICY_IGNORE || policy > TK_POLICY_RAISE) { c->err = "invalid policy"; return TK_ERR_INVALID_ARG; }
@@ -1524,23 +1592,8 @@ static int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
     TK_HIP(c, c->dec_err.reserve(64));
     TK_HIP(c, c->dec_hi.reserve((n_docs + 1) * 4));
     TK_HIP(c, c->block_sums.reserve((n_docs / 2048 + 4) * 8));
-    if (!c->t_inline.p) {
-        // by rank: the token's bytes and length in ONE 16-byte entry (tokens of up to 15 bytes), and the length alone in a byte
-        const TkHostTables& h = c->host;
-        std::vector<uint8_t> inl((size_t)h.n_ranks * 16 + 16, 0), l8((size_t)h.n_ranks + 16, 0);
-        for (uint32_t r = 0; r < h.n_ranks; ++r) {
-            const uint32_t len = h.offs[r + 1] - h.offs[r];
-            l8[r] = (uint8_t)(len < 255u ? len : 255u);
-            if (len <= 15u) {
-                memcpy(&inl[(size_t)r * 16], h.blob.data() + h.offs[r], len);
-                inl[(size_t)r * 16 + 15] = (uint8_t)len;
-            } else {
-                inl[(size_t)r * 16 + 15] = 0xFFu;
-            }
-        }
-        int rcu;
-        if ((rcu = upload(c, c->t_inline, inl.data(), inl.size())) || (rcu = upload(c, c->t_len8, l8.data(), l8.size()))) return rcu;
-    }
+    int rct = token_tables(c);
+    if (rct != TK_OK) return rct;
     TkDecodeArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = d_ids;
@@ -1723,3 +1776,155 @@ extern "C" void tk_free_text_result(tk_text_result* r) {
     tk_pinned_put(r->offsets);
     memset(r, 0, sizeof(*r));
 }
+
+// ------------------------------------------------------------------------------------------
+// per-token byte spans (include/tekken_hip.h tk_token_spans_device; csrc/tk_spans.hip)
+// ------------------------------------------------------------------------------------------
+
+// the document whose id range holds id index idx: binary search on the device offsets (error path only; the offsets may be
+// mapped pinned memory -- the small path's)
+static int doc_of_id(tk_ctx* c, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t idx, uint64_t* out) {
+    uint64_t lo = 0, hi = n_docs;
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) / 2, v = 0;
+        TK_HIP(c, hipMemcpy(&v, d_id_offs + mid + 1, 8, hipMemcpyDefault));
+        if (v <= idx) lo = mid + 1; else hi = mid;
+    }
+    *out = lo;
+    return TK_OK;
+}
+
+// The spans pass over ids on the device: (start, end) of every id into c->sp_spans, the checks of `checks` (TK_SPANS_CHECK_*
+// only) in the same pass, one host wait for the error words.  The caller holds c->mu.
+static int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids,
+                     const uint64_t* d_doc_offs, const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc) {
+    if (checks & TK_SPANS_CHECK_BYTES) checks |= TK_SPANS_CHECK_COVER;
+    if (((checks & TK_SPANS_CHECK_COVER) && !d_doc_offs) || ((checks & TK_SPANS_CHECK_BYTES) && !d_bytes)) {
+        c->err = "the spans checks need the document offsets (COVER) and the text (BYTES)";
+        return TK_ERR_INVALID_ARG;
+    }
+    int rc = token_tables(c);
+    if (rc != TK_OK) return rc;
+    TK_HIP(c, c->sp_spans.reserve(n_ids * 8 + 16));
+    TK_HIP(c, c->sp_err.reserve(64));
+    TkSpansArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ids = d_ids;
+    a.id_offs = d_id_offs;
+    a.n_docs = n_docs;
+    a.doc_offs = d_doc_offs;
+    a.bytes = d_bytes;
+    a.spans = (uint32_t*)c->sp_spans.p;
+    a.err = (unsigned long long*)c->sp_err.p;
+    a.tok_blob = (const uint8_t*)c->t_blob.p;
+    a.tok_offs = (const uint32_t*)c->t_offs.p;
+    a.tok_inline = (const uint8_t*)c->t_inline.p;
+    a.tok_len8 = (const uint8_t*)c->t_len8.p;
+    a.n_ranks = c->host.n_ranks;
+    a.num_special = c->host.num_special;
+    unsigned long long err[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    TK_HIP(c, hipMemsetAsync(c->sp_err.p, 0xFF, 32, s));
+    TK_HIP(c, tk_launch_spans(a, checks, s));
+    TK_HIP(c, hipMemcpyAsync(err, c->sp_err.p, 32, hipMemcpyDeviceToHost, s));
+    TK_HIP(c, hipStreamSynchronize(s));
+    if (err[0] == ~0ull && err[1] == ~0ull && err[2] == ~0ull && err[3] == ~0ull) return TK_OK;
+    // error path: name the first document that fails and say why
+    const TkHostTables& h = c->host;
+    uint64_t first = err[0];
+    for (int k = 1; k < 4; ++k) {
+        if (err[k] == ~0ull) continue;
+        uint64_t d = 0;
+        if ((rc = doc_of_id(c, d_id_offs, n_docs, err[k], &d)) != TK_OK) return rc;
+        if (k >= 2 || d < first) first = d;
+        if (k == 2) {
+            uint32_t id = 0;
+            TK_HIP(c, hipMemcpy(&id, d_ids + err[2], 4, hipMemcpyDefault));
+            if (bad_doc) *bad_doc = d;
+            c->err = "spans: id " + std::to_string(id) + " (document " + std::to_string(d) + ") is outside the vocabulary";
+            return TK_ERR_RUNTIME;
+        }
+        if (k == 3) {
+            if (bad_doc) *bad_doc = d;
+            c->err = "spans: document " + std::to_string(d) + " reaches 2^32 bytes (spans are uint32 offsets)";
+            return TK_ERR_INVALID_ARG;
+        }
+    }
+    if (bad_doc) *bad_doc = first;
+    // the two lengths: what the ids of the document cover, and the document itself
+    uint64_t range[2] = {0, 0}, text[2] = {0, 0};
+    TK_HIP(c, hipMemcpy(range, d_id_offs + first, 16, hipMemcpyDefault));
+    TK_HIP(c, hipMemcpy(text, d_doc_offs + first, 16, hipMemcpyDefault));
+    std::vector<uint32_t> hid((size_t)(range[1] - range[0]));
+    if (!hid.empty()) TK_HIP(c, hipMemcpy(hid.data(), d_ids + range[0], hid.size() * 4, hipMemcpyDefault));
+    uint64_t covered = 0;
+    for (uint32_t id : hid)
+        if (id >= h.num_special) covered += h.offs[id - h.num_special + 1] - h.offs[id - h.num_special];
+    const std::string lens = "the ids cover " + std::to_string(covered) + " bytes, the document has " + std::to_string(text[1] - text[0]);
+    if (err[0] == first) c->err = "spans: document " + std::to_string(first) + " is not covered by its ids: " + lens;
+    else c->err = "spans: in document " + std::to_string(first) + " the token bytes of id index " + std::to_string(err[1] - range[0]) +
+                  " differ from the text under its span (" + lens + ")";
+    return TK_ERR_RUNTIME;
+}
+
+extern "C" int tk_token_spans_device(tk_ctx* c, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                                     const void* d_doc_offsets, const void* d_bytes, int checks, void* hip_stream, void** d_spans,
+                                     uint64_t* bad_doc) {
+    if (!c) return TK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (checks & ~(TK_SPANS_CHECK_COVER | TK_SPANS_CHECK_BYTES)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    if (!d_id_offsets || (!d_ids && n_ids) || !d_spans) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    TK_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)hip_stream;  // NULL = HIP's null stream: ordered after the caller's own work on it
+    int rc = run_spans(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_docs, n_ids, (const uint64_t*)d_doc_offsets,
+                       (const uint8_t*)d_bytes, checks, s, bad_doc);
+    if (rc != TK_OK) return rc;
+    *d_spans = c->sp_spans.p;
+    return TK_OK;
+}
+
+extern "C" int tk_encode_batch_device_spans(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs,
+                                            uint64_t n_bytes, int add_bos, int add_eos, int checks, void* hip_stream, void** d_ids,
+                                            void** d_out_offsets, void** d_spans, uint64_t* n_ids, uint64_t* bad_doc) {
+    if (!c) return TK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    const int enc = TK_CHECK_OFFSETS | TK_CHECK_UTF8, sp = TK_SPANS_CHECK_COVER | TK_SPANS_CHECK_BYTES;
+    if (checks & ~(enc | sp)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    if (!d_spans) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    int rc = encode_device_checked(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks & enc, hip_stream, d_ids,
+                                   d_out_offsets, n_ids);
+    if (rc != TK_OK) return rc;
+    rc = run_spans(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, *n_ids, (const uint64_t*)d_doc_offsets,
+                   (const uint8_t*)d_bytes, checks & sp, (hipStream_t)hip_stream, bad_doc);
+    if (rc != TK_OK) return rc;
+    *d_spans = c->sp_spans.p;
+    return TK_OK;
+}
+
+extern "C" int tk_encode_batch_spans(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
+                                     int add_eos, int validate_utf8, int checks, tk_result* out, uint32_t** spans, uint64_t* bad_doc) {
+    if (!c) return TK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(c->mu);
+    if (checks & ~(TK_SPANS_CHECK_COVER | TK_SPANS_CHECK_BYTES)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    if (!spans) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    *spans = nullptr;
+    DevBatch dev;
+    int rc = encode_batch(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, out, &dev);
+    if (rc != TK_OK) return rc;
+    // (the small path's ids, offsets and text are mapped pinned memory: the spans kernel reads them there)
+    rc = run_spans(c, dev.ids, dev.id_offs, n_docs, out->n_ids, dev.doc_offs, dev.bytes, checks, c->stream, bad_doc);
+    uint32_t* h = rc == TK_OK ? (uint32_t*)tk_pinned_get(out->n_ids ? out->n_ids * 8 : 1) : nullptr;
+    if (rc == TK_OK && !h) { c->err = "hipHostMalloc failed"; rc = TK_ERR_RUNTIME; }
+    hipError_t e = hipSuccess;
+    if (rc == TK_OK && out->n_ids) e = hipMemcpyAsync(h, c->sp_spans.p, out->n_ids * 8, hipMemcpyDeviceToHost, c->stream);
+    if (rc == TK_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (rc == TK_OK && e != hipSuccess) { c->err = std::string("spans copy failed: ") + hipGetErrorString(e); rc = TK_ERR_RUNTIME; }
+    if (rc != TK_OK) {
+        tk_pinned_put(h);
+        tk_free_result(out);
+        return rc;
+    }
+    *spans = h;
+    return TK_OK;
+}
+
+extern "C" void tk_free_spans(uint32_t* spans) { tk_pinned_put(spans); }

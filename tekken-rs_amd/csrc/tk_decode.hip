@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tk_dpp_scan.h"
 #include "tk_kernels.h"
 #include "tk_utf8_swar.h"
 
@@ -44,19 +45,6 @@ __device__ __forceinline__ uint32_t tkd_piece(const TkDecodeArgs& a, uint32_t id
 __device__ __forceinline__ uint32_t tkd_wave_sum(uint32_t v) {
     for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d);
     return v;
-}
-
-// inclusive prefix sum over the 64 lanes (DPP row shifts + row broadcasts: VALU only; six ds_bpermute round trips of
-// __shfl_up were a third of a step's latency)
-__device__ __forceinline__ uint32_t tkd_scan_incl(uint32_t v) {
-    uint32_t x = v;
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);
-    return x;
 }
 
 #define TKD_DOCS TK_DECODE_GROUP_DOCS          /* consecutive documents a wave takes as one stream of ids */

@@ -95,6 +95,23 @@ hipError_t tk_launch_decode_grouplen(const TkDecodeArgs& a, hipStream_t s);   //
 hipError_t tk_launch_decode_emit(const TkDecodeArgs& a, hipStream_t s);
 hipError_t tk_launch_decode_validate(const TkDecodeArgs& a, hipStream_t s);
 
+// ---- per-token byte spans (tk_spans.hip) ----
+struct TkSpansArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const uint64_t* id_offs;   // [n_docs + 1]
+    uint64_t n_docs;
+    const uint64_t* doc_offs;  // [n_docs + 1] text offsets (TK_SPANS_CHECK_COVER / _BYTES only)
+    const uint8_t* bytes;      // the packed text (TK_SPANS_CHECK_BYTES only)
+    uint32_t* spans;           // [2 * n_ids] (start, end) per id, relative to the start of its document
+    unsigned long long* err;   // [4] see tk_spans.hip
+    const uint8_t* tok_blob;   // token bytes by rank
+    const uint32_t* tok_offs;  // [n_ranks + 1]
+    const uint8_t* tok_inline; // [n_ranks] 16-byte entries (TkDecodeArgs::tok_inline)
+    const uint8_t* tok_len8;   // [n_ranks] one-byte lengths (TkDecodeArgs::tok_len8)
+    uint32_t n_ranks, num_special;
+};
+hipError_t tk_launch_spans(const TkSpansArgs& a, int checks, hipStream_t s);
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
