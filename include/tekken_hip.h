@@ -210,6 +210,64 @@ int tk_encode_batch_spans(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc
                           int add_eos, int validate_utf8, int checks, tk_result* out, uint32_t** spans, uint64_t* bad_doc);
 void tk_free_spans(uint32_t* spans);
 
+/* ---- model-ready dense batches: truncation, padding, mask, and back (no reference equivalent: pad_id(), src/tekkenizer.rs:304,
+ * is all the reference has) ----
+ * Input: the ragged ids R_d = ids[oo[d] : oo[d+1]], n_d = len(R_d), d < D; options max_length T (0 = no limit), multiple_of m
+ * (0 = none), pad_id, keep_head h, keep_tail t and the flags below.
+ *   1. lim = T if T > 0, else unbounded.
+ *   2. Kept ids K_d: n_d <= lim: K_d = R_d.  Otherwise, truncating on the right (default), K_d = R_d[: lim - t] + R_d[n_d - t :];
+ *      with TK_DENSE_TRUNC_LEFT, K_d = R_d[: h] + R_d[n_d - (lim - h) :].  len(K_d) = min(n_d, lim); the first h / last t ids of a
+ *      document survive truncation (the fused encode entries set h = add_bos, t = add_eos: BOS and EOS are kept and the text
+ *      between them is cut, as HF tokenizers does).
+ *   3. Row length: L = T with TK_DENSE_FIXED (which needs T > 0), else L = min(max_d n_d, lim) (0 for an empty batch or all-empty
+ *      documents); then, if m > 0, L is rounded up to a multiple of m.  Truncation is to lim, never to the rounded L.
+ *   4. Row d of dense[D, L] is K_d followed by pad_id, or with TK_DENSE_PAD_LEFT pad_id first and K_d flush right.  mask[D, L]
+ *      (uint8, only with TK_DENSE_MASK, else NULL) is 1 under K_d, 0 under padding.  lengths[d] = len(K_d) (uint32, always).
+ *      n_truncated = number of documents with n_d > lim.  Elements are int32, or int64 with TK_DENSE_I64 (ids are < 2^31).
+ *   5. TK_ERR_INVALID_ARG, nothing written, an earlier dense result stays readable: T > 0 and (t > T truncating right, h > T
+ *      truncating left; in the fused entries add_bos + add_eos > T); TK_DENSE_FIXED with T == 0; an unknown flag; a tensor
+ *      beyond the bounds L < 2^31 and D * L <= 2^36 elements.  A failed allocation is TK_ERR_RUNTIME.
+ * The layout is a separate pass behind the unchanged encode pipeline (csrc/tk_dense.hip): every element is written once, pad
+ * included, in 16-byte stores where L is a multiple of 4 (element stores otherwise: pad to a multiple of 4 for the fast form).
+ * The longest-row mode reads max_d n_d back (8 bytes) before it can size the tensor; TK_DENSE_FIXED needs no read before the
+ * launch.  TK_DENSE_NT=1 in the environment (read at a context's first dense call) makes the 16-byte stores non-temporal: the
+ * A / B behind the default of plain stores (DESIGN 4.5c has the figures); it never changes a value. */
+#define TK_DENSE_PAD_LEFT 1
+#define TK_DENSE_TRUNC_LEFT 2
+#define TK_DENSE_FIXED 4
+#define TK_DENSE_I64 8
+#define TK_DENSE_MASK 16
+typedef struct tk_dense_opts { uint32_t max_length, multiple_of, pad_id, keep_head, keep_tail, flags; } tk_dense_opts;
+typedef struct tk_dense { void* ids; uint8_t* mask; uint32_t* lengths; uint64_t n_docs, row_len, n_truncated; } tk_dense;
+/* ids already on the device (encode's own outputs or the caller's; d_id_offsets: n_docs + 1 uint64, well-formed) -> dense.
+ * out's buffers are device buffers owned by the context, valid until the next dense call on it, and SEPARATE from the encode
+ * and spans outputs: an earlier encode's d_ids / d_out_offsets stay valid through this call.  The work is enqueued on hip_stream
+ * and the call returns after the stream has drained.  This entry does NOT check d_id_offsets (the fused entry below takes
+ * TK_CHECK_OFFSETS for its text offsets; the id offsets it passes on are encode's own): a decreasing pair or an offset beyond
+ * n_ids is out-of-bounds indexing on the device. */
+int tk_dense_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                             const tk_dense_opts* opts, void* hip_stream, tk_dense* out);
+/* tk_encode_batch_device_ex + the dense pass on the same stream.  keep_head / keep_tail of opts are ignored and set from
+ * add_bos / add_eos; the ragged outputs (*d_ids / *d_out_offsets / *n_ids as tk_encode_batch_device) are returned as well. */
+int tk_encode_batch_device_dense(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 int add_bos, int add_eos, int checks, const tk_dense_opts* opts, void* hip_stream,
+                                 void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_dense* out);
+/* Host in / host out: tk_encode_batch + the dense pass (batches of the one-launch small path included).  out's buffers are
+ * pinned host memory, released with tk_free_dense (out->mask is NULL without TK_DENSE_MASK). */
+int tk_encode_batch_dense(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
+                          int add_eos, int validate_utf8, const tk_dense_opts* opts, tk_dense* out);
+void tk_free_dense(tk_dense* out);
+/* The inverse: dense rows on the device -> ragged ids + offsets.  flags: TK_DENSE_I64 (the element type), TK_DENSE_PAD_LEFT.
+ * lengths[d] comes from d_lengths (n_docs uint32, clamped to row_len), or, when d_lengths is NULL, is row_len minus the maximal
+ * run of pad_id at the padded end of the row (the right end, or the left with TK_DENSE_PAD_LEFT); R_d is the lengths[d] ids at
+ * the unpadded end, the offsets their exclusive prefix sum.  ragged(dense(x)) == x whenever nothing was truncated and pad_id does
+ * not end (begin) a document -- encode never emits <pad>.  *d_ids (uint32) / *d_id_offsets (n_docs + 1 uint64) are owned by the
+ * context and apart from the decode buffers: valid through a following tk_decode_batch_device on the same context, until the
+ * next call of this entry. */
+int tk_ragged_from_dense_device(tk_ctx* ctx, const void* d_dense, uint64_t n_docs, uint64_t row_len, int flags,
+                                const void* d_lengths, uint32_t pad_id, void* hip_stream, void** d_ids,
+                                void** d_id_offsets, uint64_t* n_ids);
+
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token
  * at POSITION i of the reference's all_special_tokens vector (src/tekkenizer.rs:108-116, 536-540);

@@ -41,6 +41,31 @@ pub const TK_ERR_SPECIAL_POLICY: c_int = -10;
 pub const TK_SPANS_CHECK_COVER: c_int = 4;
 pub const TK_SPANS_CHECK_BYTES: c_int = 8;
 
+// model-ready dense batches (tk_dense_opts.flags; include/tekken_hip.h has the definition)
+pub const TK_DENSE_PAD_LEFT: u32 = 1;
+pub const TK_DENSE_TRUNC_LEFT: u32 = 2;
+pub const TK_DENSE_FIXED: u32 = 4;
+pub const TK_DENSE_I64: u32 = 8;
+pub const TK_DENSE_MASK: u32 = 16;
+#[repr(C)]
+pub struct TkDenseOpts {
+    pub max_length: u32,
+    pub multiple_of: u32,
+    pub pad_id: u32,
+    pub keep_head: u32,
+    pub keep_tail: u32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkDense {
+    pub ids: *mut c_void,
+    pub mask: *mut u8,
+    pub lengths: *mut u32,
+    pub n_docs: u64,
+    pub row_len: u64,
+    pub n_truncated: u64,
+}
+
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
     pub fn tk_ctx_create(token_bytes: *const u8, token_offsets: *const u32, n_ranks: u32, num_special_tokens: u32, bos_id: u32,
@@ -74,6 +99,18 @@ extern "C" {
     pub fn tk_tokenizer_encode_with_spans(t: *mut TkTokenizer, text: *const c_char, len: usize, add_bos: c_int, add_eos: c_int,
                                           ids: *mut *mut u32, spans: *mut *mut u32, n_ids: *mut usize) -> c_int;
     pub fn tk_free_ids(ids: *mut u32);
+    // dense batches: ragged ids -> dense[D, L] (+ mask, lengths, truncated count), fused with encode, host form, and the inverse
+    pub fn tk_dense_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                    opts: *const TkDenseOpts, hip_stream: *mut c_void, out: *mut TkDense) -> c_int;
+    pub fn tk_encode_batch_device_dense(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                        add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkDenseOpts, hip_stream: *mut c_void,
+                                        d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkDense) -> c_int;
+    pub fn tk_encode_batch_dense(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                 validate_utf8: c_int, opts: *const TkDenseOpts, out: *mut TkDense) -> c_int;
+    pub fn tk_free_dense(out: *mut TkDense);
+    pub fn tk_ragged_from_dense_device(ctx: *mut TkCtx, d_dense: *const c_void, n_docs: u64, row_len: u64, flags: c_int,
+                                       d_lengths: *const c_void, pad_id: u32, hip_stream: *mut c_void, d_ids: *mut *mut c_void,
+                                       d_id_offsets: *mut *mut c_void, n_ids: *mut u64) -> c_int;
     // memo of merged pieces (round 4): a device table {unknown piece of 2..16 bytes -> its <= 4 ids}; never changes an id
     pub fn tk_ctx_set_memo(ctx: *mut TkCtx, log2_entries: c_int, policy: c_int) -> c_int;
     pub fn tk_ctx_memo_clear(ctx: *mut TkCtx) -> c_int;

@@ -147,6 +147,34 @@ impl HipEngine {
         };
         Ok(out)
     }
+
+    /// Model-ready batch (tk_encode_batch_dense): `(input_ids [B * L] row-major, attention_mask [B * L], lengths [B], L)`.  Rows longer
+    /// than `max_length` (0 = no limit) are cut on the right with BOS / EOS kept; `fixed`: L = `max_length`, else the longest kept
+    /// row; rows are filled with `pad_id` on the right.  Ids are < 2^31, so `i32` holds them.
+    pub fn encode_batch_padded(&self, docs: &[&str], add_bos: bool, add_eos: bool, max_length: u32, fixed: bool, pad_id: u32)
+                               -> Result<(Vec<i32>, Vec<u8>, Vec<u32>, usize), HipError> {
+        let (bytes, offs) = pack_docs(docs);
+        let opts = TkDenseOpts { max_length, multiple_of: 0, pad_id, keep_head: 0, keep_tail: 0,
+                                 flags: TK_DENSE_MASK | if fixed { TK_DENSE_FIXED } else { 0 } };
+        let mut d = TkDense { ids: std::ptr::null_mut(), mask: std::ptr::null_mut(), lengths: std::ptr::null_mut(), n_docs: 0, row_len: 0,
+                              n_truncated: 0 };
+        let rc = unsafe {
+            tk_encode_batch_dense(self.ctx, bytes.as_ptr(), offs.as_ptr(), docs.len() as u64, add_bos as c_int, add_eos as c_int, 0, &opts, &mut d)
+        };
+        if rc != TK_OK {
+            return Err(map_err(rc, unsafe { tk_last_error(self.ctx) }));
+        }
+        let n = (d.n_docs * d.row_len) as usize;
+        let out = unsafe {
+            let ids = std::slice::from_raw_parts(d.ids as *const i32, n).to_vec();
+            let mask = std::slice::from_raw_parts(d.mask as *const u8, n).to_vec();
+            let lengths = std::slice::from_raw_parts(d.lengths as *const u32, d.n_docs as usize).to_vec();
+            let row_len = d.row_len as usize;
+            tk_free_dense(&mut d);
+            (ids, mask, lengths, row_len)
+        };
+        Ok(out)
+    }
 }
 impl Drop for HipEngine {
     fn drop(&mut self) {

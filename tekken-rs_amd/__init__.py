@@ -29,6 +29,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 TK_OK = 0
 CHECK_OFFSETS, CHECK_UTF8 = 1, 2   # tk_encode_batch_device_ex
 SPANS_CHECK_COVER, SPANS_CHECK_BYTES = 4, 8   # the spans entries (tk_token_spans_device, tk_encode_batch_*spans)
+DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
 TK_ERR_INVALID_UTF8 = -3
@@ -69,6 +70,16 @@ class _TextResult(ctypes.Structure):
 class _Result(ctypes.Structure):
     _fields_ = [("ids", ctypes.POINTER(ctypes.c_uint32)), ("offsets", ctypes.POINTER(ctypes.c_uint64)),
                 ("n_ids", ctypes.c_uint64), ("n_docs", ctypes.c_uint64)]
+
+
+class _DenseOpts(ctypes.Structure):
+    _fields_ = [("max_length", ctypes.c_uint32), ("multiple_of", ctypes.c_uint32), ("pad_id", ctypes.c_uint32),
+                ("keep_head", ctypes.c_uint32), ("keep_tail", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class _Dense(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("lengths", ctypes.c_void_p),
+                ("n_docs", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_truncated", ctypes.c_uint64)]
 
 
 _LIB = None
@@ -250,6 +261,20 @@ def lib():
         L.tk_tokenizer_encode_with_spans.restype = ctypes.c_int
         L.tk_tokenizer_encode_with_spans.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u32p),
                                                      ctypes.POINTER(u32p), ctypes.POINTER(ctypes.c_size_t)]
+    if hasattr(L, "tk_dense_from_ids_device"):   # (dense batches: libraries built before them still load through TK_HIP_LIB)
+        op, dp = ctypes.POINTER(_DenseOpts), ctypes.POINTER(_Dense)
+        L.tk_dense_from_ids_device.restype = ctypes.c_int
+        L.tk_dense_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, op, vp, dp]
+        L.tk_encode_batch_device_dense.restype = ctypes.c_int
+        L.tk_encode_batch_device_dense.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, dp]
+        L.tk_encode_batch_dense.restype = ctypes.c_int
+        L.tk_encode_batch_dense.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, dp]
+        L.tk_free_dense.restype = None
+        L.tk_free_dense.argtypes = [dp]
+        L.tk_ragged_from_dense_device.restype = ctypes.c_int
+        L.tk_ragged_from_dense_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, ctypes.c_uint32, vp,
+                                                  ctypes.POINTER(vp), ctypes.POINTER(vp), u64p]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -289,11 +314,33 @@ def _take_result(res):
 class DeviceView:
     """Zero-copy view of a context-owned device buffer for array libraries that understand
     `__cuda_array_interface__` (e.g. `torch.as_tensor(view, device="cuda")`).  Valid until the next
-    call on the owning context."""
+    call on the owning context.  n: the number of elements, or a shape (C-contiguous; the dense entries' [D, L])."""
 
     def __init__(self, ptr, n, typestr):
-        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr), False), "version": 2,
+        shape = tuple(int(x) for x in n) if isinstance(n, (tuple, list)) else (int(n),)
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr), False), "version": 2,
                                          "strides": None}
+
+
+def _dense_opts(max_length=0, multiple_of=0, pad_id=0, keep_head=0, keep_tail=0, flags=0):
+    return _DenseOpts(int(max_length or 0), int(multiple_of or 0), int(pad_id), int(keep_head), int(keep_tail), int(flags))
+
+
+class DenseResult:
+    """What the device dense entries return (tk_dense): raw device pointers of context-owned buffers, valid until the next dense
+    call on the context.  ids_ptr: int32 or int64 [n_docs, row_len]; mask_ptr: uint8 [n_docs, row_len] or None;
+    lengths_ptr: uint32 [n_docs] (views() shows it as int32: a length is at most row_len < 2^31)."""
+
+    def __init__(self, d, flags):
+        self.ids_ptr, self.mask_ptr, self.lengths_ptr = d.ids or 0, d.mask or None, d.lengths or 0
+        self.n_docs, self.row_len, self.n_truncated = int(d.n_docs), int(d.row_len), int(d.n_truncated)
+        self.typestr = "<i8" if flags & DENSE_I64 else "<i4"
+
+    def views(self):
+        """(ids view [n_docs, row_len], mask view or None, lengths view as int32 [n_docs]) -- DeviceView objects."""
+        shape = (self.n_docs, self.row_len)
+        return (DeviceView(self.ids_ptr, shape, self.typestr), DeviceView(self.mask_ptr, shape, "|u1") if self.mask_ptr else None,
+                DeviceView(self.lengths_ptr, self.n_docs, "<i4"))
 
 
 class Engine:
@@ -482,6 +529,71 @@ class Engine:
             e.bad_doc = int(bad.value)
             raise e
         return d_ids.value, d_oo.value, d_sp.value, int(n.value)
+
+    def dense_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, max_length=0, multiple_of=0, pad_id=0, keep_head=0,
+                              keep_tail=0, flags=0, stream=0):
+        """tk_dense_from_ids_device: ragged ids resident in HBM -> dense[n_docs, row_len] (+ mask with DENSE_MASK, lengths, the
+        truncated count); the definition is in include/tekken_hip.h.  Returns a DenseResult (context-owned device buffers,
+        apart from the encode and spans outputs)."""
+        o, d = _dense_opts(max_length, multiple_of, pad_id, keep_head, keep_tail, flags), _Dense()
+        rc = _need("tk_dense_from_ids_device")(self._h, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                                               ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(d))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return DenseResult(d, int(flags))
+
+    def encode_batch_device_dense(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, max_length=0, multiple_of=0,
+                                  pad_id=0, flags=0, checks=0, stream=0):
+        """tk_encode_batch_device_dense: encode_batch_device + the dense pass on the same stream; BOS / EOS survive truncation.
+        Returns (d_ids_ptr, d_out_offs_ptr, n_ids, DenseResult), all context-owned."""
+        o, d = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags), _Dense()
+        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        rc = _need("tk_encode_batch_device_dense")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                                                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                                                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(d))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return d_ids.value, d_oo.value, int(n.value), DenseResult(d, int(flags))
+
+    def encode_batch_dense(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, max_length=0, multiple_of=0, pad_id=0,
+                           flags=0):
+        """tk_encode_batch_dense, host in / host out: (dense int32 or int64 [D, L], mask uint8 [D, L] or None, lengths uint32 [D]);
+        .n_truncated of the call is kept in self.last_n_truncated."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        o, d = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags), _Dense()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        rc = _need("tk_encode_batch_dense")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                                            int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(d))
+        if rc != TK_OK:
+            raise self._err(rc)
+        D, L = int(d.n_docs), int(d.row_len)
+        dt = np.int64 if flags & DENSE_I64 else np.int32
+
+        def take(ptr, n, dtype):
+            if n == 0:
+                return np.zeros(0, dtype)
+            raw = (ctypes.c_uint8 * (n * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(raw, dtype=dtype, count=n).copy()
+
+        dense = take(d.ids, D * L, dt).reshape(D, L)
+        mask = take(d.mask, D * L, np.uint8).reshape(D, L) if d.mask else None
+        lengths = take(d.lengths, D, np.uint32)
+        self.last_n_truncated = int(d.n_truncated)
+        lib().tk_free_dense(ctypes.byref(d))
+        return dense, mask, lengths
+
+    def ragged_from_dense_device(self, d_dense_ptr, n_docs, row_len, flags=0, d_lengths_ptr=0, pad_id=0, stream=0):
+        """tk_ragged_from_dense_device: dense rows in HBM (int32, or int64 with DENSE_I64; DENSE_PAD_LEFT) -> (d_ids_ptr,
+        d_id_offs_ptr, n_ids), context-owned and valid through a following decode_batch_device.  d_lengths_ptr (uint32[n_docs]) 0:
+        the run of pad_id at the padded end of every row is trimmed."""
+        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        rc = _need("tk_ragged_from_dense_device")(self._h, ctypes.c_void_p(d_dense_ptr or None), n_docs, row_len, int(flags),
+                                                  ctypes.c_void_p(d_lengths_ptr or None), int(pad_id), ctypes.c_void_p(stream),
+                                                  ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return d_ids.value, d_oo.value, int(n.value)
 
     def encode_batch_device_views(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, stream=0):
         """Same, returning (ids view as int32[n_ids], offsets view as int64[n_docs+1])."""
@@ -769,6 +881,82 @@ class Tekkenizer:
         ids, oo, spans = eng.encode_batch_spans(data, offs, add_bos, add_eos, checks=checks)
         return [(ids[int(oo[d]):int(oo[d + 1])].tolist(), [tuple(x) for x in spans[int(oo[d]):int(oo[d + 1])].tolist()])
                 for d in range(len(docs))]
+
+    def _device_engine(self):
+        eng = self.engine()
+        if eng is None:
+            raise TokenizerError(TK_ERR_NO_DEVICE, "tokenizer was created without a device (host-only object)")
+        return eng
+
+    def encode_batch_padded(self, docs, add_bos=False, add_eos=False, max_length=None, padding="longest", truncation_side="right",
+                            padding_side="right", pad_to_multiple_of=None, pad_id=None, dtype="int64", return_mask=True,
+                            return_tensors="pt", copy=True):
+        """Model-ready batch (tk_encode_batch_device_dense / tk_encode_batch_dense; the definition is in include/tekken_hip.h):
+        {"input_ids": [B, L] of `dtype` ("int64" | "int32"), "attention_mask": uint8 [B, L] (None without return_mask),
+        "lengths": int32 [B] kept ids per row, "n_truncated": int}.  Rows longer than max_length are cut on truncation_side with
+        BOS / EOS kept; padding "longest": L = the longest kept row, "max_length": L = max_length; then rounded up to
+        pad_to_multiple_of.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on the tokenizer's GPU (the text goes
+        up once; copy=False returns views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
+        eng = self._device_engine()
+        if padding not in ("longest", "max_length") or truncation_side not in ("left", "right") or padding_side not in ("left", "right") \
+                or dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_padded: unknown padding / side / dtype / return_tensors value")
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        flags = (DENSE_FIXED if padding == "max_length" else 0) | (DENSE_TRUNC_LEFT if truncation_side == "left" else 0) \
+            | (DENSE_PAD_LEFT if padding_side == "left" else 0) | (DENSE_I64 if dtype == "int64" else 0) | (DENSE_MASK if return_mask else 0)
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        if return_tensors == "np":
+            dense, mask, lengths = eng.encode_batch_dense(data, offs, add_bos, add_eos, False, max_length, pad_to_multiple_of, pad, flags)
+            return {"input_ids": dense, "attention_mask": mask, "lengths": lengths.astype(np.int32), "n_truncated": eng.last_n_truncated}
+        import torch
+        d_bytes = torch.from_numpy(data if len(data) else np.zeros(1, np.uint8)).cuda()
+        d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
+        stream = torch.cuda.current_stream().cuda_stream
+        _, _, _, res = eng.encode_batch_device_dense(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos, add_eos,
+                                                     max_length, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
+        D, L = res.n_docs, res.row_len
+        tdt = torch.int64 if dtype == "int64" else torch.int32
+        v_ids, v_mask, v_len = res.views()
+
+        def wrap(view, shape, tdtype):
+            if 0 in shape:            # (nothing behind the pointer to look at)
+                return torch.empty(shape, dtype=tdtype, device="cuda")
+            t = torch.as_tensor(view, device="cuda")
+            return t.clone() if copy else t
+
+        return {"input_ids": wrap(v_ids, (D, L), tdt), "attention_mask": wrap(v_mask, (D, L), torch.uint8) if return_mask else None,
+                "lengths": wrap(v_len, (D,), torch.int32), "n_truncated": res.n_truncated}
+
+    def decode_batch_padded(self, input_ids, lengths=None, policy=SpecialTokenPolicy.Ignore, pad_id=None, padding_side="right"):
+        """Batch decode of dense rows (tk_ragged_from_dense_device + tk_decode_batch_device): input_ids [B, L], int32 or int64, a
+        torch tensor on the tokenizer's GPU or a numpy array -> list of str.  lengths (per row, optional): without them the run of
+        pad_id (None: self.pad_id()) at the padded end of every row is dropped.  Errors as decode_batch (.bad_doc)."""
+        eng = self._device_engine()
+        import torch
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        t = torch.from_numpy(np.ascontiguousarray(input_ids)) if isinstance(input_ids, np.ndarray) else input_ids
+        if t.dim() != 2 or t.dtype not in (torch.int32, torch.int64):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "decode_batch_padded: input_ids must be [B, L] of int32 or int64")
+        t = t.cuda().contiguous()
+        D, L = int(t.shape[0]), int(t.shape[1])
+        d_len = None
+        if lengths is not None:
+            d_len = torch.as_tensor(np.asarray(lengths) if not torch.is_tensor(lengths) else lengths).to(device="cuda", dtype=torch.int32).contiguous()
+            if d_len.numel() != D:
+                raise TokenizerError(TK_ERR_INVALID_ARG, "decode_batch_padded: one length per row")
+        flags = (DENSE_I64 if t.dtype == torch.int64 else 0) | (DENSE_PAD_LEFT if padding_side == "left" else 0)
+        stream = torch.cuda.current_stream().cuda_stream
+        p_ids, p_oo, n = eng.ragged_from_dense_device(t.data_ptr() if D * L else 0, D, L, flags, d_len.data_ptr() if d_len is not None and D else 0,
+                                                      pad, stream)
+        v_bytes, v_offs = eng.decode_batch_device(p_ids, p_oo, D, n, policy, stream)
+        oo = torch.as_tensor(v_offs, device="cuda").cpu().numpy()
+        total = int(oo[-1])
+        raw = torch.as_tensor(v_bytes, device="cuda").cpu().numpy().tobytes() if total else b""
+        return [raw[int(oo[d]):int(oo[d + 1])].decode("utf-8") for d in range(D)]
 
     def encode_batch(self, docs, add_bos=False, add_eos=False):
         data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])

@@ -112,6 +112,36 @@ struct TkSpansArgs {
 };
 hipError_t tk_launch_spans(const TkSpansArgs& a, int checks, hipStream_t s);
 
+// ---- model-ready dense layout (tk_dense.hip) ----
+struct TkDenseArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const uint64_t* id_offs;   // [n_docs + 1]
+    uint64_t n_docs;
+    uint32_t row_len;          // L (< 2^31)
+    uint32_t lim;              // max_length, 0xFFFFFFFF = none
+    uint32_t keep_head, keep_tail, pad_id;
+    uint32_t trunc_left, pad_left;
+    void* out;                 // [n_docs * row_len] int32 or int64
+    uint8_t* mask;             // [n_docs * row_len] or NULL
+    uint32_t* lengths;         // [n_docs] kept ids of every row
+    unsigned long long* stat;  // [0] longest document (tk_launch_dense_maxlen), [1] += truncated documents (tk_launch_dense)
+    uint32_t units, rb, magic; // the launch shape (set by the launcher): units a row, rows a block, 2^32 / units rounded up
+};
+// row_len == 0 or n_docs == 0: nothing is launched (the caller zeroes lengths).  nontemporal: the vector stores bypass the caches
+hipError_t tk_launch_dense(const TkDenseArgs& a, int i64, int nontemporal, hipStream_t s);
+hipError_t tk_launch_dense_maxlen(const uint64_t* id_offs, uint64_t n_docs, unsigned long long* stat, hipStream_t s);
+struct TkRaggedArgs {
+    const void* dense;         // [n_docs * row_len] int32 or int64
+    uint64_t n_docs;
+    uint32_t row_len, pad_id, pad_left;
+    const uint32_t* given;     // [n_docs] the caller's lengths, or NULL: trim pad_id
+    uint32_t* lens;            // [n_docs] out of tk_launch_ragged_rowlen (<= row_len), in of tk_launch_ragged_copy
+    const uint64_t* offs;      // [n_docs + 1] exclusive scan of lens
+    uint32_t* out_ids;
+};
+hipError_t tk_launch_ragged_rowlen(const TkRaggedArgs& a, int i64, hipStream_t s);
+hipError_t tk_launch_ragged_copy(const TkRaggedArgs& a, int i64, hipStream_t s);
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
