@@ -1,0 +1,215 @@
+// tk_ctx.h -- the engine's context and what the host files of the C ABI (tk_capi*.cpp, tk_pipeline.cpp) share.  Internal: only
+// they include it (tekkenizer.cpp sees tk_engine.h, tk_node.cpp the public C ABI).  Every buffer and handle of the context
+// releases itself: `delete c` is the whole of tk_ctx_destroy.
+#ifndef TK_CTX_H
+#define TK_CTX_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/tekken_hip.h"
+#include "tekkenizer.hpp"
+#include "tk_counters.h"
+#include "tk_engine.h"
+#include "tk_kernels.h"
+#include "tk_tables.h"
+
+struct DevBuf {                    // device memory that only grows; movable (the pipelined entry swaps its output sets)
+    void* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        size_t want = bytes + bytes / 8 + 256;
+        hipError_t e = hipMalloc(&p, want);
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+
+struct NoCopy { NoCopy() = default; NoCopy(const NoCopy&) = delete; NoCopy& operator=(const NoCopy&) = delete; };
+
+template <class T> struct PinBuf : NoCopy {   // a pinned host block the context owns; reads as the T* it holds
+    T* p = nullptr;
+    ~PinBuf() { release(); }
+    hipError_t alloc(size_t bytes, unsigned flags) { release(); return hipHostMalloc((void**)&p, bytes, flags); }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; }
+    operator T*() const { return p; }
+};
+
+template <class H, hipError_t (*Destroy)(H)> struct Handle : NoCopy {   // a stream or an event; reads as the handle
+    H h = nullptr;
+    ~Handle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+typedef Handle<hipStream_t, hipStreamDestroy> Stream;
+typedef Handle<hipEvent_t, hipEventDestroy> Event;
+
+// Environment knobs read ONCE, when the context is created (read_knobs, tk_capi.cpp); tk_ctx_set_memo overrides the memo pair
+struct TkKnobs {
+    bool serial_tail = false;      // TK_TAIL=serial: the tail behind the merge kernels on the one stream (A / B, tests)
+    bool no_decode_groups = false; // TK_DECODE_GROUPS=0: the per-document length pass (A / B and tests of the fall-back)
+    uint32_t decode_group_limit = 0x7FFFFF00u;   // ids / text bytes of a group from which the call falls back (TK_DECODE_GROUP_LIMIT: tests)
+    bool no_flat_long = false;     // TK_FLAT_LONG=0: pieces of 65..TKF_LONGCAP bytes hand their documents back (the round-1 behaviour; A / B and tests)
+    bool no_flat_long128 = false;  // TK_FLAT_LONG128=0: every long-piece record takes the single-wave merge
+    bool no_flat_cut = false;      // TK_FLAT_CUT=0: no cut decomposition (pieces of more than 256 bytes hand their documents back; A / B and tests)
+    uint32_t long_min = 256;       // shortest piece (bytes) merged in rounds by a workgroup (TK_LONG_MIN; 0 = never)
+    uint32_t long_lazy_mul = 0;    // TK_LONG_LAZY_MUL (0 = the default of tk_piece_is_long)
+    uint32_t long_force = 0;       // TK_LONG_FORCE (tests): 1 = every long piece through the compacting rounds, 2 = through the lazy rounds
+    uint32_t memo_log2 = 24;       // entries = 2^memo_log2 (32 bytes each: 512 MB of a 288 GB part), 0 = off; TK_MEMO_LOG2
+    int memo_policy = 0;           // 0 adaptive (pause while the hit rate is low), 1 always on; TK_MEMO_POLICY=always
+    int pipeline_forced = 0;       // TK_PIPELINE: 0 / 1 flat (default), 2 per-document kernels only
+};
+// ... and the ones read on EVERY call of the batch pipeline (call_knobs, tk_pipeline.cpp): tools set them between calls
+struct TkCallKnobs {
+    bool log = false;              // TK_DEBUG_LOG
+    bool marks = false;            // TK_DEBUG_MARKS
+    bool skip_pass2 = false;       // TK_DEBUG_SKIP_PASS2
+    int memo_log_log2 = 0;         // TK_MEMO_LOG_LOG2 (8..24; 0: the default)
+    int ablate = 0;                // TK_DEBUG_ABLATE (`make ablate` builds only)
+};
+
+struct tk_ctx {
+    int device = 0;
+    std::mutex mu;
+    std::string err;
+    TkKnobs knobs;
+    TkCallKnobs call;
+    TkHostTables host;
+    TkTablesView dview;
+    // streams: the context's own; B: the tail of a batch (documents handed back by the flat kernel) beside the merge kernels;
+    // s_in / s_out: the copy streams of tk_encode_batch_pipelined, created at its first call
+    Stream stream, stream_b, s_in, s_out;
+    Event ev[5];                   // [4]: behind the merge kernels (tk_last_merge_ms)
+    Event ev_b[3];                 // flat kernel done (A) | list of handed-back documents on the host (B) | tail done (B)
+    Event ev_in[2], ev_out[2];
+    DevBuf t_uc1, t_uc2, t_key8, t_key, t_long, t_pair, t_pair2, t_pairf, t_blob, t_offs, t_spblob, t_spoffs, t_uc2a, t_uc2b;
+    DevBuf t_key64;                // whole pieces of 17..64 bytes by the flat kernel's dword hash
+    DevBuf t_cutk2, t_cutg3, t_ucbmp;   // the cut rule's bit maps, the class trie flattened for the BMP (tk_tables.cpp make_cut_tables)
+    int pattern = 0;               // tk_ctx_set_pattern: 0 the reference's hard-coded pattern, 1 the JSON pattern (row f-3)
+    bool have_specials = false;
+    DevBuf dec_lens, dec_bytes, dec_offs, dec_bits, dec_err, dec_in_ids, dec_in_offs, dec_hi, dec_glens, dec_goffs;
+    DevBuf t_inline, t_len8;   // decode: 16-byte inline entries and one-byte lengths by rank (built at the first decode / spans call)
+    DevBuf sp_spans, sp_err;   // tk_token_spans_device: (start, end) per id, the error words (apart from every encode / decode buffer)
+    // the dense layout (tk_dense.hip): the tensor, its mask, lengths and the two statistics words; the ragged ids / offsets / row
+    // lengths of the inverse.  Apart from every encode / spans / decode buffer, allocated at the first dense call
+    DevBuf dn_ids, dn_mask, dn_len, dn_stat, dn_rids, dn_roffs, dn_rlens;
+    int dense_nt = -1;         // non-temporal stores of the dense kernel (TK_DENSE_NT: A / B; read at the first dense call, -1 = not yet)
+    DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
+    DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
+    PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
+    PinBuf<uint32_t> dbg_mark;     // mapped pinned memory, only with TK_DEBUG_MARKS
+    DevBuf long_jobs;              // tk_long.hip: the long pieces of the long-list documents
+    DevBuf long_list;              // pass 2 -> tk_long.hip: documents with a long piece that is not a vocabulary key
+    // flat path (tk_flat.hip)
+    DevBuf f_first, f_tmp, f_lstart, f_flags, f_todo, f_miss, f_mcnt, f_mpfx, f_wfirst, f_info;
+    DevBuf f_long;                 // records of the pieces of 65..TKF_LONGCAP bytes
+    DevBuf f_cut;                  // chunks left to the CUT instantiation (tk_flat_cut_kernel)
+    DevBuf f_late;                 // documents a long-piece record flagged after the list of handed-back documents was made
+    DevBuf scratch_rec;            // scratch of the long-piece record kernels (stream A; c->scratch belongs to the tail on stream B)
+    void* long_ctl_ptr = nullptr;  // what the control words at TKC_LONG_CTL describe
+    uint32_t long_ctl_cap = 0;
+    void* cut_ctl_ptr = nullptr;   // what the control words at TKC_CUT_CTL describe
+    bool use_flat = true;
+    // diagnostics of the last call
+    uint64_t n_flagged = 0, n_long_docs = 0;
+    uint64_t n_round_docs = 0;     // documents the round-based kernel took
+    uint64_t n_long_recs = 0;      // pieces of 65..TKF_LONGCAP bytes the flat path kept
+    uint64_t n_cut_chunks = 0;     // regions that went through the CUT instantiation
+    uint32_t host_syncs = 0;       // host waits of the last flat-pipeline call
+    float pipeline_ms = 0.f, encode_ms = 0.f, merge_ms = 0.f;
+    // pipelined ingestion (tk_encode_batch_pipelined): the second set of staging buffers
+    DevBuf in_bytes2, in_offs2, out_ids2, out_offs2;
+    PinBuf<uint64_t> h_offs_stage[2];   // slice-relative document offsets going up
+    uint64_t h_offs_cap = 0;
+    // small batches in one launch (tk_small_kernel): mapped pinned host buffers the kernel reads / writes directly
+    PinBuf<uint8_t> hs_in;         // [TK_SMALL_MAX_BYTES] text | [TK_SMALL_MAX_DOCS + 1] u64 offsets
+    PinBuf<uint32_t> hs_out;       // [TK_SMALL_MAX_BYTES + 2 * TK_SMALL_MAX_DOCS] ids | [TK_SMALL_MAX_DOCS + 1] u64 offsets | [4] status
+    void* ds_in = nullptr, *ds_out = nullptr;   // the same buffers as the device sees them
+    DevBuf s_offs;
+    uint64_t n_small_calls = 0;    // calls served by the one-launch path (tk_last_stats_ex)
+    bool small_ready = false;      // small_prepare() went through completely
+    // memo of merged pieces (tk_hash.h MEMO; include/tekken_hip.h tk_ctx_set_memo)
+    DevBuf t_memo, t_memo_log;
+    uint32_t memo_have_log2 = 0;   // size of the table that is allocated (0: none yet)
+    uint32_t memo_epoch = 0;       // calls that used the table so far
+    uint32_t memo_low_streak = 0, memo_pause = 0;
+    bool memo_active_last = false;
+    uint64_t memo_hits_last = 0, memo_lookups_last = 0, memo_hits_total = 0, memo_lookups_total = 0;
+
+    uint32_t* ctr(int word) const { return (uint32_t*)counters.p + word; }   // a word of the device counter block (TkCounter)
+};
+
+#define TK_SMALL_IDS_CAP (TK_SMALL_MAX_BYTES + 2 * TK_SMALL_MAX_DOCS)
+#define TK_SMALL_OUT_OFFS_WORD (TK_SMALL_IDS_CAP)                          /* u32 index of the u64 offsets in hs_out (8-byte aligned) */
+#define TK_SMALL_STATUS_WORD (TK_SMALL_OUT_OFFS_WORD + 2 * (TK_SMALL_MAX_DOCS + 1) + 2)
+
+#define TK_HIP(ctx, call)                                                                          \
+    do {                                                                                           \
+        hipError_t _e = (call);                                                                    \
+        if (_e != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(_e); return TK_ERR_RUNTIME; } \
+    } while (0)
+
+// how every entry of the C ABI opens: a null context is refused, the context is locked for the call
+#define TK_ENTRY(c)                                                                                \
+    if (!(c)) return TK_ERR_INVALID_ARG;                                                           \
+    std::lock_guard<std::mutex> lock((c)->mu)
+
+// ---- what the files need from one another (every function below expects c->mu held and the device set) ----
+#pragma GCC visibility push(hidden)
+// tk_capi.cpp
+int upload(tk_ctx* c, DevBuf& b, const void* src, size_t bytes);
+// the checks that open an entry, in the order every entry had them: the batch limit, then the device.  (What a bad call reports
+// first is behaviour: entries with a check between the two call the halves themselves.)
+int check_n_docs(tk_ctx* c, uint64_t n_docs);
+int enter_device(tk_ctx* c, uint64_t n_docs);
+// Result copy-out: pinned blocks from the process-wide pool for n arrays (an array of 0 bytes gets a block too; dev == nullptr: the
+// block alone), the device -> host copies on c->stream, ONE wait.  On a failure every block is back in the pool, c->err is
+// "hipHostMalloc failed" or "<what> copy failed: ..." and host[] is all null.
+struct CopyOut { const void* dev; size_t bytes; void* host; };
+int pinned_blocks(tk_ctx* c, CopyOut* a, int n);
+int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what);
+// tk_pipeline.cpp: the batch pipeline over text on the device; the ids end in c->out_ids, their offsets in c->out_offs
+int run_pipeline(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs, uint64_t n_docs, uint64_t n_bytes, int add_bos,
+                 int add_eos, hipStream_t s, uint64_t* n_ids);
+// what every TkEncodeArgs of the context holds (per-document kernels over c->staging / c->counts, TKC_WORK / TKC_DEFERRED, no pattern)
+TkEncodeArgs encode_args(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs, uint64_t n_docs, int add_bos, int add_eos);
+// tk_capi_encode.cpp
+int check_offsets(tk_ctx* c, const uint64_t* doc_offsets, uint64_t n_docs);
+int encode_device_checked(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, int add_bos,
+                          int add_eos, int checks, void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids);
+// Where the device copy of a host batch and of its result lives once encode_batch returns (the spans and dense passes read them):
+// the context's staging buffers, or -- one-launch small path -- the mapped pinned buffers the small kernel read and wrote.
+struct DevBatch {
+    const uint8_t* bytes = nullptr; const uint64_t* doc_offs = nullptr;
+    const uint32_t* ids = nullptr;  const uint64_t* id_offs = nullptr;
+};
+int encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                 int validate_utf8, tk_result* out, DevBatch* dev);
+// tk_capi_decode.cpp: the decode kernels' tables (also what the spans kernel reads), built at the first call that needs them
+int token_tables(tk_ctx* c);
+template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // ... as the decode and spans kernels take them
+    a.tok_blob = (const uint8_t*)c->t_blob.p; a.tok_offs = (const uint32_t*)c->t_offs.p;
+    a.tok_inline = (const uint8_t*)c->t_inline.p; a.tok_len8 = (const uint8_t*)c->t_len8.p;
+    a.n_ranks = c->host.n_ranks; a.num_special = c->host.num_special;
+}
+// tk_capi_spans.cpp: the document whose id range holds id index idx (error paths)
+int doc_of_id(tk_ctx* c, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t idx, uint64_t* out);
+#pragma GCC visibility pop
+
+#endif

@@ -1,4 +1,4 @@
-// tk_engine.h -- internal glue between the engine-level C ABI (tk_capi.cpp) and the host-side
+// tk_engine.h -- internal glue between the engine-level C ABI (tk_capi*.cpp) and the host-side
 // Tekkenizer mirror (tekkenizer.cpp).  Not part of the public interface.
 #ifndef TK_ENGINE_H
 #define TK_ENGINE_H

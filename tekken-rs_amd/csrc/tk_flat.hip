@@ -37,7 +37,7 @@ __global__ __launch_bounds__(TKF_BLOCK) void tk_flat_firstdoc_kernel(const uint6
     // document d owns the chunks whose lo lies in (doc_offs[d], doc_offs[d + 1]]  (the last document: everything above)
     const uint64_t d = (uint64_t)blockIdx.x * TKF_BLOCK + threadIdx.x;
     if (d == 0 && n_chunks) first_doc[0] = 0u;
-    if (d < 16 || d == 24) counters16[d] = 0u;      // the batch's device counters (24: memo hits)
+    if (d < TKC_CLEARED || d == TKC_MEMO_HITS) counters16[d] = 0u;      // the batch's device counters (tk_counters.h)
     if (d <= n_docs) { flags[d] = 0u; holes[d] = 0u; }
     if (d >= n_docs) return;
     const uint64_t s = doc_offs[d], e = doc_offs[d + 1];
@@ -323,8 +323,8 @@ struct TkFlatAssembleArgs {
     uint32_t bos_id, eos_id;
     int add_bos, add_eos;
     uint64_t* total_out;      // receives out_offs[n_docs] (the host reads it with the other counters)
-    const uint32_t* skip_if;  // optimistic first pass (counters + 4): nothing is copied when skip_if[0] != 0 (documents were handed back)
-                              // or skip_if[7] != 0 (long-piece records wait for tk_flat_long_kernel): the host
+    const uint32_t* skip_if;  // optimistic first pass (counters + TKC_HANDED_BACK): nothing is copied when documents were handed back
+                              // or long-piece records wait for tk_flat_long_kernel (TKC_LONG_RECS, seen from there): the host
                               // runs the per-document kernels and assembles again); NULL for the final pass
 };
 
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(TKF_BLOCK) void tk_flat_assemble_kernel(TkFlatAssem
     const uint64_t wave = (uint64_t)blockIdx.x * (TKF_BLOCK / 64) + (threadIdx.x >> 6);
     const uint64_t n_waves = (uint64_t)gridDim.x * (TKF_BLOCK / 64);
     if (wave == 0 && lane == 0) *a.total_out = a.out_offs[a.n_docs];
-    if (a.skip_if && (a.skip_if[0] != 0u || a.skip_if[7] != 0u)) return;   // (grid-uniform; counters 4 and 11)
+    if (a.skip_if && (*a.skip_if != 0u || a.skip_if[TKC_LONG_RECS - TKC_HANDED_BACK] != 0u)) return;   // (grid-uniform)
     for (uint64_t d0 = wave * 64; d0 < a.n_docs; d0 += n_waves * 64) {
         const uint64_t dm = d0 + (uint64_t)lane;
         TkFlatDocInfo mine;

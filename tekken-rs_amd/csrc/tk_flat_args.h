@@ -3,6 +3,7 @@
 #define TK_FLAT_ARGS_H
 #include <stdint.h>
 
+#include "tk_counters.h"
 #include "tk_tables.h"
 
 #define TKF_W 32                                     /* bytes per lane = bits of a lane-layout mask word */
@@ -64,13 +65,13 @@ struct TkFlatArgs {
     int long_merge128;           // records of 65..128 bytes that are no vocabulary keys are marked for tk_flat_long128_kernel (one lane per
                                  // piece); 0: the single-wave merge takes them too
     const uint32_t* long_ctl;    // what the flat kernel reads, in its rare path only, so that the three values above cost it no
-                                 // scalar registers: device words {long_recs lo, hi, long_cap, cut_list lo, hi}, the record counter
-                                 // five words BELOW them and the cut-chunk counter four words below (the context's counter block:
-                                 // counters 11 and 12, control words at 16..20).  NULL: a piece of more than 64 bytes hands its
-                                 // document back
+                                 // scalar registers: the control words TKC_LONG_CTL .. TKC_CUT_CTL_HI of the context's counter
+                                 // block (tk_counters.h: long_recs lo, hi, long_cap, cut_list lo, hi); the record counter
+                                 // TKC_LONG_RECS and the cut-chunk counter TKC_CUT_CHUNKS are reached from there.  NULL: a piece
+                                 // of more than 64 bytes hands its document back
     uint32_t* cut_list;          // [n_chunks] chunks with a piece of more than 64 bytes: left by tk_flat_kernel to the CUT instantiation
                                  // (tk_flat_cut_kernel), which cuts such pieces into fragments where no token can span (NULL: no cuts)
-    const uint32_t* cut_count;   // entries of cut_list (device counter 12)
+    const uint32_t* cut_count;   // entries of cut_list (device counter TKC_CUT_CHUNKS)
     uint32_t* late_list;         // [n_docs] documents that a long-piece record flags (an open piece beyond TKF_LONGCAP) after the list of
                                  // the handed-back documents was made; NULL: the flag alone (the list is made afterwards)
     uint32_t* late_count;

@@ -727,10 +727,10 @@ TK_DEV bool tk_flat_chunk(const TkFlatArgs& a, uint64_t c, int lane, uint32_t* l
             const uint64_t lc = (uint64_t)wv_first(lds[TKF_L_CONST + 6]) | ((uint64_t)wv_first(lds[TKF_L_CONST + 7]) << 32);
             if (lc != 0ull) {
                 const uint32_t* ctl = reinterpret_cast<const uint32_t*>(wv_global_ptr(lc));
-                const uint64_t lp = (uint64_t)wv_first(ctl[3]) | ((uint64_t)wv_first(ctl[4]) << 32);
+                const uint64_t lp = (uint64_t)wv_first(ctl[TKC_CTL(TKC_CUT_CTL)]) | ((uint64_t)wv_first(ctl[TKC_CTL(TKC_CUT_CTL_HI)]) << 32);
                 if (lp != 0ull) {
                     if (lane == 0) {
-                        const uint32_t q = wv_atomic_add(const_cast<uint32_t*>(ctl) - 4, 1u);
+                        const uint32_t q = wv_atomic_add(const_cast<uint32_t*>(ctl) + TKC_CTL(TKC_CUT_CHUNKS), 1u);
                         reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(wv_global_ptr(lp)))[q] = (uint32_t)c;
                     }
                     return true;
@@ -1061,12 +1061,12 @@ TK_DEV bool tk_flat_chunk(const TkFlatArgs& a, uint64_t c, int lane, uint32_t* l
                     const int lfirst = tk_ctz64(LB);
                     const uint32_t* ctl = reinterpret_cast<const uint32_t*>(wv_global_ptr((uint64_t)lds[TKF_L_CONST + 6] | ((uint64_t)lds[TKF_L_CONST + 7] << 32)));
                     uint32_t qbase = 0;
-                    if (lane == lfirst) qbase = wv_atomic_add(const_cast<uint32_t*>(ctl) - 5, (uint32_t)tk_popc64(LB));
+                    if (lane == lfirst) qbase = wv_atomic_add(const_cast<uint32_t*>(ctl) + TKC_CTL(TKC_LONG_RECS), (uint32_t)tk_popc64(LB));
                     qbase = wv_shfl(qbase, lfirst);
                     const uint32_t q = qbase + (uint32_t)tk_popc64(LB & tk_lowmask(lane));
-                    TkFlatLongRec* recs = reinterpret_cast<TkFlatLongRec*>(const_cast<uint8_t*>(wv_global_ptr((uint64_t)ctl[0] | ((uint64_t)ctl[1] << 32))));
+                    TkFlatLongRec* recs = reinterpret_cast<TkFlatLongRec*>(const_cast<uint8_t*>(wv_global_ptr((uint64_t)ctl[TKC_CTL(TKC_LONG_CTL)] | ((uint64_t)ctl[TKC_CTL(TKC_LONG_CTL_HI)] << 32))));
                     if (!longp) {
-                    } else if (q < ctl[2]) {
+                    } else if (q < ctl[TKC_CTL(TKC_LONG_CTL_CAP)]) {
                         TkFlatLongRec lr;
                         lr.pos = (uint64_t)(r0 + (int64_t)pos); lr.chunk = (uint32_t)c; lr.slot = lslot; lr.len = lopen ? 0u : (CUT && frag ? len | TKF_LREC_FRAG : len); lr.reserved = lres;
                         recs[q] = lr;

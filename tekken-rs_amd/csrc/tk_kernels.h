@@ -40,6 +40,7 @@ hipError_t tk_launch_validate(const uint8_t* bytes, const uint64_t* doc_offs, ui
                               hipStream_t s);
 
 // ---- flat path (tk_flat.hip, tk_flat_impl.h): one wave per 2048-byte region of the packed stream ----
+// (counters16: the context's counter block, words by name in tk_counters.h; the pre-pass clears TKC_CLEARED words and TKC_MEMO_HITS)
 hipError_t tk_launch_flat_firstdoc(const uint64_t* doc_offs, uint64_t n_docs, uint64_t n_chunks, uint32_t* first_doc,
                                    uint32_t* flags, uint32_t* holes, uint32_t* counters16, hipStream_t s);
 hipError_t tk_launch_flat(const TkFlatArgs& a, hipStream_t s);
@@ -57,7 +58,7 @@ hipError_t tk_launch_flat_counts(const uint64_t* doc_offs, uint64_t n_docs, uint
 hipError_t tk_launch_flat_assemble(uint64_t n_docs, const void* doc_info, const uint32_t* kcount, const uint64_t* out_offs,
                                    const uint32_t* tmp, const uint32_t* staging, uint32_t* out_ids, uint32_t bos_id,
                                    uint32_t eos_id, int add_bos, int add_eos, uint64_t* total_out, const uint32_t* skip_if, hipStream_t s);
-hipError_t tk_launch_merge(const TkFlatArgs& a, uint32_t* narrow_left_out, hipStream_t s);  // both merge kernels, persistent grids
+hipError_t tk_launch_merge(const TkFlatArgs& a, uint32_t* narrow_left_out, hipStream_t s);  // both merge kernels, persistent grids (narrow_left_out: TKC_NARROW_LEFT)
 
 hipError_t tk_launch_iota(uint32_t* out, uint64_t n, hipStream_t s);   // out[i] = i
 hipError_t tk_launch_add_u64(uint64_t* p, uint64_t n, uint64_t add, hipStream_t s);   // p[i] += add

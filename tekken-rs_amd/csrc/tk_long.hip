@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void tk_long_walk_kernel(TkEncodeArgs a) {
                     } else if (a.defer_count) {
                         // cannot happen with the host's sizing (a job is at least long_min bytes of text); if it ever does the
                         // piece's slots stay unwritten, so the call must fail loudly: an error word the host checks
-                        *a.defer_count = 0xDEADu;
+                        *a.defer_count = TKC_OVERFLOW;
                     }
                 }
                 cur = len;                                         // (its slots are written by tk_long_merge_kernel)

@@ -3,7 +3,7 @@
 // Input is the validated rank table (rank i <-> token bytes i), i.e. the contents of the
 // FxHashMap built by reload_mergeable_ranks (reference src/tekkenizer.rs:776-816) and handed
 // to CoreBPE::new (:122-126).  Output is the flat, pointer-free image uploaded to HBM once
-// per context (tk_capi.cpp) -- and the same image is what the CPU wave emulator of the
+// per context (tk_ctx_create, tk_capi.cpp) -- and the same image is what the CPU wave emulator of the
 // test-suite runs the kernel source against.
 #ifndef TK_TABLES_H
 #define TK_TABLES_H

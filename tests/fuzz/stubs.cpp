@@ -1,6 +1,6 @@
 // Host-only build of the loader for the fuzzer (tests/fuzz/fuzz_loaders.cpp): the engine entry points the host-side
 // Tekkenizer mirror links against, answering "no device".  Test infrastructure -- the product library has no such stubs
-// (tk_capi.cpp fails loudly without a GPU); the fuzzer only ever builds host-only objects (device = -1).
+// (tk_ctx_create, tk_capi.cpp, fails loudly without a GPU); the fuzzer only ever builds host-only objects (device = -1).
 #include <string>
 
 #include "../../include/tekken_hip.h"
