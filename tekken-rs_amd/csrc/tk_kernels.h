@@ -51,13 +51,16 @@ hipError_t tk_launch_flat_long(const TkFlatArgs& a, uint32_t* work_counter, uint
 // flagged documents -> todo list (count in *n_todo), the longest of them in *maxlen (atomicMax: zero it first)
 hipError_t tk_launch_flat_todo(const uint32_t* flags, const uint64_t* doc_offs, uint64_t n_docs, uint32_t* todo, uint32_t* n_todo,
                                uint32_t* maxlen, hipStream_t s);
-// doc_info: [n_docs] 16-byte records (TkFlatDocInfo, tk_flat.hip) written by counts, read by assemble
+// doc_info: [n_docs] 16-byte records (TkFlatDocInfo, tk_flat_tail_impl.h) written by counts, read by assemble
 hipError_t tk_launch_flat_counts(const uint64_t* doc_offs, uint64_t n_docs, uint64_t n_bytes, uint64_t n_chunks,
                                  const uint64_t* P, const uint32_t* lstart, const uint32_t* flags, const uint32_t* holes,
                                  uint32_t extra, uint32_t* counts, void* doc_info, int final_pass, uint32_t* n_flagged, hipStream_t s);
 hipError_t tk_launch_flat_assemble(uint64_t n_docs, const void* doc_info, const uint32_t* kcount, const uint64_t* out_offs,
                                    const uint32_t* tmp, const uint32_t* staging, uint32_t* out_ids, uint32_t bos_id,
                                    uint32_t eos_id, int add_bos, int add_eos, uint64_t* total_out, const uint32_t* skip_if, hipStream_t s);
+// the first launch of tk_launch_merge on its own: which sub-queue holds the first item of every merge wave
+hipError_t tk_launch_merge_wavefirst(const uint64_t* prefix, uint64_t n_chunks, uint32_t* wave_first, uint32_t* wave_first_wide,
+                                     uint32_t* narrow_left_out, hipStream_t s);
 hipError_t tk_launch_merge(const TkFlatArgs& a, uint32_t* narrow_left_out, hipStream_t s);  // both merge kernels, persistent grids (narrow_left_out: TKC_NARROW_LEFT)
 
 hipError_t tk_launch_iota(uint32_t* out, uint64_t n, hipStream_t s);   // out[i] = i

@@ -14,6 +14,8 @@
 #include "../../tekken-rs_amd/csrc/tk_encode_impl.h"
 #include "../../tekken-rs_amd/csrc/tk_flat_impl.h"
 #include "../../tekken-rs_amd/csrc/tk_long_impl.h"
+#include "../../tekken-rs_amd/csrc/tk_flat_tail_impl.h"
+#include "../../tekken-rs_amd/csrc/tk_test_hooks.h"
 
 namespace tkemu {
 Wave* g_wave = nullptr;
@@ -122,9 +124,102 @@ extern "C" int emu_memo_pack_roundtrip(const uint32_t* ranks5, uint32_t n, uint3
     return 0;
 }
 
-// Flat path on the emulator: tk_flat_chunk for every chunk (one emulated wave), the flagged documents through
-// the per-document algorithm (mode 3, then pass 2), and host restatements of the small bookkeeping kernels of
-// tk_flat.hip (first_doc, todo list, chunk prefix sums, counts, assemble).
+// ------------------------------------------------------------------------------------------
+// The bookkeeping tail of the flat path (tk_flat_tail_impl.h: firstdoc, wavefirst, todo, counts, assemble) on the emulator,
+// in the order and with the thread / wave indices the launch functions of tk_flat.hip give the kernels; the exclusive scans
+// between them are done by the host (tk_kernels.hip's block scan shuffles 64-bit values, which the emulator does not model).
+// What the bodies only read sits in exactly sized heap arrays (a read past the end is the sanitizer's); what they write
+// sits between two guard zones.
+// ------------------------------------------------------------------------------------------
+namespace {
+struct GBuf {   // n words between two guard zones
+    std::vector<uint32_t> raw;
+    size_t n;
+    const char* name;
+    GBuf(const char* nm, size_t words, const uint32_t* init) : raw(words + 2 * TK_TEST_GUARD_WORDS, TK_TEST_GUARD_FILL), n(words), name(nm) {
+        if (init && words) memcpy(p(), init, words * 4);
+    }
+    uint32_t* p() { return raw.data() + TK_TEST_GUARD_WORDS; }
+    bool intact() const {
+        for (size_t i = 0; i < TK_TEST_GUARD_WORDS; ++i)
+            if (raw[i] != TK_TEST_GUARD_FILL || raw[TK_TEST_GUARD_WORDS + n + i] != TK_TEST_GUARD_FILL) return false;
+        return true;
+    }
+    void out(void* dst) { if (dst && n) memcpy(dst, p(), n * 4); }
+};
+template <class T> std::vector<T> exact(const T* p, size_t n) { return n ? std::vector<T>(p, p + n) : std::vector<T>(); }
+}
+
+static int run_flat_tail(TkTestTailCase& t) {
+    const uint64_t D = t.n_docs, C = t.n_chunks;
+    const std::vector<uint64_t> doc_offs = exact(t.doc_offs, D + 1);
+    const std::vector<uint32_t> kcount = exact(t.kcount, C), lstart = exact(t.lstart, D), tmp = exact(t.tmp, C * TKF_STRIDE),
+                                staging = exact(t.staging, t.n_staging);
+    std::vector<uint64_t> mpfx(4 * C + 1, 0), P(C + 1, t.p_base);
+    for (uint64_t e = 0; e < 4 * C; ++e) mpfx[e + 1] = mpfx[e] + t.miss_count[e];
+    for (uint64_t c = 0; c < C; ++c) P[c + 1] = P[c] + kcount[c];
+    GBuf first_doc("first_doc", C, t.first_doc), flags("flags", D + 1, t.flags_cleared), holes("holes", D + 1, t.holes_cleared);
+    GBuf ctr("the counters", TKC_DEVICE_WORDS, t.counters_in), wf("wave_first", t.n_wave_first, t.wave_first);
+    GBuf wfw("wave_first_wide", t.n_wave_first_wide, t.wave_first_wide), todo("todo", D, t.todo), counts("counts", D, t.counts);
+    GBuf info("the info records", 4 * D, nullptr), out_offs("out_offs", 2 * (D + 1), (const uint32_t*)t.out_offs), out_ids("out_ids", t.out_cap, t.out_ids);
+    GBuf* all[] = {&first_doc, &flags, &holes, &ctr, &wf, &wfw, &todo, &counts, &info, &out_offs, &out_ids};
+    // tk_launch_flat_firstdoc: n_docs + 32 threads
+    for (uint64_t d = 0; d < D + 32; ++d) tkf_firstdoc_body(d, doc_offs.data(), D, C, first_doc.p(), flags.p(), holes.p(), ctr.p());
+    first_doc.out(t.first_doc); flags.out(t.flags_cleared); holes.out(t.holes_cleared);
+    // what the flat / merge kernels would have left
+    if (D) { memcpy(flags.p(), t.flags, D * 4); memcpy(holes.p(), t.holes, D * 4); }
+    ctr.p()[TKC_LONG_RECS] = t.long_recs;
+    if (C)   // tk_launch_merge
+        for (uint64_t e = 0; e < 4 * C + 32; ++e) tkf_wavefirst_body(e, mpfx.data(), C, wf.p(), wfw.p(), ctr.p() + TKC_NARROW_LEFT);
+    const uint64_t n_waves = (D + 255) / 256 * 4;   // blocks of 256 threads, one thread per document
+    for (uint64_t w = 0; w < n_waves; ++w)
+        tkemu::run_wave([&](int lane) { tkf_todo_body(w * 64 + (uint64_t)lane, lane, flags.p(), doc_offs.data(), D, todo.p(), ctr.p() + TKC_TODO, ctr.p() + TKC_TODO_MAXLEN); });
+    const uint32_t extra = (uint32_t)((t.add_bos ? 1 : 0) + (t.add_eos ? 1 : 0));
+    TkFlatDocInfo* inf = reinterpret_cast<TkFlatDocInfo*>(info.p());
+    for (uint64_t w = 0; w < n_waves; ++w)
+        tkemu::run_wave([&](int lane) {
+            tkf_counts_body(w * 64 + (uint64_t)lane, lane, doc_offs.data(), D, t.n_bytes, C, P.data(), lstart.data(), flags.p(), holes.p(), extra,
+                            counts.p(), inf, t.final_pass, ctr.p() + TKC_HANDED_BACK);
+        });
+    uint64_t* oo = reinterpret_cast<uint64_t*>(out_offs.p());
+    if (D) {   // (tk_launch_scan; with no documents the pipeline launches nothing of this)
+        uint64_t run = 0;
+        for (uint64_t d = 0; d < D; ++d) { oo[d] = run; run += counts.p()[d]; }
+        oo[D] = run;
+    } else {
+        oo[0] = 0;
+    }
+    if (D) {
+        TkFlatAssembleArgs a;
+        a.n_docs = D; a.info = inf; a.kcount = kcount.data(); a.out_offs = oo; a.tmp = tmp.data(); a.staging = staging.data();
+        a.out_ids = out_ids.p(); a.bos_id = t.bos_id; a.eos_id = t.eos_id; a.add_bos = t.add_bos; a.add_eos = t.add_eos;
+        a.total_out = reinterpret_cast<uint64_t*>(ctr.p() + TKC_TOTAL);
+        a.skip_if = t.final_pass ? nullptr : ctr.p() + TKC_HANDED_BACK;
+        const uint64_t aw = D > 64 ? 3 : 2;   // the waves stride over the documents
+        for (uint64_t w = 0; w < aw; ++w) tkemu::run_wave([&](int lane) { tkf_assemble_waves(a, w, aw, lane); });
+    }
+    for (GBuf* g : all)
+        if (!g->intact()) { g_err = std::string("the tail wrote outside ") + g->name; return TK_ERR_RUNTIME; }
+    wf.out(t.wave_first); wfw.out(t.wave_first_wide); todo.out(t.todo); counts.out(t.counts); out_offs.out(t.out_offs);
+    out_ids.out(t.out_ids); ctr.out(t.counters_out);
+    return TK_OK;
+}
+
+extern "C" int emu_flat_tail(TkTestTailCase* t) {
+    const int rc = run_flat_tail(*t);
+    if (rc != TK_OK && t->err && t->err_cap) snprintf(t->err, t->err_cap, "%s", g_err.c_str());
+    return rc;
+}
+
+// the geometry the test layouts are built from: {TKF_COMMIT, TKF_HL, TKF_STRIDE, TKF_HOLE, TKC_CLEARED, TKC_DEVICE_WORDS}
+extern "C" void emu_flat_consts(uint64_t* out) {
+    out[0] = TKF_COMMIT; out[1] = TKF_HL; out[2] = TKF_STRIDE; out[3] = TKF_HOLE; out[4] = TKC_CLEARED; out[5] = TKC_DEVICE_WORDS;
+}
+
+// Flat path on the emulator: tk_flat_chunk for every chunk (one emulated wave), the merge and long-piece waves, the flagged
+// documents through the per-document algorithm (mode 3, then pass 2), and the bookkeeping tail (tk_flat_tail_impl.h:
+// first_doc, wave_first, todo list, counts, assemble) twice: as the device bodies run by run_flat_tail above, optimistic and
+// final pass, and as plain host loops next to them, which are the reference the device bodies are compared with.
 #ifndef TKF_LONG_SCRATCH_WORDS
 #define TKF_LONG_SCRATCH_WORDS 2048u
 #endif
@@ -196,6 +291,7 @@ extern "C" int emu_flat_encode_batch(const uint8_t* blob, const uint32_t* offs, 
         fa.cut_count = &ctlblk[12];
     }
     std::vector<uint32_t> lds(TKF_LDS_WORDS_CUT, 0);
+    std::vector<uint32_t> ref_wf, ref_wfw;                  // wave_first / wave_first_wide as the host loops below make them
     uint64_t ops = 0;
     if (n_chunks) {
         tkemu::run_wave([&](int lane) {
@@ -236,6 +332,8 @@ extern "C" int emu_flat_encode_batch(const uint8_t* blob, const uint32_t* offs, 
         for (uint64_t e = 2 * n_chunks; e < 4 * n_chunks; ++e)
             for (uint64_t w = (mpfx[e] - n_narrow + 63) / 64; w * 64 < mpfx[e + 1] - n_narrow; ++w) wave_first_wide[w] = (uint32_t)e;
         fa.wave_first_wide = wave_first_wide.data();
+        ref_wf.assign(wave_first.begin(), wave_first.begin() + (n_narrow + 63) / 64);
+        ref_wfw.assign(wave_first_wide.begin(), wave_first_wide.begin() + (n_wide + 63) / 64);
         // the wave's LDS columns sit between two guard zones: a write outside the kernel's share (8 KB narrow, 16 KB
         // wide) would be silent on the device
         const size_t G = 256;
@@ -375,7 +473,7 @@ extern "C" int emu_flat_encode_batch(const uint8_t* blob, const uint32_t* offs, 
         }
     }
     if (n_ops) *n_ops = ops;
-    // chunk prefix sums, counts, assemble (host restatement of tk_flat.hip's bookkeeping kernels)
+    // chunk prefix sums, counts, assemble: the plain reference of the device tail (compared below)
     std::vector<uint64_t> P(n_chunks + 1, 0);
     for (uint64_t c = 0; c < n_chunks; ++c) P[c + 1] = P[c] + kcount[c];
     auto G = [&](uint64_t i) -> uint64_t {
@@ -405,6 +503,74 @@ extern "C" int emu_flat_encode_batch(const uint8_t* blob, const uint32_t* offs, 
         if (add_eos) out_ids[t++] = T.eos_id;
     }
     out_offs[n_docs] = t;
+    // the device bodies of the tail on the same arrays, as the pipeline runs them: the optimistic pass (nothing copied when
+    // documents were handed back or long-piece records wait), then the final pass
+    for (int final_pass = 0; final_pass < 2; ++final_pass) {
+        const uint32_t FILL = 0xA5A5A5A5u;
+        const uint64_t base = (1ull << 33) + 12345u;          // (the pipeline passes P offset by the miss total)
+        std::vector<uint32_t> ctr_in(TKC_DEVICE_WORDS), ctr_out(TKC_DEVICE_WORDS, 0), d_counts(counts.begin(), counts.begin() + n_docs);
+        for (uint32_t i = 0; i < TKC_DEVICE_WORDS; ++i) ctr_in[i] = 0xC0DE0000u + i;
+        std::vector<uint32_t> d_ids(t + 8, FILL), d_first(n_chunks, FILL), d_fl(n_docs + 1, FILL), d_ho(n_docs + 1, FILL);
+        std::vector<uint32_t> d_wf(ref_wf.size(), FILL), d_wfw(ref_wfw.size(), FILL), d_todo(n_docs, FILL);
+        std::vector<uint64_t> d_offs(n_docs + 1, 0x5A5A5A5A5A5A5A5Aull);
+        TkTestTailCase tc;
+        memset(&tc, 0, sizeof(tc));
+        tc.n_docs = n_docs; tc.n_bytes = n_bytes; tc.n_chunks = n_chunks; tc.p_base = base;
+        tc.doc_offs = doc_offs; tc.kcount = kcount.data(); tc.miss_count = miss_count.data(); tc.lstart = lstart.data();
+        tc.flags = flags.data(); tc.holes = holes.data(); tc.tmp = tmp.data(); tc.staging = staging.data();
+        tc.n_staging = n_bytes + 2 * n_docs; tc.counters_in = ctr_in.data(); tc.long_recs = final_pass ? 0u : long_count;
+        tc.bos_id = T.bos_id; tc.eos_id = T.eos_id; tc.add_bos = add_bos; tc.add_eos = add_eos; tc.final_pass = final_pass;
+        tc.out_cap = d_ids.size(); tc.n_wave_first = d_wf.size(); tc.n_wave_first_wide = d_wfw.size();
+        tc.counts = d_counts.data(); tc.out_ids = d_ids.data(); tc.first_doc = d_first.data(); tc.flags_cleared = d_fl.data();
+        tc.holes_cleared = d_ho.data(); tc.wave_first = d_wf.data(); tc.wave_first_wide = d_wfw.data(); tc.todo = d_todo.data();
+        tc.out_offs = d_offs.data(); tc.counters_out = ctr_out.data();
+        if ((rc = run_flat_tail(tc)) != TK_OK) return rc;
+        const std::string pass = final_pass ? "final pass: " : "optimistic pass: ";
+        auto bad = [&](const char* what, uint64_t i, uint64_t got, uint64_t want) {
+            g_err = "device tail, " + pass + what + "[" + std::to_string(i) + "] = " + std::to_string(got) + ", the reference has " + std::to_string(want);
+            return TK_ERR_RUNTIME;
+        };
+        for (uint64_t c = 0; c < n_chunks; ++c)
+            if (d_first[c] != first_doc[c]) return bad("first_doc", c, d_first[c], first_doc[c]);
+        for (uint64_t d = 0; d <= n_docs; ++d) {
+            if (d_fl[d] != 0u) return bad("flags after the pre-pass", d, d_fl[d], 0);
+            if (d_ho[d] != 0u) return bad("holes after the pre-pass", d, d_ho[d], 0);
+        }
+        for (size_t w = 0; w < ref_wf.size(); ++w)
+            if (d_wf[w] != ref_wf[w]) return bad("wave_first", w, d_wf[w], ref_wf[w]);
+        for (size_t w = 0; w < ref_wfw.size(); ++w)
+            if (d_wfw[w] != ref_wfw[w]) return bad("wave_first_wide", w, d_wfw[w], ref_wfw[w]);
+        if (ctr_out[TKC_TODO] != todo.size()) return bad("n_todo", 0, ctr_out[TKC_TODO], todo.size());
+        for (size_t i = 0; i < todo.size(); ++i)   // (one emulated wave after the other: the list comes out in document order)
+            if (d_todo[i] != todo[i]) return bad("todo", i, d_todo[i], todo[i]);
+        const uint32_t want_flagged = final_pass ? 0u : (uint32_t)todo.size();
+        if (ctr_out[TKC_HANDED_BACK] != want_flagged) return bad("the flagged count", 0, ctr_out[TKC_HANDED_BACK], want_flagged);
+        uint64_t d_total;
+        memcpy(&d_total, &ctr_out[TKC_TOTAL], 8);
+        const bool skipped = !final_pass && (!todo.empty() || long_count != 0u);
+        if (skipped && n_docs) {
+            // nothing is copied; the counts of the handed-back documents are left alone, the others are the reference's
+            for (uint64_t d = 0; d < n_docs; ++d) {
+                const uint32_t want = flags[d] ? counts[d] : (uint32_t)(out_offs[d + 1] - out_offs[d]);
+                if (d_counts[d] != want) return bad("counts", d, d_counts[d], want);
+            }
+            for (size_t i = 0; i < d_ids.size(); ++i)
+                if (d_ids[i] != FILL) return bad("out_ids (nothing may be copied)", i, d_ids[i], FILL);
+            if (d_total != d_offs[n_docs]) return bad("total", 0, d_total, d_offs[n_docs]);
+            continue;
+        }
+        for (uint64_t d = 0; d < n_docs; ++d) {
+            const uint32_t want = (uint32_t)(out_offs[d + 1] - out_offs[d]);
+            if (d_counts[d] != want) return bad("counts", d, d_counts[d], want);
+        }
+        for (uint64_t d = 0; d <= n_docs && n_docs; ++d)
+            if (d_offs[d] != out_offs[d]) return bad("out_offs", d, d_offs[d], out_offs[d]);
+        if (d_total != (n_docs ? t : 0)) return bad("total", 0, d_total, t);
+        for (uint64_t i = 0; i < t; ++i)
+            if (d_ids[i] != out_ids[i]) return bad("out_ids", i, d_ids[i], out_ids[i]);
+        for (uint64_t i = t; i < d_ids.size(); ++i)
+            if (d_ids[i] != FILL) return bad("out_ids past the total", i, d_ids[i], FILL);
+    }
     return TK_OK;
 }
 

@@ -169,6 +169,16 @@ def test_c_abi_exports(tk):
         assert hasattr(L, n), n
 
 
+def test_shipped_library_has_no_test_hooks(tk):
+    """csrc/tk_test_hooks.h: the entries that run single stages of the pipeline on made-up inputs exist in the development build
+    (`make ablate`, -DTK_TEST_HOOKS) only."""
+    import os
+    L = tk.lib()
+    assert "ablate" not in os.path.basename(getattr(L, "_name", ""))
+    for n in ("tk_test_flat_tail", "tk_test_scan"):
+        assert not hasattr(L, n), n
+
+
 def test_table_cache_round_trip(tmp_path, test_vocab, bench_vocab):
     """the derived device tables written to / read from a side file keyed by the rank table are
     identical, field by field, to freshly built ones; a wrong key, a truncated or a corrupted file is refused."""

@@ -4,7 +4,7 @@
   tk_encode_impl.h, tk_long_impl.h: every LDS index, queue record, table probe, and the workgroup merges' scratch) compiled for the CPU wave emulator with
   -fsanitize=address,undefined, and oracle/libtk_oracle_asan.so the oracle; a subset of the emulator / oracle suites is
   re-run against them in a child interpreter (libasan preloaded).  TK_SANITIZE_FULL=1 runs all of test_flat_path.py,
-  test_kernel_emu.py, test_oracle_golden.py and test_merge_golden.py that way (seven to ten minutes here; last run clean).
+  test_flat_tail_emu.py, test_kernel_emu.py, test_oracle_golden.py and test_merge_golden.py that way (seven to ten minutes here; last run clean).
 * `test_loaders_fuzzed_under_asan_ubsan`: tests/fuzz/fuzz_loaders -- the hand-written JSON / base64 reader and the two
   cache side-file loaders of the host side, fed truncated / bit-flipped / spliced inputs.  A damaged side file must
   never change what a load returns (both files end with a checksum of their payload).
@@ -35,14 +35,14 @@ def test_device_source_under_asan_ubsan():
                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     if os.environ.get("TK_SANITIZE_FULL"):
         sel = ["tests/test_flat_path.py", "tests/test_kernel_emu.py", "tests/test_oracle_golden.py", "tests/test_merge_golden.py",
-               "tests/test_long_merge_emu.py"]
+               "tests/test_long_merge_emu.py", "tests/test_flat_tail_emu.py"]
         extra = []
     else:
         # the flat chunk kernel + both merge kernels on UTF-8 / run-heavy / dense-piece streams and on the adversarial merge
         # vocabularies; the per-document kernels against the oracle; the oracle against its golden vectors
         sel = ["tests/test_flat_path.py", "tests/test_kernel_emu.py", "tests/test_oracle_golden.py", "tests/test_merge_golden.py",
-               "tests/test_long_merge_emu.py"]
-        extra = ["-k", "test_block_merges_on_repetitive or test_emu_cut_decomposition or test_emu_flat_utf8 or test_emu_flat_runs_and_misses or test_emu_flat_dense_pieces or test_emu_flat_baseline_shapes "
+               "tests/test_long_merge_emu.py", "tests/test_flat_tail_emu.py"]
+        extra = ["-k", "test_emu_flat_tail_directed or test_emu_flat_tail_random_layouts or test_constants_are_the_headers or test_block_merges_on_repetitive or test_emu_cut_decomposition or test_emu_flat_utf8 or test_emu_flat_runs_and_misses or test_emu_flat_dense_pieces or test_emu_flat_baseline_shapes "
                        "or test_emu_memo_of_merged_pieces or test_emu_flat_handback_and_mixed or test_emu_flat_small_alphabet_packed or test_emu_flat_every_ascii_byte_pair "
                        "or test_emu_long_single_piece or test_emu_split_only or test_emu_small_vocab_known_answer "
                        "or test_emu_reference_vectors_on_consistent_vocab or test_split_matches_independent_engine "
