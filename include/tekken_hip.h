@@ -268,6 +268,61 @@ int tk_ragged_from_dense_device(tk_ctx* ctx, const void* d_dense, uint64_t n_doc
                                 const void* d_lengths, uint32_t pad_id, void* hip_stream, void** d_ids,
                                 void** d_id_offsets, uint64_t* n_ids);
 
+/* ---- packed fixed-length training rows: input_ids, position_ids, segment_ids, cu_seqlens (no reference equivalent: pad_id(),
+ * src/tekkenizer.rs:304, is all the reference has) ----
+ * Pre-training does not pad documents: it concatenates them, BOS / EOS included, into one stream and cuts the stream into rows
+ * of seq_len.  Input: the ragged ids R_d = ids[oo[d] : oo[d+1]], d < D; N = oo[D]; options seq_len = L (required, > 0), pad_id
+ * and the flags below.
+ *   1. The stream is S = R_0 + R_1 + ... + R_{D-1}: the ids are already concatenated, S[g] = ids[g].  n_rows = ceil(N / L), or
+ *      floor(N / L) with TK_SEQPACK_DROP_LAST; n_used = min(N, n_rows * L); n_left = N - n_used.  The ids ids[n_used :] are left
+ *      for the caller to carry into its next batch (carrying them across calls is the caller's business).
+ *   2. input_ids[r, c] = ids[g] with g = r * L + c, if g < n_used, else pad_id.  Only the last row can hold pads, and only
+ *      without DROP_LAST.
+ *   3. A segment is a maximal run of positions g < n_used that lie in one document and in one row.  Its starts are
+ *      B = sorted({oo[d] : n_d > 0, oo[d] < n_used} u {r * L : r * L < n_used}), without duplicates: empty documents make no
+ *      segment, a document that crosses a row boundary is split there.  n_segments = |B|.
+ *   4. position_ids[r, c] = g - (start of g's segment); a pad gets 0.  Positions restart at a document start and at a row
+ *      start: the continued part of a document cannot see its head in the previous row.
+ *   5. segment_ids[r, c] = 1 + the number of segment starts in (r * L, g]: segments are numbered 1, 2, 3, ... within a row; a
+ *      pad gets 0.
+ *   6. cu_seqlens (int32, n_segments + 1 entries) is B followed by n_used: offsets into the flattened [n_rows * L] tensor, pads
+ *      lie beyond its last entry.  max_seqlen = max diff(cu_seqlens); 0 when n_used == 0, where cu_seqlens = [0].  n_segments
+ *      and max_seqlen are filled whether or not cu_seqlens is selected.
+ *   7. input_ids, position_ids and segment_ids are int32, or int64 with TK_SEQPACK_I64; cu_seqlens is always int32.
+ *      TK_SEQPACK_POSITIONS, TK_SEQPACK_SEGMENTS and TK_SEQPACK_CU_SEQLENS select the optional outputs; an unselected output is
+ *      NULL.
+ *   8. TK_ERR_INVALID_ARG, nothing written, an earlier packed result stays readable: L == 0; L >= 2^31; an unknown flag;
+ *      n_rows * L > 2^36; TK_SEQPACK_CU_SEQLENS with n_used >= 2^31; n_docs == 0 with n_ids > 0.  A failed allocation is TK_ERR_RUNTIME.  D == 0 or N == 0
+ *      is valid and gives n_rows == 0.
+ * The layout is a separate pass behind the unchanged encode pipeline (csrc/tk_seqpack.hip): every element is written once, pad
+ * included, in 16-byte stores where L is a multiple of 4 (element stores otherwise).  n_rows, n_used and n_left follow from
+ * n_ids on the host: nothing is read before the launches, and one wait at the end reads n_segments and max_seqlen. */
+#define TK_SEQPACK_I64 1
+#define TK_SEQPACK_POSITIONS 2
+#define TK_SEQPACK_SEGMENTS 4
+#define TK_SEQPACK_CU_SEQLENS 8
+#define TK_SEQPACK_DROP_LAST 16
+typedef struct tk_seqpack_opts { uint32_t seq_len, pad_id, flags; } tk_seqpack_opts;
+typedef struct tk_seqpack { void *input_ids, *position_ids, *segment_ids; int32_t* cu_seqlens;
+                            uint64_t n_rows, row_len, n_used, n_left, n_segments, max_seqlen; } tk_seqpack;
+/* ids already on the device (encode's own outputs or the caller's; d_id_offsets: n_docs + 1 uint64, [0] = 0, non-decreasing,
+ * [n_docs] = n_ids -- NOT checked, as in tk_dense_from_ids_device: anything else is out-of-bounds indexing on the device) ->
+ * packed rows.  out's buffers are device buffers owned by the context, valid until the next packed call on it, and SEPARATE from
+ * the encode, spans, dense and decode outputs.  The work is enqueued on hip_stream and the call returns after the stream has
+ * drained. */
+int tk_seqpack_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                               const tk_seqpack_opts* opts, void* hip_stream, tk_seqpack* out);
+/* tk_encode_batch_device_ex + the packed pass on the same stream; the ragged outputs (*d_ids / *d_out_offsets / *n_ids as
+ * tk_encode_batch_device) are returned as well: ids[out->n_used :] is what the caller carries on. */
+int tk_encode_batch_device_seqpack(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                   int add_bos, int add_eos, int checks, const tk_seqpack_opts* opts, void* hip_stream,
+                                   void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_seqpack* out);
+/* Host in / host out: tk_encode_batch + the packed pass (batches of the one-launch small path included).  out's buffers are
+ * pinned host memory, released with tk_free_seqpack (an unselected output is NULL). */
+int tk_encode_batch_seqpack(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                            int validate_utf8, const tk_seqpack_opts* opts, tk_seqpack* out);
+void tk_free_seqpack(tk_seqpack* out);
+
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token
  * at POSITION i of the reference's all_special_tokens vector (src/tekkenizer.rs:108-116, 536-540);

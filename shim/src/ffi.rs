@@ -65,6 +65,31 @@ pub struct TkDense {
     pub row_len: u64,
     pub n_truncated: u64,
 }
+// packed fixed-length training rows (tk_seqpack_opts.flags; include/tekken_hip.h has the definition)
+pub const TK_SEQPACK_I64: u32 = 1;
+pub const TK_SEQPACK_POSITIONS: u32 = 2;
+pub const TK_SEQPACK_SEGMENTS: u32 = 4;
+pub const TK_SEQPACK_CU_SEQLENS: u32 = 8;
+pub const TK_SEQPACK_DROP_LAST: u32 = 16;
+#[repr(C)]
+pub struct TkSeqpackOpts {
+    pub seq_len: u32,
+    pub pad_id: u32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkSeqpack {
+    pub input_ids: *mut c_void,
+    pub position_ids: *mut c_void,
+    pub segment_ids: *mut c_void,
+    pub cu_seqlens: *mut i32,
+    pub n_rows: u64,
+    pub row_len: u64,
+    pub n_used: u64,
+    pub n_left: u64,
+    pub n_segments: u64,
+    pub max_seqlen: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -111,6 +136,15 @@ extern "C" {
     pub fn tk_ragged_from_dense_device(ctx: *mut TkCtx, d_dense: *const c_void, n_docs: u64, row_len: u64, flags: c_int,
                                        d_lengths: *const c_void, pad_id: u32, hip_stream: *mut c_void, d_ids: *mut *mut c_void,
                                        d_id_offsets: *mut *mut c_void, n_ids: *mut u64) -> c_int;
+    // packed training rows: the id stream cut into rows of seq_len (+ position_ids, segment_ids, cu_seqlens), fused with encode, host form
+    pub fn tk_seqpack_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                      opts: *const TkSeqpackOpts, hip_stream: *mut c_void, out: *mut TkSeqpack) -> c_int;
+    pub fn tk_encode_batch_device_seqpack(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                          add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkSeqpackOpts, hip_stream: *mut c_void,
+                                          d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkSeqpack) -> c_int;
+    pub fn tk_encode_batch_seqpack(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                   validate_utf8: c_int, opts: *const TkSeqpackOpts, out: *mut TkSeqpack) -> c_int;
+    pub fn tk_free_seqpack(out: *mut TkSeqpack);
     // memo of merged pieces (round 4): a device table {unknown piece of 2..16 bytes -> its <= 4 ids}; never changes an id
     pub fn tk_ctx_set_memo(ctx: *mut TkCtx, log2_entries: c_int, policy: c_int) -> c_int;
     pub fn tk_ctx_memo_clear(ctx: *mut TkCtx) -> c_int;

@@ -30,6 +30,7 @@ TK_OK = 0
 CHECK_OFFSETS, CHECK_UTF8 = 1, 2   # tk_encode_batch_device_ex
 SPANS_CHECK_COVER, SPANS_CHECK_BYTES = 4, 8   # the spans entries (tk_token_spans_device, tk_encode_batch_*spans)
 DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
+SEQPACK_I64, SEQPACK_POSITIONS, SEQPACK_SEGMENTS, SEQPACK_CU_SEQLENS, SEQPACK_DROP_LAST = 1, 2, 4, 8, 16   # tk_seqpack_opts.flags (the packed entries)
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
 TK_ERR_INVALID_UTF8 = -3
@@ -80,6 +81,16 @@ class _DenseOpts(ctypes.Structure):
 class _Dense(ctypes.Structure):
     _fields_ = [("ids", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("lengths", ctypes.c_void_p),
                 ("n_docs", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_truncated", ctypes.c_uint64)]
+
+
+class _SeqpackOpts(ctypes.Structure):
+    _fields_ = [("seq_len", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class _Seqpack(ctypes.Structure):
+    _fields_ = [("input_ids", ctypes.c_void_p), ("position_ids", ctypes.c_void_p), ("segment_ids", ctypes.c_void_p),
+                ("cu_seqlens", ctypes.c_void_p), ("n_rows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_used", ctypes.c_uint64),
+                ("n_left", ctypes.c_uint64), ("n_segments", ctypes.c_uint64), ("max_seqlen", ctypes.c_uint64)]
 
 
 _LIB = None
@@ -275,6 +286,17 @@ def lib():
         L.tk_ragged_from_dense_device.restype = ctypes.c_int
         L.tk_ragged_from_dense_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, ctypes.c_uint32, vp,
                                                   ctypes.POINTER(vp), ctypes.POINTER(vp), u64p]
+    if hasattr(L, "tk_seqpack_from_ids_device"):   # (packed training rows: libraries built before them still load through TK_HIP_LIB)
+        op, pp = ctypes.POINTER(_SeqpackOpts), ctypes.POINTER(_Seqpack)
+        L.tk_seqpack_from_ids_device.restype = ctypes.c_int
+        L.tk_seqpack_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, op, vp, pp]
+        L.tk_encode_batch_device_seqpack.restype = ctypes.c_int
+        L.tk_encode_batch_device_seqpack.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, pp]
+        L.tk_encode_batch_seqpack.restype = ctypes.c_int
+        L.tk_encode_batch_seqpack.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, pp]
+        L.tk_free_seqpack.restype = None
+        L.tk_free_seqpack.argtypes = [pp]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -341,6 +363,28 @@ class DenseResult:
         shape = (self.n_docs, self.row_len)
         return (DeviceView(self.ids_ptr, shape, self.typestr), DeviceView(self.mask_ptr, shape, "|u1") if self.mask_ptr else None,
                 DeviceView(self.lengths_ptr, self.n_docs, "<i4"))
+
+
+class SeqpackResult:
+    """What the device packed entries return (tk_seqpack): raw device pointers of context-owned buffers, valid until the next
+    packed call on the context.  input_ids_ptr / position_ids_ptr / segment_ids_ptr: int32 or int64 [n_rows, row_len] (an
+    unselected one: None); cu_seqlens_ptr: int32 [n_segments + 1] or None."""
+
+    def __init__(self, p, flags):
+        self.input_ids_ptr, self.position_ids_ptr, self.segment_ids_ptr = p.input_ids or 0, p.position_ids or None, p.segment_ids or None
+        self.cu_seqlens_ptr = p.cu_seqlens or None
+        self.n_rows, self.row_len, self.n_used, self.n_left = int(p.n_rows), int(p.row_len), int(p.n_used), int(p.n_left)
+        self.n_segments, self.max_seqlen = int(p.n_segments), int(p.max_seqlen)
+        self.typestr = "<i8" if flags & SEQPACK_I64 else "<i4"
+
+    def views(self):
+        """(input_ids, position_ids or None, segment_ids or None -- views [n_rows, row_len] --, cu_seqlens view [n_segments + 1]
+        or None) -- DeviceView objects."""
+        shape = (self.n_rows, self.row_len)
+        return (DeviceView(self.input_ids_ptr, shape, self.typestr),
+                DeviceView(self.position_ids_ptr, shape, self.typestr) if self.position_ids_ptr else None,
+                DeviceView(self.segment_ids_ptr, shape, self.typestr) if self.segment_ids_ptr else None,
+                DeviceView(self.cu_seqlens_ptr, self.n_segments + 1, "<i4") if self.cu_seqlens_ptr else None)
 
 
 class Engine:
@@ -582,6 +626,60 @@ class Engine:
         self.last_n_truncated = int(d.n_truncated)
         lib().tk_free_dense(ctypes.byref(d))
         return dense, mask, lengths
+
+    def seqpack_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, seq_len, pad_id=0, flags=0, stream=0):
+        """tk_seqpack_from_ids_device: ragged ids resident in HBM -> the id stream cut into rows of seq_len (+ position_ids,
+        segment_ids, cu_seqlens as flags select); the definition is in include/tekken_hip.h.  Returns a SeqpackResult
+        (context-owned device buffers, apart from the encode, spans and dense outputs)."""
+        o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
+        rc = _need("tk_seqpack_from_ids_device")(self._h, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                                                 ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(p))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return SeqpackResult(p, int(flags))
+
+    def encode_batch_device_seqpack(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, seq_len, add_bos=True, add_eos=True, pad_id=0, flags=0,
+                                    checks=0, stream=0):
+        """tk_encode_batch_device_seqpack: encode_batch_device + the packed pass on the same stream.
+        Returns (d_ids_ptr, d_out_offs_ptr, n_ids, SeqpackResult), all context-owned."""
+        o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
+        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        rc = _need("tk_encode_batch_device_seqpack")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                                                     int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                                                     ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(p))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return d_ids.value, d_oo.value, int(n.value), SeqpackResult(p, int(flags))
+
+    def encode_batch_seqpack(self, data, offs, seq_len, add_bos=True, add_eos=True, validate_utf8=False, pad_id=0, flags=0):
+        """tk_encode_batch_seqpack, host in / host out: a dict of numpy arrays (input_ids, position_ids, segment_ids [n_rows, seq_len]
+        int32 or int64, cu_seqlens int32 [n_segments + 1]; an unselected one: None) and the counts n_rows, n_used, n_left,
+        n_segments, max_seqlen."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        rc = _need("tk_encode_batch_seqpack")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                                              int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(p))
+        if rc != TK_OK:
+            raise self._err(rc)
+        R, L = int(p.n_rows), int(p.row_len)
+        dt = np.int64 if flags & SEQPACK_I64 else np.int32
+
+        def take(ptr, n, dtype):
+            if n == 0:
+                return np.zeros(0, dtype)
+            raw = (ctypes.c_uint8 * (n * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(raw, dtype=dtype, count=n).copy()
+
+        out = {"input_ids": take(p.input_ids, R * L, dt).reshape(R, L),
+               "position_ids": take(p.position_ids, R * L, dt).reshape(R, L) if p.position_ids else None,
+               "segment_ids": take(p.segment_ids, R * L, dt).reshape(R, L) if p.segment_ids else None,
+               "cu_seqlens": take(p.cu_seqlens, int(p.n_segments) + 1, np.int32) if p.cu_seqlens else None,
+               "max_seqlen": int(p.max_seqlen), "n_rows": R, "n_used": int(p.n_used), "n_left": int(p.n_left),
+               "n_segments": int(p.n_segments)}
+        lib().tk_free_seqpack(ctypes.byref(p))
+        return out
 
     def ragged_from_dense_device(self, d_dense_ptr, n_docs, row_len, flags=0, d_lengths_ptr=0, pad_id=0, stream=0):
         """tk_ragged_from_dense_device: dense rows in HBM (int32, or int64 with DENSE_I64; DENSE_PAD_LEFT) -> (d_ids_ptr,
@@ -930,6 +1028,54 @@ class Tekkenizer:
 
         return {"input_ids": wrap(v_ids, (D, L), tdt), "attention_mask": wrap(v_mask, (D, L), torch.uint8) if return_mask else None,
                 "lengths": wrap(v_len, (D,), torch.int32), "n_truncated": res.n_truncated}
+
+    def encode_batch_packed(self, docs, seq_len, add_bos=True, add_eos=True, drop_last=False, pad_id=None, dtype="int64",
+                            return_position_ids=True, return_segment_ids=True, return_cu_seqlens=True, return_tensors="pt", copy=True):
+        """Packed pre-training rows (tk_encode_batch_device_seqpack / tk_encode_batch_seqpack; the definition is in
+        include/tekken_hip.h): the documents' ids, BOS / EOS included, are one stream that is cut into rows of seq_len.
+        {"input_ids", "position_ids", "segment_ids": [n_rows, seq_len] of `dtype` ("int64" | "int32"), "cu_seqlens": int32
+        [n_segments + 1] (offsets into the flattened tensor, for variable-length attention), "max_seqlen", "n_rows", "n_used",
+        "n_left", "n_segments": int}; an unselected tensor is None.  Positions restart and segment numbers advance at every document
+        start and row start.  drop_last: no padded last row; the last n_left ids of the stream are not in the tensor (carry them
+        into the next batch).  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on the tokenizer's GPU (copy=False:
+        views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
+        eng = self._device_engine()
+        if dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed: unknown dtype / return_tensors value")
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        if not 0 <= int(seq_len) < 2 ** 32:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed: seq_len %r" % (seq_len,))
+        flags = (SEQPACK_I64 if dtype == "int64" else 0) | (SEQPACK_POSITIONS if return_position_ids else 0) \
+            | (SEQPACK_SEGMENTS if return_segment_ids else 0) | (SEQPACK_CU_SEQLENS if return_cu_seqlens else 0) \
+            | (SEQPACK_DROP_LAST if drop_last else 0)
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        if return_tensors == "np":
+            return eng.encode_batch_seqpack(data, offs, seq_len, add_bos, add_eos, False, pad, flags)
+        import torch
+        d_bytes = torch.from_numpy(data if len(data) else np.zeros(1, np.uint8)).cuda()
+        d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
+        stream = torch.cuda.current_stream().cuda_stream
+        _, _, _, res = eng.encode_batch_device_seqpack(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), seq_len, add_bos, add_eos,
+                                                       pad, flags, CHECK_OFFSETS, stream)
+        tdt = torch.int64 if dtype == "int64" else torch.int32
+
+        def wrap(view, shape, tdtype):
+            if view is None:
+                return None
+            if 0 in shape:            # (nothing behind the pointer to look at)
+                return torch.empty(shape, dtype=tdtype, device="cuda")
+            t = torch.as_tensor(view, device="cuda")
+            return t.clone() if copy else t
+
+        v_ids, v_pos, v_seg, v_cu = res.views()
+        shape = (res.n_rows, res.row_len)
+        return {"input_ids": wrap(v_ids, shape, tdt), "position_ids": wrap(v_pos, shape, tdt), "segment_ids": wrap(v_seg, shape, tdt),
+                "cu_seqlens": wrap(v_cu, (res.n_segments + 1,), torch.int32), "max_seqlen": res.max_seqlen, "n_rows": res.n_rows,
+                "n_used": res.n_used, "n_left": res.n_left, "n_segments": res.n_segments}
 
     def decode_batch_padded(self, input_ids, lengths=None, policy=SpecialTokenPolicy.Ignore, pad_id=None, padding_side="right"):
         """Batch decode of dense rows (tk_ragged_from_dense_device + tk_decode_batch_device): input_ids [B, L], int32 or int64, a

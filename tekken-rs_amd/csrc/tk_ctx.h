@@ -110,6 +110,9 @@ struct tk_ctx {
     // lengths of the inverse.  Apart from every encode / spans / decode buffer, allocated at the first dense call
     DevBuf dn_ids, dn_mask, dn_len, dn_stat, dn_rids, dn_roffs, dn_rlens;
     int dense_nt = -1;         // non-temporal stores of the dense kernel (TK_DENSE_NT: A / B; read at the first dense call, -1 = not yet)
+    // the packed training rows (tk_seqpack.hip): the three tensors, cu_seqlens and the two statistics words; the work arrays
+    // (flags and their scans, the compacted starts, the scan workspace).  Apart from every other buffer, allocated at the first packed call
+    DevBuf sp_ids, sp_pos, sp_seg, sp_cu, sp_stat, sp_flags, sp_aflags, sp_fpos, sp_apos, sp_starts, sp_aligned, sp_bsum;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy

@@ -146,6 +146,31 @@ struct TkRaggedArgs {
 hipError_t tk_launch_ragged_rowlen(const TkRaggedArgs& a, int i64, hipStream_t s);
 hipError_t tk_launch_ragged_copy(const TkRaggedArgs& a, int i64, hipStream_t s);
 
+// ---- packed fixed-length training rows (tk_seqpack.hip) ----
+struct TkSeqpackArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents: the stream
+    const uint64_t* id_offs;   // [n_docs + 1]
+    uint64_t n_docs;
+    uint32_t row_len, pad_id;  // L (0 < L < 2^31)
+    uint64_t n_rows, n_used;   // rows of the tensor; ids that go into it (the rest of the last row is pad)
+    uint32_t* flags;           // [n_docs] the document has ids
+    uint32_t* aflags;          // [n_docs] ... and starts at a multiple of L
+    const uint64_t* fpos;      // [n_docs + 1] exclusive scan of flags; [n_docs] = M, the non-empty documents
+    const uint64_t* apos;      // [n_docs + 1] exclusive scan of aflags
+    uint64_t* starts;          // [M + 1] starts of the non-empty documents, strictly increasing; [M] = n_ids
+    uint64_t* n_aligned;       // [M + 1] apos of the same documents: aligned starts before each
+    void* out_ids;             // [n_rows * L] int32 or int64
+    void* out_pos;             // the same shape, or NULL
+    void* out_seg;             // the same shape, or NULL
+    int32_t* cu;               // [n_segments + 1] (at most n_docs + n_rows + 1), or NULL
+    unsigned long long* stat;  // [0] = n_segments, [1] = max_seqlen (atomicMax: zeroed by the caller)
+    uint32_t ids_al16;         // ids is 16-byte aligned (set by the launcher)
+};
+hipError_t tk_launch_seqpack_flags(const TkSeqpackArgs& a, hipStream_t s);    // flags, aflags
+hipError_t tk_launch_seqpack_starts(const TkSeqpackArgs& a, hipStream_t s);   // starts, n_aligned (behind the two scans)
+hipError_t tk_launch_seqpack(const TkSeqpackArgs& a, int i64, hipStream_t s); // the tensors; n_rows == 0: nothing is launched
+hipError_t tk_launch_seqpack_cu(const TkSeqpackArgs& a, hipStream_t s);       // cu_seqlens (a.cu != NULL), n_segments, max_seqlen
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
