@@ -323,6 +323,67 @@ int tk_encode_batch_seqpack(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* d
                             int validate_utf8, const tk_seqpack_opts* opts, tk_seqpack* out);
 void tk_free_seqpack(tk_seqpack* out);
 
+/* ---- chat batches: text parts joined with control ids, plus labels (no reference equivalent: the reference never makes a
+ * control token out of text -- "[INST]" in the input stays plain text -- and get_control_token, src/tekkenizer.rs:331-341, only
+ * hands out the id) ----
+ * A batch has C conversations over P parts.  Conversation c owns parts conv_offsets[c] .. conv_offsets[c+1] (C + 1 uint64,
+ * [0] = 0, [C] = P, non-decreasing).  Part p has a text -- document p of the usual packed bytes / doc_offsets[P + 1], possibly
+ * empty --, part_ctrl[p] (uint32: a control id, or TK_JOIN_NONE) and part_flags[p] (uint32: TK_PART_LABEL_CTRL |
+ * TK_PART_LABEL_TEXT; a NULL part_flags means all zero; other bits are ignored).
+ *   1. E_p = the encoding of part p's text alone, without BOS / EOS: what tk_encode_batch_device returns for document p, so no
+ *      token spans a part boundary.  T_p = [part_ctrl[p]] (only if it is not TK_JOIN_NONE) followed by E_p.  J_c = the
+ *      concatenation of T_p over the parts of c, in order.
+ *   2. ids (uint32, N = sum |T_p|) = J_0 + J_1 + ...; offsets (uint64, C + 1) = the exclusive prefix sum of |J_c|.  n_ctrl = the
+ *      number of parts with a control id: N = n_text_ids + n_ctrl.
+ *   3. labels (int32, N, only with TK_JOIN_LABELS, else NULL): the element of a control id is that id if part_flags &
+ *      TK_PART_LABEL_CTRL, else ignore_index; the element of a text id is that id if part_flags & TK_PART_LABEL_TEXT, else
+ *      ignore_index (callers pass -100).  n_labelled = the number of elements that are not ignored by these rules; it is filled
+ *      whether or not labels is selected.
+ *   4. part_index (uint32, N, only with TK_JOIN_PART_INDEX, else NULL) = p - conv_offsets[c] of the part the element came from.
+ *   5. Valid and empty: C == 0 (conv_offsets = [0]; P must be 0), conversations without parts, parts with neither a control id
+ *      nor text, P == 0.
+ *   6. TK_ERR_INVALID_ARG, nothing written, an earlier join result stays readable: an unknown flag (opts or checks); a NULL
+ *      required argument; C == 0 with P > 0; P == 0 with ids; and, with TK_CHECK_PARTS (a bit of the `checks` word beside
+ *      TK_CHECK_OFFSETS / TK_CHECK_UTF8), conv_offsets that do not start at 0, decrease or do not end at P, or a control id that is
+ *      neither TK_JOIN_NONE nor < num_special_tokens -- the message names the first bad conversation or part.  The host entry
+ *      always makes these checks, on the host.  Without the check on a device entry a control id is copied as given, and
+ *      malformed offsets are out-of-bounds indexing on the device, as in tk_dense_from_ids_device.  A failed allocation is
+ *      TK_ERR_RUNTIME.
+ *   7. out's buffers are owned by the context, valid until the next join call on it, and SEPARATE from the encode, spans, dense,
+ *      packed and decode buffers: ids / offsets can be passed straight to tk_dense_from_ids_device, tk_seqpack_from_ids_device,
+ *      tk_token_spans_device (without checks) or tk_decode_batch_device.
+ * The join is a separate pass behind the unchanged encode pipeline (csrc/tk_join.hip): every element is written once, in 16-byte
+ * stores but for the last N % 4 elements; an unselected output is not touched.  The buffers are sized for n_ids + P elements, so
+ * nothing is read before the launches, and one wait at the end reads N, n_ctrl and n_labelled.  TK_CHECK_PARTS on a device entry
+ * costs one small kernel and one more wait in front: the earlier result can only be given up once the arguments are accepted. */
+#define TK_CHECK_PARTS 16
+#define TK_JOIN_NONE 0xFFFFFFFFu
+#define TK_PART_LABEL_CTRL 1
+#define TK_PART_LABEL_TEXT 2
+#define TK_JOIN_LABELS 1
+#define TK_JOIN_PART_INDEX 2
+typedef struct tk_join_opts { int32_t ignore_index; uint32_t flags; } tk_join_opts;
+typedef struct tk_join { uint32_t* ids; uint64_t* offsets; int32_t* labels; uint32_t* part_index;
+                         uint64_t n_convs, n_parts, n_ids, n_ctrl, n_labelled; } tk_join;
+/* ids already on the device (encode's own outputs for add_bos = add_eos = 0, or the caller's; d_id_offsets: n_parts + 1 uint64,
+ * [0] = 0, non-decreasing, [n_parts] = n_ids -- NOT checked) -> the joined stream.  d_part_ctrl: n_parts uint32; d_part_flags:
+ * n_parts uint32 or NULL; d_conv_offsets: n_convs + 1 uint64.  checks: 0 | TK_CHECK_PARTS.  The work is enqueued on hip_stream
+ * and the call returns after the stream has drained. */
+int tk_join_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_parts, uint64_t n_ids,
+                            const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                            int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out);
+/* tk_encode_batch_device_ex(add_bos = 0, add_eos = 0) over the part texts + the join on the same stream.  checks may combine
+ * TK_CHECK_OFFSETS / TK_CHECK_UTF8 (the text) with TK_CHECK_PARTS. */
+int tk_encode_parts_device_join(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
+                                const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                                int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out);
+/* Host in / host out: tk_encode_batch + the join (batches of the one-launch small path included).  out's buffers are pinned host
+ * memory, released with tk_free_join (an unselected output is NULL). */
+int tk_encode_parts_join(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_parts, const uint32_t* part_ctrl,
+                         const uint32_t* part_flags, const uint64_t* conv_offsets, uint64_t n_convs, int validate_utf8,
+                         const tk_join_opts* opts, tk_join* out);
+void tk_free_join(tk_join* out);
+
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token
  * at POSITION i of the reference's all_special_tokens vector (src/tekkenizer.rs:108-116, 536-540);

@@ -90,6 +90,30 @@ pub struct TkSeqpack {
     pub n_segments: u64,
     pub max_seqlen: u64,
 }
+// chat batches: parts joined with control ids, plus labels (include/tekken_hip.h has the definition)
+pub const TK_CHECK_PARTS: c_int = 16;
+pub const TK_JOIN_NONE: u32 = 0xFFFF_FFFF;
+pub const TK_PART_LABEL_CTRL: u32 = 1;
+pub const TK_PART_LABEL_TEXT: u32 = 2;
+pub const TK_JOIN_LABELS: u32 = 1;
+pub const TK_JOIN_PART_INDEX: u32 = 2;
+#[repr(C)]
+pub struct TkJoinOpts {
+    pub ignore_index: i32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkJoin {
+    pub ids: *mut u32,
+    pub offsets: *mut u64,
+    pub labels: *mut i32,
+    pub part_index: *mut u32,
+    pub n_convs: u64,
+    pub n_parts: u64,
+    pub n_ids: u64,
+    pub n_ctrl: u64,
+    pub n_labelled: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -145,6 +169,17 @@ extern "C" {
     pub fn tk_encode_batch_seqpack(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
                                    validate_utf8: c_int, opts: *const TkSeqpackOpts, out: *mut TkSeqpack) -> c_int;
     pub fn tk_free_seqpack(out: *mut TkSeqpack);
+    // chat batches: the ids of text parts joined with control ids per conversation (+ labels, part_index), fused with encode, host form
+    pub fn tk_join_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_parts: u64, n_ids: u64,
+                                   d_part_ctrl: *const c_void, d_part_flags: *const c_void, d_conv_offsets: *const c_void, n_convs: u64,
+                                   checks: c_int, opts: *const TkJoinOpts, hip_stream: *mut c_void, out: *mut TkJoin) -> c_int;
+    pub fn tk_encode_parts_device_join(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_parts: u64, n_bytes: u64,
+                                       d_part_ctrl: *const c_void, d_part_flags: *const c_void, d_conv_offsets: *const c_void, n_convs: u64,
+                                       checks: c_int, opts: *const TkJoinOpts, hip_stream: *mut c_void, out: *mut TkJoin) -> c_int;
+    pub fn tk_encode_parts_join(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_parts: u64, part_ctrl: *const u32,
+                                part_flags: *const u32, conv_offsets: *const u64, n_convs: u64, validate_utf8: c_int,
+                                opts: *const TkJoinOpts, out: *mut TkJoin) -> c_int;
+    pub fn tk_free_join(out: *mut TkJoin);
     // memo of merged pieces (round 4): a device table {unknown piece of 2..16 bytes -> its <= 4 ids}; never changes an id
     pub fn tk_ctx_set_memo(ctx: *mut TkCtx, log2_entries: c_int, policy: c_int) -> c_int;
     pub fn tk_ctx_memo_clear(ctx: *mut TkCtx) -> c_int;

@@ -175,6 +175,41 @@ impl HipEngine {
         };
         Ok(out)
     }
+
+    /// Chat batch (tk_encode_parts_join): every part is `(control id or None, text, label the control id, label the text)`, a
+    /// conversation is a slice of parts.  Returns `(ids, offsets [C + 1], labels)`: all conversations back to back, every text
+    /// encoded on its own without BOS / EOS, its control id in front; `labels[i]` is the id or `ignore_index`.
+    pub fn encode_conversations(&self, convs: &[&[(Option<u32>, &str, bool, bool)]], ignore_index: i32)
+                                -> Result<(Vec<u32>, Vec<u64>, Vec<i32>), HipError> {
+        let parts: Vec<&(Option<u32>, &str, bool, bool)> = convs.iter().flat_map(|c| c.iter()).collect();
+        let texts: Vec<&str> = parts.iter().map(|p| p.1).collect();
+        let (bytes, offs) = pack_docs(&texts);
+        let ctrl: Vec<u32> = parts.iter().map(|p| p.0.unwrap_or(TK_JOIN_NONE)).collect();
+        let flags: Vec<u32> = parts.iter().map(|p| (if p.2 { TK_PART_LABEL_CTRL } else { 0 }) | (if p.3 { TK_PART_LABEL_TEXT } else { 0 })).collect();
+        let mut conv_offs: Vec<u64> = vec![0];
+        for c in convs {
+            conv_offs.push(conv_offs[conv_offs.len() - 1] + c.len() as u64);
+        }
+        let opts = TkJoinOpts { ignore_index, flags: TK_JOIN_LABELS };
+        let mut j = TkJoin { ids: std::ptr::null_mut(), offsets: std::ptr::null_mut(), labels: std::ptr::null_mut(),
+                             part_index: std::ptr::null_mut(), n_convs: 0, n_parts: 0, n_ids: 0, n_ctrl: 0, n_labelled: 0 };
+        let rc = unsafe {
+            tk_encode_parts_join(self.ctx, bytes.as_ptr(), offs.as_ptr(), parts.len() as u64, ctrl.as_ptr(), flags.as_ptr(), conv_offs.as_ptr(),
+                                 convs.len() as u64, 0, &opts, &mut j)
+        };
+        if rc != TK_OK {
+            return Err(map_err(rc, unsafe { tk_last_error(self.ctx) }));
+        }
+        let n = j.n_ids as usize;
+        let out = unsafe {
+            let ids = std::slice::from_raw_parts(j.ids as *const u32, n).to_vec();
+            let offsets = std::slice::from_raw_parts(j.offsets as *const u64, convs.len() + 1).to_vec();
+            let labels = std::slice::from_raw_parts(j.labels as *const i32, n).to_vec();
+            tk_free_join(&mut j);
+            (ids, offsets, labels)
+        };
+        Ok(out)
+    }
 }
 impl Drop for HipEngine {
     fn drop(&mut self) {

@@ -31,6 +31,10 @@ CHECK_OFFSETS, CHECK_UTF8 = 1, 2   # tk_encode_batch_device_ex
 SPANS_CHECK_COVER, SPANS_CHECK_BYTES = 4, 8   # the spans entries (tk_token_spans_device, tk_encode_batch_*spans)
 DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
 SEQPACK_I64, SEQPACK_POSITIONS, SEQPACK_SEGMENTS, SEQPACK_CU_SEQLENS, SEQPACK_DROP_LAST = 1, 2, 4, 8, 16   # tk_seqpack_opts.flags (the packed entries)
+CHECK_PARTS = 16   # the join entries: conv_offsets and the control ids are checked (beside CHECK_OFFSETS / CHECK_UTF8 in one word)
+JOIN_NONE = 0xFFFFFFFF   # part_ctrl: the part has no control id
+PART_LABEL_CTRL, PART_LABEL_TEXT = 1, 2   # part_flags
+JOIN_LABELS, JOIN_PART_INDEX = 1, 2   # tk_join_opts.flags (the join entries)
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
 TK_ERR_INVALID_UTF8 = -3
@@ -91,6 +95,16 @@ class _Seqpack(ctypes.Structure):
     _fields_ = [("input_ids", ctypes.c_void_p), ("position_ids", ctypes.c_void_p), ("segment_ids", ctypes.c_void_p),
                 ("cu_seqlens", ctypes.c_void_p), ("n_rows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_used", ctypes.c_uint64),
                 ("n_left", ctypes.c_uint64), ("n_segments", ctypes.c_uint64), ("max_seqlen", ctypes.c_uint64)]
+
+
+class _JoinOpts(ctypes.Structure):
+    _fields_ = [("ignore_index", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
+class _Join(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("part_index", ctypes.c_void_p),
+                ("n_convs", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_ids", ctypes.c_uint64), ("n_ctrl", ctypes.c_uint64),
+                ("n_labelled", ctypes.c_uint64)]
 
 
 _LIB = None
@@ -297,6 +311,16 @@ def lib():
         L.tk_encode_batch_seqpack.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, pp]
         L.tk_free_seqpack.restype = None
         L.tk_free_seqpack.argtypes = [pp]
+    if hasattr(L, "tk_join_from_ids_device"):   # (chat batches: libraries built before them still load through TK_HIP_LIB)
+        op, jp = ctypes.POINTER(_JoinOpts), ctypes.POINTER(_Join)
+        L.tk_join_from_ids_device.restype = ctypes.c_int
+        L.tk_join_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, op, vp, jp]
+        L.tk_encode_parts_device_join.restype = ctypes.c_int
+        L.tk_encode_parts_device_join.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, op, vp, jp]
+        L.tk_encode_parts_join.restype = ctypes.c_int
+        L.tk_encode_parts_join.argtypes = [vp, u8p, u64p, ctypes.c_uint64, u32p, u32p, u64p, ctypes.c_uint64, ctypes.c_int, op, jp]
+        L.tk_free_join.restype = None
+        L.tk_free_join.argtypes = [jp]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -385,6 +409,24 @@ class SeqpackResult:
                 DeviceView(self.position_ids_ptr, shape, self.typestr) if self.position_ids_ptr else None,
                 DeviceView(self.segment_ids_ptr, shape, self.typestr) if self.segment_ids_ptr else None,
                 DeviceView(self.cu_seqlens_ptr, self.n_segments + 1, "<i4") if self.cu_seqlens_ptr else None)
+
+
+class JoinResult:
+    """What the device join entries return (tk_join): raw device pointers of context-owned buffers, valid until the next join call
+    on the context.  ids_ptr: uint32 [n_ids]; offsets_ptr: uint64 [n_convs + 1]; labels_ptr: int32 [n_ids] or None;
+    part_index_ptr: uint32 [n_ids] or None."""
+
+    def __init__(self, j):
+        self.ids_ptr, self.offsets_ptr, self.labels_ptr, self.part_index_ptr = j.ids or 0, j.offsets or 0, j.labels or None, j.part_index or None
+        self.n_convs, self.n_parts, self.n_ids = int(j.n_convs), int(j.n_parts), int(j.n_ids)
+        self.n_ctrl, self.n_labelled = int(j.n_ctrl), int(j.n_labelled)
+
+    def views(self):
+        """(ids as int32 [n_ids], offsets as int64 [n_convs + 1], labels int32 [n_ids] or None, part_index as int32 [n_ids] or
+        None) -- DeviceView objects."""
+        return (DeviceView(self.ids_ptr, self.n_ids, "<i4"), DeviceView(self.offsets_ptr, self.n_convs + 1, "<i8"),
+                DeviceView(self.labels_ptr, self.n_ids, "<i4") if self.labels_ptr else None,
+                DeviceView(self.part_index_ptr, self.n_ids, "<i4") if self.part_index_ptr else None)
 
 
 class Engine:
@@ -679,6 +721,70 @@ class Engine:
                "max_seqlen": int(p.max_seqlen), "n_rows": R, "n_used": int(p.n_used), "n_left": int(p.n_left),
                "n_segments": int(p.n_segments)}
         lib().tk_free_seqpack(ctypes.byref(p))
+        return out
+
+    def join_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, d_part_ctrl_ptr, d_part_flags_ptr, d_conv_offs_ptr, n_convs,
+                             ignore_index=-100, flags=0, checks=0, stream=0):
+        """tk_join_from_ids_device: ragged ids of parts resident in HBM (+ part_ctrl uint32[n_parts], part_flags uint32[n_parts] or
+        0, conv_offsets uint64[n_convs + 1], all raw device pointers) -> the joined stream; the definition is in
+        include/tekken_hip.h.  checks: 0 | CHECK_PARTS.  Returns a JoinResult (context-owned device buffers, apart from every
+        other output)."""
+        o, j = _JoinOpts(int(ignore_index), int(flags)), _Join()
+        rc = _need("tk_join_from_ids_device")(self._h, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr or None), n_parts, n_ids,
+                                              ctypes.c_void_p(d_part_ctrl_ptr or None), ctypes.c_void_p(d_part_flags_ptr or None),
+                                              ctypes.c_void_p(d_conv_offs_ptr or None), n_convs, int(checks), ctypes.byref(o),
+                                              ctypes.c_void_p(stream), ctypes.byref(j))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return JoinResult(j)
+
+    def encode_parts_device_join(self, d_bytes_ptr, d_offs_ptr, n_parts, n_bytes, d_part_ctrl_ptr, d_part_flags_ptr, d_conv_offs_ptr, n_convs,
+                                 ignore_index=-100, flags=0, checks=0, stream=0):
+        """tk_encode_parts_device_join: the part texts encoded one by one without BOS / EOS + the join on the same stream.
+        checks may mix CHECK_OFFSETS / CHECK_UTF8 with CHECK_PARTS.  Returns a JoinResult."""
+        o, j = _JoinOpts(int(ignore_index), int(flags)), _Join()
+        rc = _need("tk_encode_parts_device_join")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_parts, n_bytes,
+                                                  ctypes.c_void_p(d_part_ctrl_ptr or None), ctypes.c_void_p(d_part_flags_ptr or None),
+                                                  ctypes.c_void_p(d_conv_offs_ptr or None), n_convs, int(checks), ctypes.byref(o),
+                                                  ctypes.c_void_p(stream), ctypes.byref(j))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return JoinResult(j)
+
+    def encode_parts_join(self, data, offs, part_ctrl, part_flags, conv_offs, ignore_index=-100, flags=0, validate_utf8=False):
+        """tk_encode_parts_join, host in / host out: a dict of numpy arrays (ids uint32 [N], offsets uint64 [n_convs + 1], labels
+        int32 [N], part_index uint32 [N]; an unselected one: None) and the counts n_ids, n_ctrl, n_labelled.  part_flags may be
+        None (all zero)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        ctrl = np.ascontiguousarray(part_ctrl, dtype=np.uint32)
+        pf = None if part_flags is None else np.ascontiguousarray(part_flags, dtype=np.uint32)
+        conv = np.ascontiguousarray(conv_offs, dtype=np.uint64)
+        n_parts = len(offs) - 1
+        if len(ctrl) != n_parts or (pf is not None and len(pf) != n_parts) or len(conv) < 1:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_parts_join: one part_ctrl / part_flags entry per part, n_convs + 1 conv_offsets")
+        o, j = _JoinOpts(int(ignore_index), int(flags)), _Join()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        cbuf = ctrl if n_parts else np.zeros(1, np.uint32)
+        fbuf = None if pf is None else pf if n_parts else np.zeros(1, np.uint32)
+        rc = _need("tk_encode_parts_join")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), n_parts, _p(cbuf, ctypes.c_uint32),
+                                           None if fbuf is None else _p(fbuf, ctypes.c_uint32), _p(conv, ctypes.c_uint64), len(conv) - 1,
+                                           int(validate_utf8), ctypes.byref(o), ctypes.byref(j))
+        if rc != TK_OK:
+            raise self._err(rc)
+        N, C = int(j.n_ids), int(j.n_convs)
+
+        def take(ptr, n, dtype):
+            if n == 0:
+                return np.zeros(0, dtype)
+            raw = (ctypes.c_uint8 * (n * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(raw, dtype=dtype, count=n).copy()
+
+        out = {"ids": take(j.ids, N, np.uint32), "offsets": take(j.offsets, C + 1, np.uint64),
+               "labels": take(j.labels, N, np.int32) if j.labels else None,
+               "part_index": take(j.part_index, N, np.uint32) if j.part_index else None,
+               "n_ids": N, "n_ctrl": int(j.n_ctrl), "n_labelled": int(j.n_labelled)}
+        lib().tk_free_join(ctypes.byref(j))
         return out
 
     def ragged_from_dense_device(self, d_dense_ptr, n_docs, row_len, flags=0, d_lengths_ptr=0, pad_id=0, stream=0):
@@ -1076,6 +1182,137 @@ class Tekkenizer:
         return {"input_ids": wrap(v_ids, shape, tdt), "position_ids": wrap(v_pos, shape, tdt), "segment_ids": wrap(v_seg, shape, tdt),
                 "cu_seqlens": wrap(v_cu, (res.n_segments + 1,), torch.int32), "max_seqlen": res.max_seqlen, "n_rows": res.n_rows,
                 "n_used": res.n_used, "n_left": res.n_left, "n_segments": res.n_segments}
+
+    CHAT_ROLES = {"user": ("[INST]", "[/INST]", False), "system": ("[SYSTEM_PROMPT]", "[/SYSTEM_PROMPT]", False),
+                  "assistant": (None, "</s>", True)}
+
+    def _parts_of(self, convs):
+        """Conversations of (ctrl, text, label) parts -> (data, offs, part_ctrl, part_flags, conv_offs) as the join entries take them."""
+        names, texts, ctrl, pf, conv = {}, [], [], [], [0]
+        for parts in convs:
+            for part in parts:
+                if len(part) != 3:
+                    raise TokenizerError(TK_ERR_INVALID_ARG, "encode_conversations: a part is (ctrl, text, label)")
+                c, text, label = part
+                if isinstance(c, str):
+                    if c not in names:
+                        names[c] = self.get_control_token(c)      # (TokenNotFound for an unknown name)
+                    c = names[c]
+                ctrl.append(JOIN_NONE if c is None else int(c))
+                lc, lt = label if isinstance(label, (tuple, list)) else (label, label)
+                pf.append((PART_LABEL_CTRL if lc else 0) | (PART_LABEL_TEXT if lt else 0))
+                texts.append(text.encode("utf-8") if isinstance(text, str) else bytes(text or b""))
+            conv.append(len(texts))
+        data, offs = pack_docs(texts)
+        return data, offs, np.array(ctrl, np.uint32), np.array(pf, np.uint32), np.array(conv, np.uint64)
+
+    def _join_device(self, eng, parts, ignore_index, flags):
+        """The parts (from _parts_of) go up once; -> (JoinResult, stream).  The result's buffers are the context's."""
+        import torch
+        data, offs, ctrl, pf, conv = parts
+        up = [torch.from_numpy(x).cuda() for x in (data if len(data) else np.zeros(1, np.uint8), offs.astype(np.int64),
+                                                    (ctrl if len(ctrl) else np.zeros(1, np.uint32)).view(np.int32),
+                                                    (pf if len(pf) else np.zeros(1, np.uint32)).view(np.int32), conv.astype(np.int64))]
+        stream = torch.cuda.current_stream().cuda_stream
+        res = eng.encode_parts_device_join(up[0].data_ptr(), up[1].data_ptr(), len(ctrl), len(data), up[2].data_ptr(), up[3].data_ptr(),
+                                           up[4].data_ptr(), len(conv) - 1, ignore_index, flags, CHECK_OFFSETS | CHECK_PARTS, stream)
+        return res, stream
+
+    def encode_conversations(self, convs, return_labels=True, return_part_index=False, ignore_index=-100, return_tensors="pt", copy=True):
+        """Chat batches from explicit parts (tk_encode_parts_device_join / tk_encode_parts_join; the definition is in
+        include/tekken_hip.h).  convs: a list of conversations, each a list of parts (ctrl, text, label) -- ctrl: None, an id, or a
+        control-token name (get_control_token: an unknown one raises TokenNotFound); text: encoded on its own, without BOS / EOS,
+        so no token spans a part boundary and control strings inside it stay plain text; label: a bool, or a pair (ctrl, text).
+        -> {"input_ids": [N] all conversations back to back, "offsets": [C + 1], "labels": [N] int32 (the id, or ignore_index
+        where the part is not labelled), "part_index": [N], "n_labelled": int}; an unselected tensor is None.  return_tensors
+        "pt": torch tensors on the tokenizer's GPU (input_ids / labels / part_index int32, offsets int64; copy=False: views of
+        context-owned buffers, valid until the next call on this tokenizer); "np": numpy (uint32 / uint64 / int32 / uint32)."""
+        eng = self._device_engine()
+        if return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_conversations: unknown return_tensors value")
+        flags = (JOIN_LABELS if return_labels else 0) | (JOIN_PART_INDEX if return_part_index else 0)
+        parts = self._parts_of(convs)
+        if return_tensors == "np":
+            r = eng.encode_parts_join(*parts, ignore_index=ignore_index, flags=flags)
+            return {"input_ids": r["ids"], "offsets": r["offsets"], "labels": r["labels"], "part_index": r["part_index"],
+                    "n_labelled": r["n_labelled"]}
+        import torch
+        res, _ = self._join_device(eng, parts, ignore_index, flags)
+
+        def wrap(view, n, tdtype):
+            if view is None:
+                return None
+            if n == 0:                # (nothing behind the pointer to look at)
+                return torch.empty((0,), dtype=tdtype, device="cuda")
+            t = torch.as_tensor(view, device="cuda")
+            return t.clone() if copy else t
+
+        v_ids, v_offs, v_lab, v_pi = res.views()
+        return {"input_ids": wrap(v_ids, res.n_ids, torch.int32), "offsets": wrap(v_offs, res.n_convs + 1, torch.int64),
+                "labels": wrap(v_lab, res.n_ids, torch.int32), "part_index": wrap(v_pi, res.n_ids, torch.int32),
+                "n_labelled": res.n_labelled}
+
+    def _chat_parts(self, conversations, roles, add_bos):
+        table = dict(self.CHAT_ROLES)
+        table.update(roles or {})
+        convs = []
+        for msgs in conversations:
+            parts = [("<s>", "", False)] if add_bos else []
+            for m in msgs:
+                if m["role"] not in table:
+                    raise TokenizerError(TK_ERR_INVALID_ARG, "encode_chat: no entry in roles for %r" % (m["role"],))
+                opn, close, train = table[m["role"]]
+                parts.append((opn, m["content"], (False, bool(train))))
+                if close is not None:
+                    parts.append((close, "", bool(train)))
+            convs.append(parts)
+        return convs
+
+    def encode_chat(self, conversations, roles=None, add_bos=True, **kw):
+        """encode_conversations over messages: a conversation is a list of {"role", "content"}.  roles maps a role to (open control
+        name or None, close control name or None, train); given entries replace the defaults
+            user: ("[INST]", "[/INST]", False), system: ("[SYSTEM_PROMPT]", "[/SYSTEM_PROMPT]", False), assistant: (None, "</s>", True).
+        Layout of one conversation: "<s>" as one leading part (add_bos); then per message one part (open control id, the content)
+        and, if the role has a close token, one part (close control id, no text).  With train the content and the close token are
+        labelled; the open token never is, nor is "<s>".  The content is encoded on its own, so "[INST]" typed by a user stays
+        text.  This is the plain Mistral instruct layout as far as the vocabulary's control tokens describe it; parity with
+        mistral-common's templates (spacing, tool calls, where the system prompt goes in each version) is NOT claimed: that
+        package was not at hand to compare against.  **kw: as encode_conversations."""
+        return self.encode_conversations(self._chat_parts(conversations, roles, add_bos), **kw)
+
+    def encode_chat_padded(self, conversations, roles=None, add_bos=True, max_length=None, padding="longest", truncation_side="right",
+                           padding_side="right", pad_to_multiple_of=None, pad_id=None, dtype="int64", ignore_index=-100, return_mask=True):
+        """encode_chat as a model-ready batch: {"input_ids": [B, L], "attention_mask": uint8 [B, L] (None without return_mask),
+        "labels": [B, L] (ignore_index under the padding and under everything that is not trained), "lengths": int32 [B],
+        "n_truncated", "n_labelled" (before truncation)}, torch tensors on the tokenizer's GPU.  The joined ids and the labels
+        stream go through the dense pass of encode_batch_padded one after the other (the same options; "<s>" survives
+        truncation), the labels padded with ignore_index; dtype "int64" | "int32" is the type of input_ids and labels."""
+        eng = self._device_engine()
+        if padding not in ("longest", "max_length") or truncation_side not in ("left", "right") or padding_side not in ("left", "right") \
+                or dtype not in ("int64", "int32"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_chat_padded: unknown padding / side / dtype value")
+        import torch
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        res, stream = self._join_device(eng, self._parts_of(self._chat_parts(conversations, roles, add_bos)), ignore_index, JOIN_LABELS)
+        C, N = res.n_convs, res.n_ids
+        flags = (DENSE_FIXED if padding == "max_length" else 0) | (DENSE_TRUNC_LEFT if truncation_side == "left" else 0) \
+            | (DENSE_PAD_LEFT if padding_side == "left" else 0)
+
+        def dense(ptr, pad_value, fl, tdtype, want_mask):
+            d = eng.dense_from_ids_device(ptr if N else 0, res.offsets_ptr, C, N, max_length, pad_to_multiple_of, pad_value, int(bool(add_bos)), 0,
+                                          fl, stream)
+            shape = (d.n_docs, d.row_len)
+            v_ids, v_mask, v_len = d.views()
+            take = lambda v, sh, dt: torch.empty(sh, dtype=dt, device="cuda") if 0 in sh else torch.as_tensor(v, device="cuda").clone()
+            return d, take(v_ids, shape, tdtype), take(v_mask, shape, torch.uint8) if want_mask else None, take(v_len, (d.n_docs,), torch.int32)
+
+        i64 = dtype == "int64"
+        d, ids, mask, lengths = dense(res.ids_ptr, pad, flags | (DENSE_I64 if i64 else 0) | (DENSE_MASK if return_mask else 0),
+                                      torch.int64 if i64 else torch.int32, return_mask)
+        # (the labels are int32 with negative values: int32 elements through the pass, widened here -- which sign-extends)
+        _, labels, _, _ = dense(res.labels_ptr, int(ignore_index) & 0xFFFFFFFF, flags, torch.int32, False)
+        return {"input_ids": ids, "attention_mask": mask, "labels": labels.to(torch.int64) if i64 else labels, "lengths": lengths,
+                "n_truncated": d.n_truncated, "n_labelled": res.n_labelled}
 
     def decode_batch_padded(self, input_ids, lengths=None, policy=SpecialTokenPolicy.Ignore, pad_id=None, padding_side="right"):
         """Batch decode of dense rows (tk_ragged_from_dense_device + tk_decode_batch_device): input_ids [B, L], int32 or int64, a

@@ -1,0 +1,212 @@
+// tk_capi_join.cpp -- chat batches (include/tekken_hip.h tk_join_from_ids_device and the entries around it; csrc/tk_join.hip):
+// the ids of text parts, encoded one by one, joined with control ids into one stream per conversation, with labels and the part
+// index of every element.
+#include "tk_ctx.h"
+
+#define TK_JOIN_ALL_FLAGS (TK_JOIN_LABELS | TK_JOIN_PART_INDEX)
+
+// what can be refused before anything is on the device (step 6 of the definition)
+static int join_check_args(tk_ctx* c, uint64_t n_parts, uint64_t n_convs, const tk_join_opts* o) {
+    if (!o) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    if (o->flags & ~(uint32_t)TK_JOIN_ALL_FLAGS) { c->err = "unknown join flag"; return TK_ERR_INVALID_ARG; }
+    int rc = check_n_docs(c, n_parts);
+    if (rc != TK_OK) return rc;
+    if ((rc = check_n_docs(c, n_convs)) != TK_OK) return rc;
+    if (n_convs == 0 && n_parts) { c->err = "join: parts without a conversation"; return TK_ERR_INVALID_ARG; }
+    return TK_OK;
+}
+
+// the two messages of TK_CHECK_PARTS, the same from the host and the device check
+static int bad_conv(tk_ctx* c, uint64_t conv, uint64_t n_parts) {
+    c->err = "conv_offsets must start at 0, be non-decreasing and end at n_parts (" + std::to_string(n_parts) +
+             "): first violation at conversation " + std::to_string(conv);
+    return TK_ERR_INVALID_ARG;
+}
+static int bad_ctrl(tk_ctx* c, uint64_t part, uint32_t id) {
+    c->err = "part " + std::to_string(part) + ": control id " + std::to_string(id) + " is neither TK_JOIN_NONE nor below num_special_tokens (" +
+             std::to_string(c->host.num_special) + ")";
+    return TK_ERR_INVALID_ARG;
+}
+
+static int check_parts_host(tk_ctx* c, const uint32_t* ctrl, const uint64_t* conv, uint64_t P, uint64_t C) {
+    for (uint64_t i = 0; i <= C; ++i)
+        if ((i == 0 && conv[0] != 0) || (i < C && conv[i + 1] < conv[i]) || (i == C && conv[C] != P)) return bad_conv(c, i, P);
+    for (uint64_t p = 0; p < P; ++p)
+        if (ctrl[p] != TK_JOIN_NONE && ctrl[p] >= c->host.num_special) return bad_ctrl(c, p, ctrl[p]);
+    return TK_OK;
+}
+
+// TK_CHECK_PARTS on the device: one small kernel and one wait, before any buffer of an earlier result is given up
+static int check_parts_device(tk_ctx* c, const uint32_t* d_ctrl, const uint64_t* d_conv, uint64_t P, uint64_t C, hipStream_t s) {
+    TK_HIP(c, c->jn_stat.reserve(64));
+    TkJoinArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_parts = P; a.n_convs = C; a.ctrl = d_ctrl; a.conv_offs = d_conv; a.num_special = c->host.num_special;
+    a.stat = (unsigned long long*)c->jn_stat.p;
+    unsigned long long bad[2] = {0, 0};
+    TK_HIP(c, hipMemsetAsync(a.stat + 1, 0xFF, 16, s));
+    TK_HIP(c, tk_launch_join_check(a, s));
+    TK_HIP(c, hipMemcpyAsync(bad, a.stat + 1, 16, hipMemcpyDeviceToHost, s));
+    TK_HIP(c, hipStreamSynchronize(s));
+    if (bad[0] != ~0ull) return bad_conv(c, bad[0], P);
+    if (bad[1] != ~0ull) {
+        uint32_t id = 0;
+        TK_HIP(c, hipMemcpy(&id, d_ctrl + bad[1], 4, hipMemcpyDeviceToHost));
+        return bad_ctrl(c, bad[1], id);
+    }
+    return TK_OK;
+}
+
+// The join over ids on the device into the context's jn_* buffers; *out gets the device pointers.  The outputs are sized for
+// n_ids + n_parts elements, so nothing is read before the launches; ONE wait at the end (N, n_ctrl, n_labelled).  Nothing of an
+// earlier result is touched before every argument has been accepted.  The caller holds c->mu.
+static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t P, uint64_t n_ids, const uint32_t* d_ctrl,
+                    const uint32_t* d_pflags, const uint64_t* d_conv, uint64_t C, bool check_parts, const tk_join_opts* o, hipStream_t s,
+                    tk_join* out) {
+    int rc = join_check_args(c, P, C, o);
+    if (rc != TK_OK) return rc;
+    if (P == 0 && n_ids) { c->err = "join: ids without a part"; return TK_ERR_INVALID_ARG; }
+    if (check_parts && (rc = check_parts_device(c, d_ctrl, d_conv, P, C, s)) != TK_OK) return rc;
+    const bool want_lab = (o->flags & TK_JOIN_LABELS) != 0, want_pi = (o->flags & TK_JOIN_PART_INDEX) != 0;
+    const uint64_t cap = n_ids + P;
+    TK_HIP(c, c->jn_stat.reserve(64));
+    TK_HIP(c, c->jn_ids.reserve(cap * 4 + 16));
+    TK_HIP(c, c->jn_offs.reserve((C + 1) * 8));
+    if (want_lab) TK_HIP(c, c->jn_labels.reserve(cap * 4 + 16));
+    if (want_pi) TK_HIP(c, c->jn_pidx.reserve(cap * 4 + 16));
+    unsigned long long got[3] = {0, 0, 0};      // N, n_ctrl, n_labelled
+    if (P == 0) {                               // (no part: offsets = [0] * (C + 1), nothing to launch)
+        TK_HIP(c, hipMemsetAsync(c->jn_offs.p, 0, (C + 1) * 8, s));
+    } else {
+        TK_HIP(c, c->jn_has.reserve(P * 4 + 16));
+        TK_HIP(c, c->jn_cb.reserve((P + 1) * 8));
+        TK_HIP(c, c->jn_start.reserve((P + 1) * 8));
+        if (want_pi) TK_HIP(c, c->jn_plocal.reserve(P * 4 + 16));
+        TK_HIP(c, c->jn_bsum.reserve((P / 2048 + 4) * 8));
+        TkJoinArgs a;
+        memset(&a, 0, sizeof(a));
+        a.ids = d_ids;
+        a.id_offs = d_id_offs;
+        a.n_parts = P;
+        a.n_convs = C;
+        a.ctrl = d_ctrl;
+        a.pflags = d_pflags;
+        a.conv_offs = d_conv;
+        a.cap = cap;
+        a.num_special = c->host.num_special;
+        a.ignore = o->ignore_index;
+        a.has = (uint32_t*)c->jn_has.p;
+        a.cb = (const uint64_t*)c->jn_cb.p;
+        a.start = (uint64_t*)c->jn_start.p;
+        a.plocal = (uint32_t*)c->jn_plocal.p;
+        a.out_ids = (uint32_t*)c->jn_ids.p;
+        a.out_offs = (uint64_t*)c->jn_offs.p;
+        a.labels = want_lab ? (int32_t*)c->jn_labels.p : nullptr;
+        a.part_index = want_pi ? (uint32_t*)c->jn_pidx.p : nullptr;
+        a.stat = (unsigned long long*)c->jn_stat.p;
+        TK_HIP(c, hipMemsetAsync(a.stat, 0, 8, s));
+        TK_HIP(c, tk_launch_join_has(a, s));
+        TK_HIP(c, tk_launch_scan(a.has, P, (uint64_t*)c->jn_cb.p, (uint64_t*)c->jn_bsum.p, s));
+        TK_HIP(c, tk_launch_join_parts(a, s));
+        TK_HIP(c, tk_launch_join(a, s));
+        TK_HIP(c, hipMemcpyAsync(got, a.start + P, 8, hipMemcpyDeviceToHost, s));
+        TK_HIP(c, hipMemcpyAsync(got + 1, a.cb + P, 8, hipMemcpyDeviceToHost, s));
+        TK_HIP(c, hipMemcpyAsync(got + 2, a.stat, 8, hipMemcpyDeviceToHost, s));
+    }
+    TK_HIP(c, hipStreamSynchronize(s));
+    if (got[0] > cap) {
+        c->err = "join: id_offsets end at " + std::to_string(got[0] - got[1]) + ", beyond n_ids = " + std::to_string(n_ids);
+        return TK_ERR_INVALID_ARG;
+    }
+    out->ids = (uint32_t*)c->jn_ids.p;
+    out->offsets = (uint64_t*)c->jn_offs.p;
+    out->labels = want_lab ? (int32_t*)c->jn_labels.p : nullptr;
+    out->part_index = want_pi ? (uint32_t*)c->jn_pidx.p : nullptr;
+    out->n_convs = C;
+    out->n_parts = P;
+    out->n_ids = got[0];
+    out->n_ctrl = got[1];
+    out->n_labelled = got[2];
+    return TK_OK;
+}
+
+extern "C" int tk_join_from_ids_device(tk_ctx* c, const void* d_ids, const void* d_id_offsets, uint64_t n_parts, uint64_t n_ids,
+                                       const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                                       int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out) {
+    TK_ENTRY(c);
+    if (checks & ~TK_CHECK_PARTS) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    if (!d_id_offsets || (!d_ids && n_ids) || (!d_part_ctrl && n_parts) || !d_conv_offsets || !opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    TK_HIP(c, hipSetDevice(c->device));
+    return run_join(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_parts, n_ids, (const uint32_t*)d_part_ctrl,
+                    (const uint32_t*)d_part_flags, (const uint64_t*)d_conv_offsets, n_convs, (checks & TK_CHECK_PARTS) != 0, opts,
+                    (hipStream_t)hip_stream, out);
+}
+
+extern "C" int tk_encode_parts_device_join(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
+                                           const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                                           int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out) {
+    TK_ENTRY(c);
+    if (checks & ~(TK_CHECK_OFFSETS | TK_CHECK_UTF8 | TK_CHECK_PARTS)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    if (!d_doc_offsets || (!d_bytes && n_bytes) || (!d_part_ctrl && n_parts) || !d_conv_offsets || !opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    int rc = join_check_args(c, n_parts, n_convs, opts);
+    if (rc != TK_OK) return rc;
+    TK_HIP(c, hipSetDevice(c->device));
+    // (the parts are checked before the text is encoded: a refused call costs one small kernel)
+    if ((checks & TK_CHECK_PARTS) && (rc = check_parts_device(c, (const uint32_t*)d_part_ctrl, (const uint64_t*)d_conv_offsets, n_parts, n_convs,
+                                                               (hipStream_t)hip_stream)) != TK_OK) return rc;
+    void *d_ids = nullptr, *d_oo = nullptr;
+    uint64_t n_ids = 0;
+    rc = encode_device_checked(c, d_bytes, d_doc_offsets, n_parts, n_bytes, 0, 0, checks & (TK_CHECK_OFFSETS | TK_CHECK_UTF8), hip_stream,
+                               &d_ids, &d_oo, &n_ids);
+    if (rc != TK_OK) return rc;
+    return run_join(c, (const uint32_t*)d_ids, (const uint64_t*)d_oo, n_parts, n_ids, (const uint32_t*)d_part_ctrl, (const uint32_t*)d_part_flags,
+                    (const uint64_t*)d_conv_offsets, n_convs, false, opts, (hipStream_t)hip_stream, out);
+}
+
+extern "C" void tk_free_join(tk_join* r) {
+    if (!r) return;
+    tk_pinned_put(r->ids);
+    tk_pinned_put(r->offsets);
+    tk_pinned_put(r->labels);
+    tk_pinned_put(r->part_index);
+    memset(r, 0, sizeof(*r));
+}
+
+extern "C" int tk_encode_parts_join(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_parts, const uint32_t* part_ctrl,
+                                    const uint32_t* part_flags, const uint64_t* conv_offsets, uint64_t n_convs, int validate_utf8,
+                                    const tk_join_opts* opts, tk_join* out) {
+    TK_ENTRY(c);
+    if (!opts || !out || !doc_offsets || !conv_offsets || (!part_ctrl && n_parts)) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    memset(out, 0, sizeof(*out));
+    int rc = join_check_args(c, n_parts, n_convs, opts);
+    if (rc != TK_OK) return rc;
+    if ((rc = check_parts_host(c, part_ctrl, conv_offsets, n_parts, n_convs)) != TK_OK) return rc;
+    tk_result res;
+    DevBatch dev;
+    rc = encode_batch(c, bytes, doc_offsets, n_parts, 0, 0, validate_utf8, &res, &dev);
+    if (rc != TK_OK) return rc;
+    const uint64_t n_ids = res.n_ids;
+    tk_free_result(&res);   // (the host copy of the ragged ids is not part of this entry's result)
+    TK_HIP(c, c->jn_in_ctrl.reserve(n_parts * 4 + 16));
+    TK_HIP(c, c->jn_in_flags.reserve(n_parts * 4 + 16));
+    TK_HIP(c, c->jn_in_conv.reserve((n_convs + 1) * 8));
+    if (n_parts) TK_HIP(c, hipMemcpyAsync(c->jn_in_ctrl.p, part_ctrl, n_parts * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_parts && part_flags) TK_HIP(c, hipMemcpyAsync(c->jn_in_flags.p, part_flags, n_parts * 4, hipMemcpyHostToDevice, c->stream));
+    TK_HIP(c, hipMemcpyAsync(c->jn_in_conv.p, conv_offsets, (n_convs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    // (the small path's ids and offsets are mapped pinned memory: the kernels read them there)
+    tk_join j;
+    rc = run_join(c, dev.ids, dev.id_offs, n_parts, n_ids, (const uint32_t*)c->jn_in_ctrl.p, part_flags ? (const uint32_t*)c->jn_in_flags.p : nullptr,
+                  (const uint64_t*)c->jn_in_conv.p, n_convs, false, opts, c->stream, &j);
+    if (rc != TK_OK) return rc;
+    // (an unselected output: no device source, an empty block that is given back at once)
+    CopyOut h[4] = {{j.n_ids ? j.ids : nullptr, (j.n_ids ? j.n_ids : 1) * 4, nullptr}, {j.offsets, (n_convs + 1) * 8, nullptr},
+                    {j.n_ids ? j.labels : nullptr, j.labels ? (j.n_ids ? j.n_ids : 1) * 4 : 0, nullptr},
+                    {j.n_ids ? j.part_index : nullptr, j.part_index ? (j.n_ids ? j.n_ids : 1) * 4 : 0, nullptr}};
+    if ((rc = copy_out(c, h, 4, "join")) != TK_OK) return rc;
+    *out = j;
+    out->ids = (uint32_t*)h[0].host;
+    out->offsets = (uint64_t*)h[1].host;
+    if (j.labels) out->labels = (int32_t*)h[2].host; else tk_pinned_put(h[2].host);
+    if (j.part_index) out->part_index = (uint32_t*)h[3].host; else tk_pinned_put(h[3].host);
+    return TK_OK;
+}

@@ -113,6 +113,10 @@ struct tk_ctx {
     // the packed training rows (tk_seqpack.hip): the three tensors, cu_seqlens and the two statistics words; the work arrays
     // (flags and their scans, the compacted starts, the scan workspace).  Apart from every other buffer, allocated at the first packed call
     DevBuf sp_ids, sp_pos, sp_seg, sp_cu, sp_stat, sp_flags, sp_aflags, sp_fpos, sp_apos, sp_starts, sp_aligned, sp_bsum;
+    // the chat batches (tk_join.hip): the joined ids, their per-conversation offsets, labels, part indices and the statistics
+    // words; the work arrays (has-a-control-id and its scan, the parts' output starts and local indices, the scan workspace); the
+    // host entry's copies of part_ctrl / part_flags / conv_offsets.  Apart from every other buffer, allocated at the first join call
+    DevBuf jn_ids, jn_offs, jn_labels, jn_pidx, jn_stat, jn_has, jn_cb, jn_start, jn_plocal, jn_bsum, jn_in_ctrl, jn_in_flags, jn_in_conv;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy

@@ -171,6 +171,32 @@ hipError_t tk_launch_seqpack_starts(const TkSeqpackArgs& a, hipStream_t s);   //
 hipError_t tk_launch_seqpack(const TkSeqpackArgs& a, int i64, hipStream_t s); // the tensors; n_rows == 0: nothing is launched
 hipError_t tk_launch_seqpack_cu(const TkSeqpackArgs& a, hipStream_t s);       // cu_seqlens (a.cu != NULL), n_segments, max_seqlen
 
+// ---- chat batches: parts joined with control ids, plus labels (tk_join.hip) ----
+struct TkJoinArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all parts, encoded without BOS / EOS
+    const uint64_t* id_offs;   // [n_parts + 1]
+    uint64_t n_parts, n_convs;
+    const uint32_t* ctrl;      // [n_parts] a control id or TK_JOIN_NONE
+    const uint32_t* pflags;    // [n_parts] TK_PART_LABEL_* or NULL (all zero)
+    const uint64_t* conv_offs; // [n_convs + 1]
+    uint64_t cap;              // elements the outputs hold (n_ids + n_parts): nothing is written at or beyond it
+    uint32_t num_special;      // (the check kernel)
+    int32_t ignore;            // ignore_index
+    uint32_t* has;             // [n_parts] the part has a control id
+    const uint64_t* cb;        // [n_parts + 1] exclusive scan of has: control ids before the part; [n_parts] = n_ctrl
+    uint64_t* start;           // [n_parts + 1] id_offs + cb: where the part starts in the output, non-decreasing; [n_parts] = N
+    uint32_t* plocal;          // [n_parts] the part's index inside its conversation (only with part_index)
+    uint32_t* out_ids;         // [N]
+    uint64_t* out_offs;        // [n_convs + 1]
+    int32_t* labels;           // [N] or NULL
+    uint32_t* part_index;      // [N] or NULL
+    unsigned long long* stat;  // [0] += n_labelled; [1], [2]: the first bad conversation / part (atomicMin: ~0 from the caller)
+};
+hipError_t tk_launch_join_check(const TkJoinArgs& a, hipStream_t s);   // TK_CHECK_PARTS: stat[1], stat[2]
+hipError_t tk_launch_join_has(const TkJoinArgs& a, hipStream_t s);     // has
+hipError_t tk_launch_join_parts(const TkJoinArgs& a, hipStream_t s);   // start, plocal, out_offs, n_labelled (behind the scan of has)
+hipError_t tk_launch_join(const TkJoinArgs& a, hipStream_t s);         // ids, labels, part_index; n_parts == 0: nothing is launched
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);

@@ -30,6 +30,7 @@
 
 #include "tk_dpp_scan.h"
 #include "tk_kernels.h"
+#include "tk_wave_search.h"
 
 #define TKS_BLOCK 256
 #define TKS_TILE 4096u     /* stream positions of a block's tile (16 a thread) */
@@ -53,25 +54,6 @@ __global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_starts_kernel(TkSeqpackA
         a.starts[i] = a.id_offs[d];
         a.n_aligned[i] = a.apos[d];
     }
-}
-
-// Entries of the strictly increasing a[0 .. n) that are <= key.  The whole wave calls it with the same arguments: every step the
-// 64 lanes probe the last entries of 64 equal parts of the range and a ballot keeps the one part the answer lies in.
-__device__ __forceinline__ uint64_t tks_wave_count_le(const uint64_t* a, uint64_t n, uint64_t key) {
-    const uint32_t lane = threadIdx.x & 63u;
-    uint64_t lo = 0, hi = n;                            // the answer is in [lo, hi]
-    while (hi > lo) {
-        const uint64_t step = (hi - lo + 63u) / 64u;
-        uint64_t p = lo + (lane + 1u) * step - 1u;
-        if (p >= hi) p = hi - 1u;
-        const uint32_t c = (uint32_t)__builtin_popcountll(__ballot(a[p] <= key));   // a prefix of the lanes
-        if (c == 64u) { lo = hi; break; }
-        uint64_t pc = lo + (c + 1u) * step - 1u;        // the first probe above key: the answer is at most its index
-        if (pc >= hi) pc = hi - 1u;
-        lo += c * step;
-        hi = pc;
-    }
-    return lo;
 }
 
 // entries of a[0 .. n) that are < key, one lane on its own (the cu_seqlens kernel: once a row)
