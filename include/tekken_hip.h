@@ -230,8 +230,7 @@ void tk_free_spans(uint32_t* spans);
  * The layout is a separate pass behind the unchanged encode pipeline (csrc/tk_dense.hip): every element is written once, pad
  * included, in 16-byte stores where L is a multiple of 4 (element stores otherwise: pad to a multiple of 4 for the fast form).
  * The longest-row mode reads max_d n_d back (8 bytes) before it can size the tensor; TK_DENSE_FIXED needs no read before the
- * launch.  TK_DENSE_NT=1 in the environment (read at a context's first dense call) makes the 16-byte stores non-temporal: the
- * A / B behind the default of plain stores (DESIGN 4.5c has the figures); it never changes a value. */
+ * launch. */
 #define TK_DENSE_PAD_LEFT 1
 #define TK_DENSE_TRUNC_LEFT 2
 #define TK_DENSE_FIXED 4

@@ -349,6 +349,32 @@ def _need(name):
     return fn
 
 
+def _take(ptr, n, dtype):
+    """A numpy copy of the n elements of dtype at the host address ptr."""
+    if n == 0:
+        return np.zeros(0, dtype)
+    raw = (ctypes.c_uint8 * (n * np.dtype(dtype).itemsize)).from_address(ptr)
+    return np.frombuffer(raw, dtype=dtype, count=n).copy()
+
+
+def _torch_wrap(view, shape, dtype, copy):
+    """A DeviceView as a torch tensor on the GPU (copy: a clone of it); an unselected output (None) stays None."""
+    import torch
+    if view is None:
+        return None
+    if 0 in shape:            # (nothing behind the pointer to look at)
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    t = torch.as_tensor(view, device="cuda")
+    return t.clone() if copy else t
+
+
+def _upload(data, offs):
+    """The packed text and its offsets go up once: (uint8 tensor, int64 tensor) on the GPU and the current stream."""
+    import torch
+    return (torch.from_numpy(data if len(data) else np.zeros(1, np.uint8)).cuda(), torch.from_numpy(offs.astype(np.int64)).cuda(),
+            torch.cuda.current_stream().cuda_stream)
+
+
 def _take_result(res):
     n, D = int(res.n_ids), int(res.n_docs)
     ids = np.ctypeslib.as_array(res.ids, shape=(max(n, 1),))[:n].copy()
@@ -461,6 +487,12 @@ class Engine:
 
     def _err(self, rc):
         return TokenizerError(rc, lib().tk_last_error(self._h).decode())
+
+    def _call(self, name, *args):
+        """The C entry `name` on this context; anything but TK_OK raises with tk_last_error."""
+        rc = _need(name)(self._h, *args)
+        if rc != TK_OK:
+            raise self._err(rc)
 
     def encode_batch(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False):
         """Host buffers in, host buffers out: (ids uint32[T], out_offsets uint64[D+1])."""
@@ -622,10 +654,8 @@ class Engine:
         truncated count); the definition is in include/tekken_hip.h.  Returns a DenseResult (context-owned device buffers,
         apart from the encode and spans outputs)."""
         o, d = _dense_opts(max_length, multiple_of, pad_id, keep_head, keep_tail, flags), _Dense()
-        rc = _need("tk_dense_from_ids_device")(self._h, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
-                                               ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(d))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_dense_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                   ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(d))
         return DenseResult(d, int(flags))
 
     def encode_batch_device_dense(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, max_length=0, multiple_of=0,
@@ -634,11 +664,9 @@ class Engine:
         Returns (d_ids_ptr, d_out_offs_ptr, n_ids, DenseResult), all context-owned."""
         o, d = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags), _Dense()
         d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
-        rc = _need("tk_encode_batch_device_dense")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
-                                                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
-                                                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(d))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_encode_batch_device_dense", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(d))
         return d_ids.value, d_oo.value, int(n.value), DenseResult(d, int(flags))
 
     def encode_batch_dense(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, max_length=0, multiple_of=0, pad_id=0,
@@ -649,22 +677,14 @@ class Engine:
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         o, d = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags), _Dense()
         dbuf = data if len(data) else np.zeros(1, np.uint8)
-        rc = _need("tk_encode_batch_dense")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
-                                            int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(d))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_encode_batch_dense", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(d))
         D, L = int(d.n_docs), int(d.row_len)
         dt = np.int64 if flags & DENSE_I64 else np.int32
 
-        def take(ptr, n, dtype):
-            if n == 0:
-                return np.zeros(0, dtype)
-            raw = (ctypes.c_uint8 * (n * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(raw, dtype=dtype, count=n).copy()
-
-        dense = take(d.ids, D * L, dt).reshape(D, L)
-        mask = take(d.mask, D * L, np.uint8).reshape(D, L) if d.mask else None
-        lengths = take(d.lengths, D, np.uint32)
+        dense = _take(d.ids, D * L, dt).reshape(D, L)
+        mask = _take(d.mask, D * L, np.uint8).reshape(D, L) if d.mask else None
+        lengths = _take(d.lengths, D, np.uint32)
         self.last_n_truncated = int(d.n_truncated)
         lib().tk_free_dense(ctypes.byref(d))
         return dense, mask, lengths
@@ -674,10 +694,8 @@ class Engine:
         segment_ids, cu_seqlens as flags select); the definition is in include/tekken_hip.h.  Returns a SeqpackResult
         (context-owned device buffers, apart from the encode, spans and dense outputs)."""
         o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
-        rc = _need("tk_seqpack_from_ids_device")(self._h, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
-                                                 ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(p))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_seqpack_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                   ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(p))
         return SeqpackResult(p, int(flags))
 
     def encode_batch_device_seqpack(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, seq_len, add_bos=True, add_eos=True, pad_id=0, flags=0,
@@ -686,11 +704,9 @@ class Engine:
         Returns (d_ids_ptr, d_out_offs_ptr, n_ids, SeqpackResult), all context-owned."""
         o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
         d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
-        rc = _need("tk_encode_batch_device_seqpack")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
-                                                     int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
-                                                     ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(p))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_encode_batch_device_seqpack", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(p))
         return d_ids.value, d_oo.value, int(n.value), SeqpackResult(p, int(flags))
 
     def encode_batch_seqpack(self, data, offs, seq_len, add_bos=True, add_eos=True, validate_utf8=False, pad_id=0, flags=0):
@@ -701,23 +717,15 @@ class Engine:
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
         dbuf = data if len(data) else np.zeros(1, np.uint8)
-        rc = _need("tk_encode_batch_seqpack")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
-                                              int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(p))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_encode_batch_seqpack", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(p))
         R, L = int(p.n_rows), int(p.row_len)
         dt = np.int64 if flags & SEQPACK_I64 else np.int32
 
-        def take(ptr, n, dtype):
-            if n == 0:
-                return np.zeros(0, dtype)
-            raw = (ctypes.c_uint8 * (n * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(raw, dtype=dtype, count=n).copy()
-
-        out = {"input_ids": take(p.input_ids, R * L, dt).reshape(R, L),
-               "position_ids": take(p.position_ids, R * L, dt).reshape(R, L) if p.position_ids else None,
-               "segment_ids": take(p.segment_ids, R * L, dt).reshape(R, L) if p.segment_ids else None,
-               "cu_seqlens": take(p.cu_seqlens, int(p.n_segments) + 1, np.int32) if p.cu_seqlens else None,
+        out = {"input_ids": _take(p.input_ids, R * L, dt).reshape(R, L),
+               "position_ids": _take(p.position_ids, R * L, dt).reshape(R, L) if p.position_ids else None,
+               "segment_ids": _take(p.segment_ids, R * L, dt).reshape(R, L) if p.segment_ids else None,
+               "cu_seqlens": _take(p.cu_seqlens, int(p.n_segments) + 1, np.int32) if p.cu_seqlens else None,
                "max_seqlen": int(p.max_seqlen), "n_rows": R, "n_used": int(p.n_used), "n_left": int(p.n_left),
                "n_segments": int(p.n_segments)}
         lib().tk_free_seqpack(ctypes.byref(p))
@@ -730,12 +738,10 @@ class Engine:
         include/tekken_hip.h.  checks: 0 | CHECK_PARTS.  Returns a JoinResult (context-owned device buffers, apart from every
         other output)."""
         o, j = _JoinOpts(int(ignore_index), int(flags)), _Join()
-        rc = _need("tk_join_from_ids_device")(self._h, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr or None), n_parts, n_ids,
-                                              ctypes.c_void_p(d_part_ctrl_ptr or None), ctypes.c_void_p(d_part_flags_ptr or None),
-                                              ctypes.c_void_p(d_conv_offs_ptr or None), n_convs, int(checks), ctypes.byref(o),
-                                              ctypes.c_void_p(stream), ctypes.byref(j))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_join_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr or None), n_parts, n_ids,
+                   ctypes.c_void_p(d_part_ctrl_ptr or None), ctypes.c_void_p(d_part_flags_ptr or None),
+                   ctypes.c_void_p(d_conv_offs_ptr or None), n_convs, int(checks), ctypes.byref(o),
+                   ctypes.c_void_p(stream), ctypes.byref(j))
         return JoinResult(j)
 
     def encode_parts_device_join(self, d_bytes_ptr, d_offs_ptr, n_parts, n_bytes, d_part_ctrl_ptr, d_part_flags_ptr, d_conv_offs_ptr, n_convs,
@@ -743,12 +749,10 @@ class Engine:
         """tk_encode_parts_device_join: the part texts encoded one by one without BOS / EOS + the join on the same stream.
         checks may mix CHECK_OFFSETS / CHECK_UTF8 with CHECK_PARTS.  Returns a JoinResult."""
         o, j = _JoinOpts(int(ignore_index), int(flags)), _Join()
-        rc = _need("tk_encode_parts_device_join")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_parts, n_bytes,
-                                                  ctypes.c_void_p(d_part_ctrl_ptr or None), ctypes.c_void_p(d_part_flags_ptr or None),
-                                                  ctypes.c_void_p(d_conv_offs_ptr or None), n_convs, int(checks), ctypes.byref(o),
-                                                  ctypes.c_void_p(stream), ctypes.byref(j))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_encode_parts_device_join", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_parts, n_bytes,
+                   ctypes.c_void_p(d_part_ctrl_ptr or None), ctypes.c_void_p(d_part_flags_ptr or None),
+                   ctypes.c_void_p(d_conv_offs_ptr or None), n_convs, int(checks), ctypes.byref(o),
+                   ctypes.c_void_p(stream), ctypes.byref(j))
         return JoinResult(j)
 
     def encode_parts_join(self, data, offs, part_ctrl, part_flags, conv_offs, ignore_index=-100, flags=0, validate_utf8=False):
@@ -767,22 +771,14 @@ class Engine:
         dbuf = data if len(data) else np.zeros(1, np.uint8)
         cbuf = ctrl if n_parts else np.zeros(1, np.uint32)
         fbuf = None if pf is None else pf if n_parts else np.zeros(1, np.uint32)
-        rc = _need("tk_encode_parts_join")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), n_parts, _p(cbuf, ctypes.c_uint32),
-                                           None if fbuf is None else _p(fbuf, ctypes.c_uint32), _p(conv, ctypes.c_uint64), len(conv) - 1,
-                                           int(validate_utf8), ctypes.byref(o), ctypes.byref(j))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_encode_parts_join", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), n_parts, _p(cbuf, ctypes.c_uint32),
+                   None if fbuf is None else _p(fbuf, ctypes.c_uint32), _p(conv, ctypes.c_uint64), len(conv) - 1,
+                   int(validate_utf8), ctypes.byref(o), ctypes.byref(j))
         N, C = int(j.n_ids), int(j.n_convs)
 
-        def take(ptr, n, dtype):
-            if n == 0:
-                return np.zeros(0, dtype)
-            raw = (ctypes.c_uint8 * (n * np.dtype(dtype).itemsize)).from_address(ptr)
-            return np.frombuffer(raw, dtype=dtype, count=n).copy()
-
-        out = {"ids": take(j.ids, N, np.uint32), "offsets": take(j.offsets, C + 1, np.uint64),
-               "labels": take(j.labels, N, np.int32) if j.labels else None,
-               "part_index": take(j.part_index, N, np.uint32) if j.part_index else None,
+        out = {"ids": _take(j.ids, N, np.uint32), "offsets": _take(j.offsets, C + 1, np.uint64),
+               "labels": _take(j.labels, N, np.int32) if j.labels else None,
+               "part_index": _take(j.part_index, N, np.uint32) if j.part_index else None,
                "n_ids": N, "n_ctrl": int(j.n_ctrl), "n_labelled": int(j.n_labelled)}
         lib().tk_free_join(ctypes.byref(j))
         return out
@@ -792,11 +788,9 @@ class Engine:
         d_id_offs_ptr, n_ids), context-owned and valid through a following decode_batch_device.  d_lengths_ptr (uint32[n_docs]) 0:
         the run of pad_id at the padded end of every row is trimmed."""
         d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
-        rc = _need("tk_ragged_from_dense_device")(self._h, ctypes.c_void_p(d_dense_ptr or None), n_docs, row_len, int(flags),
-                                                  ctypes.c_void_p(d_lengths_ptr or None), int(pad_id), ctypes.c_void_p(stream),
-                                                  ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n))
-        if rc != TK_OK:
-            raise self._err(rc)
+        self._call("tk_ragged_from_dense_device", ctypes.c_void_p(d_dense_ptr or None), n_docs, row_len, int(flags),
+                   ctypes.c_void_p(d_lengths_ptr or None), int(pad_id), ctypes.c_void_p(stream),
+                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n))
         return d_ids.value, d_oo.value, int(n.value)
 
     def encode_batch_device_views(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, stream=0):
@@ -1117,23 +1111,15 @@ class Tekkenizer:
             dense, mask, lengths = eng.encode_batch_dense(data, offs, add_bos, add_eos, False, max_length, pad_to_multiple_of, pad, flags)
             return {"input_ids": dense, "attention_mask": mask, "lengths": lengths.astype(np.int32), "n_truncated": eng.last_n_truncated}
         import torch
-        d_bytes = torch.from_numpy(data if len(data) else np.zeros(1, np.uint8)).cuda()
-        d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
-        stream = torch.cuda.current_stream().cuda_stream
+        d_bytes, d_offs, stream = _upload(data, offs)
         _, _, _, res = eng.encode_batch_device_dense(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos, add_eos,
                                                      max_length, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
         D, L = res.n_docs, res.row_len
         tdt = torch.int64 if dtype == "int64" else torch.int32
         v_ids, v_mask, v_len = res.views()
-
-        def wrap(view, shape, tdtype):
-            if 0 in shape:            # (nothing behind the pointer to look at)
-                return torch.empty(shape, dtype=tdtype, device="cuda")
-            t = torch.as_tensor(view, device="cuda")
-            return t.clone() if copy else t
-
-        return {"input_ids": wrap(v_ids, (D, L), tdt), "attention_mask": wrap(v_mask, (D, L), torch.uint8) if return_mask else None,
-                "lengths": wrap(v_len, (D,), torch.int32), "n_truncated": res.n_truncated}
+        return {"input_ids": _torch_wrap(v_ids, (D, L), tdt, copy),
+                "attention_mask": _torch_wrap(v_mask, (D, L), torch.uint8, copy) if return_mask else None,
+                "lengths": _torch_wrap(v_len, (D,), torch.int32, copy), "n_truncated": res.n_truncated}
 
     def encode_batch_packed(self, docs, seq_len, add_bos=True, add_eos=True, drop_last=False, pad_id=None, dtype="int64",
                             return_position_ids=True, return_segment_ids=True, return_cu_seqlens=True, return_tensors="pt", copy=True):
@@ -1162,25 +1148,15 @@ class Tekkenizer:
         if return_tensors == "np":
             return eng.encode_batch_seqpack(data, offs, seq_len, add_bos, add_eos, False, pad, flags)
         import torch
-        d_bytes = torch.from_numpy(data if len(data) else np.zeros(1, np.uint8)).cuda()
-        d_offs = torch.from_numpy(offs.astype(np.int64)).cuda()
-        stream = torch.cuda.current_stream().cuda_stream
+        d_bytes, d_offs, stream = _upload(data, offs)
         _, _, _, res = eng.encode_batch_device_seqpack(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), seq_len, add_bos, add_eos,
                                                        pad, flags, CHECK_OFFSETS, stream)
         tdt = torch.int64 if dtype == "int64" else torch.int32
-
-        def wrap(view, shape, tdtype):
-            if view is None:
-                return None
-            if 0 in shape:            # (nothing behind the pointer to look at)
-                return torch.empty(shape, dtype=tdtype, device="cuda")
-            t = torch.as_tensor(view, device="cuda")
-            return t.clone() if copy else t
-
         v_ids, v_pos, v_seg, v_cu = res.views()
         shape = (res.n_rows, res.row_len)
-        return {"input_ids": wrap(v_ids, shape, tdt), "position_ids": wrap(v_pos, shape, tdt), "segment_ids": wrap(v_seg, shape, tdt),
-                "cu_seqlens": wrap(v_cu, (res.n_segments + 1,), torch.int32), "max_seqlen": res.max_seqlen, "n_rows": res.n_rows,
+        return {"input_ids": _torch_wrap(v_ids, shape, tdt, copy), "position_ids": _torch_wrap(v_pos, shape, tdt, copy),
+                "segment_ids": _torch_wrap(v_seg, shape, tdt, copy),
+                "cu_seqlens": _torch_wrap(v_cu, (res.n_segments + 1,), torch.int32, copy), "max_seqlen": res.max_seqlen, "n_rows": res.n_rows,
                 "n_used": res.n_used, "n_left": res.n_left, "n_segments": res.n_segments}
 
     CHAT_ROLES = {"user": ("[INST]", "[/INST]", False), "system": ("[SYSTEM_PROMPT]", "[/SYSTEM_PROMPT]", False),
@@ -1210,12 +1186,11 @@ class Tekkenizer:
         """The parts (from _parts_of) go up once; -> (JoinResult, stream).  The result's buffers are the context's."""
         import torch
         data, offs, ctrl, pf, conv = parts
-        up = [torch.from_numpy(x).cuda() for x in (data if len(data) else np.zeros(1, np.uint8), offs.astype(np.int64),
-                                                    (ctrl if len(ctrl) else np.zeros(1, np.uint32)).view(np.int32),
+        d_bytes, d_offs, stream = _upload(data, offs)
+        up = [torch.from_numpy(x).cuda() for x in ((ctrl if len(ctrl) else np.zeros(1, np.uint32)).view(np.int32),
                                                     (pf if len(pf) else np.zeros(1, np.uint32)).view(np.int32), conv.astype(np.int64))]
-        stream = torch.cuda.current_stream().cuda_stream
-        res = eng.encode_parts_device_join(up[0].data_ptr(), up[1].data_ptr(), len(ctrl), len(data), up[2].data_ptr(), up[3].data_ptr(),
-                                           up[4].data_ptr(), len(conv) - 1, ignore_index, flags, CHECK_OFFSETS | CHECK_PARTS, stream)
+        res = eng.encode_parts_device_join(d_bytes.data_ptr(), d_offs.data_ptr(), len(ctrl), len(data), up[0].data_ptr(), up[1].data_ptr(),
+                                           up[2].data_ptr(), len(conv) - 1, ignore_index, flags, CHECK_OFFSETS | CHECK_PARTS, stream)
         return res, stream
 
     def encode_conversations(self, convs, return_labels=True, return_part_index=False, ignore_index=-100, return_tensors="pt", copy=True):
@@ -1238,18 +1213,10 @@ class Tekkenizer:
                     "n_labelled": r["n_labelled"]}
         import torch
         res, _ = self._join_device(eng, parts, ignore_index, flags)
-
-        def wrap(view, n, tdtype):
-            if view is None:
-                return None
-            if n == 0:                # (nothing behind the pointer to look at)
-                return torch.empty((0,), dtype=tdtype, device="cuda")
-            t = torch.as_tensor(view, device="cuda")
-            return t.clone() if copy else t
-
         v_ids, v_offs, v_lab, v_pi = res.views()
-        return {"input_ids": wrap(v_ids, res.n_ids, torch.int32), "offsets": wrap(v_offs, res.n_convs + 1, torch.int64),
-                "labels": wrap(v_lab, res.n_ids, torch.int32), "part_index": wrap(v_pi, res.n_ids, torch.int32),
+        N = (res.n_ids,)
+        return {"input_ids": _torch_wrap(v_ids, N, torch.int32, copy), "offsets": _torch_wrap(v_offs, (res.n_convs + 1,), torch.int64, copy),
+                "labels": _torch_wrap(v_lab, N, torch.int32, copy), "part_index": _torch_wrap(v_pi, N, torch.int32, copy),
                 "n_labelled": res.n_labelled}
 
     def _chat_parts(self, conversations, roles, add_bos):
@@ -1303,8 +1270,8 @@ class Tekkenizer:
                                           fl, stream)
             shape = (d.n_docs, d.row_len)
             v_ids, v_mask, v_len = d.views()
-            take = lambda v, sh, dt: torch.empty(sh, dtype=dt, device="cuda") if 0 in sh else torch.as_tensor(v, device="cuda").clone()
-            return d, take(v_ids, shape, tdtype), take(v_mask, shape, torch.uint8) if want_mask else None, take(v_len, (d.n_docs,), torch.int32)
+            return (d, _torch_wrap(v_ids, shape, tdtype, True), _torch_wrap(v_mask, shape, torch.uint8, True) if want_mask else None,
+                    _torch_wrap(v_len, (d.n_docs,), torch.int32, True))
 
         i64 = dtype == "int64"
         d, ids, mask, lengths = dense(res.ids_ptr, pad, flags | (DENSE_I64 if i64 else 0) | (DENSE_MASK if return_mask else 0),

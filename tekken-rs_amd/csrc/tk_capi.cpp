@@ -97,7 +97,8 @@ static int copy_out_fail(tk_ctx* c, CopyOut* a, int n, const std::string& err) {
 }
 int pinned_blocks(tk_ctx* c, CopyOut* a, int n) {
     bool ok = true;
-    for (int i = 0; i < n; ++i) ok = (a[i].host = tk_pinned_get(a[i].bytes)) != nullptr && ok;
+    for (int i = 0; i < n; ++i)
+        if (a[i].selected) ok = (a[i].host = tk_pinned_get(a[i].bytes)) != nullptr && ok;
     return ok ? TK_OK : copy_out_fail(c, a, n, "hipHostMalloc failed");
 }
 int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what) {
@@ -105,9 +106,29 @@ int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what) {
     if (rc != TK_OK) return rc;
     hipError_t e = hipSuccess;
     for (int i = 0; i < n && e == hipSuccess; ++i)
-        if (a[i].dev && a[i].bytes) e = hipMemcpyAsync(a[i].host, a[i].dev, a[i].bytes, hipMemcpyDeviceToHost, c->stream);
+        if (a[i].selected && a[i].dev && a[i].bytes) e = hipMemcpyAsync(a[i].host, a[i].dev, a[i].bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     return e == hipSuccess ? TK_OK : copy_out_fail(c, a, n, std::string(what) + " copy failed: " + hipGetErrorString(e));
+}
+
+int check_flags_and_args(tk_ctx* c, int checks, int known, bool null_arg) {
+    if (checks & ~known) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
+    if (null_arg) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    return TK_OK;
+}
+int scan_u32(tk_ctx* c, DevBuf& workspace, const uint32_t* counts, uint64_t n, uint64_t* offs, hipStream_t s) {
+    TK_HIP(c, workspace.reserve(scan_workspace_bytes(n)));
+    TK_HIP(c, tk_launch_scan(counts, n, offs, (uint64_t*)workspace.p, s));
+    return TK_OK;
+}
+int encode_batch_for_layout(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                            int validate_utf8, DevBatch* dev, uint64_t* n_ids) {
+    tk_result res;
+    int rc = encode_batch(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &res, dev);
+    if (rc != TK_OK) return rc;
+    *n_ids = res.n_ids;
+    tk_free_result(&res);
+    return TK_OK;
 }
 
 // The environment knobs of a context, read once at its creation (the per-call ones: call_knobs, tk_pipeline.cpp)

@@ -3,8 +3,6 @@
 #include "tk_ctx.h"
 
 #define TK_DENSE_ALL_FLAGS (TK_DENSE_PAD_LEFT | TK_DENSE_TRUNC_LEFT | TK_DENSE_FIXED | TK_DENSE_I64 | TK_DENSE_MASK)
-#define TK_DENSE_MAX_ROW 0x7FFFFFFFull          /* row_len stays below 2^31 */
-#define TK_DENSE_MAX_ELEMS (1ull << 36)         /* n_docs * row_len: 256 GiB of int32, more than the part holds */
 
 // the options that can be refused before anything is enqueued (step 5 of the definition)
 static int dense_check_opts(tk_ctx* c, const tk_dense_opts* o) {
@@ -59,15 +57,11 @@ static int run_dense(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
         L = o->max_length && longest > o->max_length ? o->max_length : longest;
     }
     if (o->multiple_of) L = (L + o->multiple_of - 1) / o->multiple_of * o->multiple_of;
-    if (L > TK_DENSE_MAX_ROW || (n_docs && L > TK_DENSE_MAX_ELEMS / n_docs)) return dense_too_large(c, n_docs, L);
+    if (L > TK_LAYOUT_MAX_ROW || (n_docs && L > TK_LAYOUT_MAX_ELEMS / n_docs)) return dense_too_large(c, n_docs, L);
     const uint64_t elems = n_docs * L;
     TK_HIP(c, c->dn_ids.reserve(elems * (i64 ? 8 : 4) + 16));
     if (mask) TK_HIP(c, c->dn_mask.reserve(elems + 16));
     TK_HIP(c, c->dn_len.reserve(n_docs * 4 + 16));
-    if (c->dense_nt < 0) {                  // (read at the first dense call of the context)
-        const char* e = getenv("TK_DENSE_NT");
-        c->dense_nt = e && *e == '1' ? 1 : 0;
-    }
     TkDenseArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = d_ids;
@@ -86,7 +80,7 @@ static int run_dense(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
     a.stat = d_stat;
     unsigned long long n_trunc = 0;
     if (L == 0 && n_docs) TK_HIP(c, hipMemsetAsync(c->dn_len.p, 0, n_docs * 4, s));   // (no document has an id: nothing to launch)
-    TK_HIP(c, tk_launch_dense(a, i64, c->dense_nt, s));
+    TK_HIP(c, tk_launch_dense(a, i64, s));
     TK_HIP(c, hipMemcpyAsync(&n_trunc, d_stat + 1, 8, hipMemcpyDeviceToHost, s));
     TK_HIP(c, hipStreamSynchronize(s));
     out->ids = c->dn_ids.p;
@@ -110,11 +104,10 @@ extern "C" int tk_encode_batch_device_dense(tk_ctx* c, const void* d_bytes, cons
                                             uint64_t n_bytes, int add_bos, int add_eos, int checks, const tk_dense_opts* opts,
                                             void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_dense* out) {
     TK_ENTRY(c);
-    if (checks & ~(TK_CHECK_OFFSETS | TK_CHECK_UTF8)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
-    if (!opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    tk_dense_opts o;
-    int rc = dense_encode_opts(c, opts, add_bos, add_eos, &o);
+    int rc = check_flags_and_args(c, checks, TK_CHECK_OFFSETS | TK_CHECK_UTF8, !opts || !out);
     if (rc != TK_OK) return rc;
+    tk_dense_opts o;
+    if ((rc = dense_encode_opts(c, opts, add_bos, add_eos, &o)) != TK_OK) return rc;
     rc = encode_device_checked(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, hip_stream, d_ids, d_out_offsets, n_ids);
     if (rc != TK_OK) return rc;
     return run_dense(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, &o, (hipStream_t)hip_stream, out);
@@ -136,24 +129,19 @@ extern "C" int tk_encode_batch_dense(tk_ctx* c, const uint8_t* bytes, const uint
     tk_dense_opts o;
     int rc = dense_encode_opts(c, opts, add_bos, add_eos, &o);
     if (rc != TK_OK) return rc;
-    tk_result res;
     DevBatch dev;
-    rc = encode_batch(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &res, &dev);
-    if (rc != TK_OK) return rc;
-    tk_free_result(&res);   // (the host copy of the ragged ids is not part of this entry's result)
-    // (the small path's ids and offsets are mapped pinned memory: the dense kernel reads them there)
+    uint64_t n_ids;
+    if ((rc = encode_batch_for_layout(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &dev, &n_ids)) != TK_OK) return rc;
     tk_dense d;
     rc = run_dense(c, dev.ids, dev.id_offs, n_docs, &o, c->stream, &d);
     if (rc != TK_OK) return rc;
     const uint64_t elems = d.n_docs * d.row_len, esz = (o.flags & TK_DENSE_I64) ? 8 : 4;
-    CopyOut h[3] = {{d.ids, elems * esz, nullptr}, {d.mask, elems, nullptr}, {d.lengths, n_docs * 4, nullptr}};
-    const int n = d.mask ? 3 : 2;
-    if (!d.mask) h[1] = h[2];                   // (no mask: the tensor and the lengths alone)
-    if ((rc = copy_out(c, h, n, "dense")) != TK_OK) return rc;
+    CopyOut h[3] = {{d.ids, elems * esz, nullptr}, {d.mask, elems, nullptr, d.mask != nullptr}, {d.lengths, n_docs * 4, nullptr}};
+    if ((rc = copy_out(c, h, 3, "dense")) != TK_OK) return rc;
     *out = d;
     out->ids = h[0].host;
-    out->mask = d.mask ? (uint8_t*)h[1].host : nullptr;
-    out->lengths = (uint32_t*)h[n - 1].host;
+    out->mask = (uint8_t*)h[1].host;
+    out->lengths = (uint32_t*)h[2].host;
     return TK_OK;
 }
 
@@ -163,7 +151,7 @@ extern "C" int tk_ragged_from_dense_device(tk_ctx* c, const void* d_dense, uint6
     TK_ENTRY(c);
     if (flags & ~(TK_DENSE_I64 | TK_DENSE_PAD_LEFT)) { c->err = "unknown dense flag"; return TK_ERR_INVALID_ARG; }
     if ((!d_dense && n_docs && row_len) || !d_ids || !d_id_offsets || !n_ids) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    if (n_docs >= 0xFFFFFFF0ull || row_len > TK_DENSE_MAX_ROW || (n_docs && row_len > TK_DENSE_MAX_ELEMS / n_docs)) return dense_too_large(c, n_docs, row_len);
+    if (n_docs >= 0xFFFFFFF0ull || row_len > TK_LAYOUT_MAX_ROW || (n_docs && row_len > TK_LAYOUT_MAX_ELEMS / n_docs)) return dense_too_large(c, n_docs, row_len);
     TK_HIP(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
     const int i64 = (flags & TK_DENSE_I64) != 0;
@@ -171,7 +159,7 @@ extern "C" int tk_ragged_from_dense_device(tk_ctx* c, const void* d_dense, uint6
     TK_HIP(c, c->dn_rids.reserve(n_docs * row_len * 4 + 16));
     TK_HIP(c, c->dn_roffs.reserve((n_docs + 1) * 8));
     TK_HIP(c, c->dn_rlens.reserve(n_docs * 4 + 16));
-    TK_HIP(c, c->block_sums.reserve((n_docs / 2048 + 4) * 8));
+    TK_HIP(c, c->block_sums.reserve(scan_workspace_bytes(n_docs)));
     TkRaggedArgs a;
     memset(&a, 0, sizeof(a));
     a.dense = d_dense;
@@ -189,7 +177,8 @@ extern "C" int tk_ragged_from_dense_device(tk_ctx* c, const void* d_dense, uint6
     } else {
         if (row_len == 0) TK_HIP(c, hipMemsetAsync(c->dn_rlens.p, 0, n_docs * 4, s));
         else TK_HIP(c, tk_launch_ragged_rowlen(a, i64, s));
-        TK_HIP(c, tk_launch_scan(a.lens, n_docs, (uint64_t*)c->dn_roffs.p, (uint64_t*)c->block_sums.p, s));
+        int rc = scan_u32(c, c->block_sums, a.lens, n_docs, (uint64_t*)c->dn_roffs.p, s);
+        if (rc != TK_OK) return rc;
         TK_HIP(c, tk_launch_ragged_copy(a, i64, s));
         TK_HIP(c, hipMemcpyAsync(&total, (const uint64_t*)c->dn_roffs.p + n_docs, 8, hipMemcpyDeviceToHost, s));
     }

@@ -82,7 +82,7 @@ static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs,
         TK_HIP(c, c->jn_cb.reserve((P + 1) * 8));
         TK_HIP(c, c->jn_start.reserve((P + 1) * 8));
         if (want_pi) TK_HIP(c, c->jn_plocal.reserve(P * 4 + 16));
-        TK_HIP(c, c->jn_bsum.reserve((P / 2048 + 4) * 8));
+        TK_HIP(c, c->jn_bsum.reserve(scan_workspace_bytes(P)));
         TkJoinArgs a;
         memset(&a, 0, sizeof(a));
         a.ids = d_ids;
@@ -106,7 +106,7 @@ static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs,
         a.stat = (unsigned long long*)c->jn_stat.p;
         TK_HIP(c, hipMemsetAsync(a.stat, 0, 8, s));
         TK_HIP(c, tk_launch_join_has(a, s));
-        TK_HIP(c, tk_launch_scan(a.has, P, (uint64_t*)c->jn_cb.p, (uint64_t*)c->jn_bsum.p, s));
+        if ((rc = scan_u32(c, c->jn_bsum, a.has, P, (uint64_t*)c->jn_cb.p, s)) != TK_OK) return rc;
         TK_HIP(c, tk_launch_join_parts(a, s));
         TK_HIP(c, tk_launch_join(a, s));
         TK_HIP(c, hipMemcpyAsync(got, a.start + P, 8, hipMemcpyDeviceToHost, s));
@@ -134,8 +134,8 @@ extern "C" int tk_join_from_ids_device(tk_ctx* c, const void* d_ids, const void*
                                        const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
                                        int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out) {
     TK_ENTRY(c);
-    if (checks & ~TK_CHECK_PARTS) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
-    if (!d_id_offsets || (!d_ids && n_ids) || (!d_part_ctrl && n_parts) || !d_conv_offsets || !opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    int rc = check_flags_and_args(c, checks, TK_CHECK_PARTS, !d_id_offsets || (!d_ids && n_ids) || (!d_part_ctrl && n_parts) || !d_conv_offsets || !opts || !out);
+    if (rc != TK_OK) return rc;
     TK_HIP(c, hipSetDevice(c->device));
     return run_join(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_parts, n_ids, (const uint32_t*)d_part_ctrl,
                     (const uint32_t*)d_part_flags, (const uint64_t*)d_conv_offsets, n_convs, (checks & TK_CHECK_PARTS) != 0, opts,
@@ -146,10 +146,9 @@ extern "C" int tk_encode_parts_device_join(tk_ctx* c, const void* d_bytes, const
                                            const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
                                            int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out) {
     TK_ENTRY(c);
-    if (checks & ~(TK_CHECK_OFFSETS | TK_CHECK_UTF8 | TK_CHECK_PARTS)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
-    if (!d_doc_offsets || (!d_bytes && n_bytes) || (!d_part_ctrl && n_parts) || !d_conv_offsets || !opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    int rc = join_check_args(c, n_parts, n_convs, opts);
-    if (rc != TK_OK) return rc;
+    int rc = check_flags_and_args(c, checks, TK_CHECK_OFFSETS | TK_CHECK_UTF8 | TK_CHECK_PARTS,
+                                  !d_doc_offsets || (!d_bytes && n_bytes) || (!d_part_ctrl && n_parts) || !d_conv_offsets || !opts || !out);
+    if (rc != TK_OK || (rc = join_check_args(c, n_parts, n_convs, opts)) != TK_OK) return rc;
     TK_HIP(c, hipSetDevice(c->device));
     // (the parts are checked before the text is encoded: a refused call costs one small kernel)
     if ((checks & TK_CHECK_PARTS) && (rc = check_parts_device(c, (const uint32_t*)d_part_ctrl, (const uint64_t*)d_conv_offsets, n_parts, n_convs,
@@ -181,32 +180,28 @@ extern "C" int tk_encode_parts_join(tk_ctx* c, const uint8_t* bytes, const uint6
     int rc = join_check_args(c, n_parts, n_convs, opts);
     if (rc != TK_OK) return rc;
     if ((rc = check_parts_host(c, part_ctrl, conv_offsets, n_parts, n_convs)) != TK_OK) return rc;
-    tk_result res;
     DevBatch dev;
-    rc = encode_batch(c, bytes, doc_offsets, n_parts, 0, 0, validate_utf8, &res, &dev);
-    if (rc != TK_OK) return rc;
-    const uint64_t n_ids = res.n_ids;
-    tk_free_result(&res);   // (the host copy of the ragged ids is not part of this entry's result)
+    uint64_t n_ids;
+    if ((rc = encode_batch_for_layout(c, bytes, doc_offsets, n_parts, 0, 0, validate_utf8, &dev, &n_ids)) != TK_OK) return rc;
     TK_HIP(c, c->jn_in_ctrl.reserve(n_parts * 4 + 16));
     TK_HIP(c, c->jn_in_flags.reserve(n_parts * 4 + 16));
     TK_HIP(c, c->jn_in_conv.reserve((n_convs + 1) * 8));
     if (n_parts) TK_HIP(c, hipMemcpyAsync(c->jn_in_ctrl.p, part_ctrl, n_parts * 4, hipMemcpyHostToDevice, c->stream));
     if (n_parts && part_flags) TK_HIP(c, hipMemcpyAsync(c->jn_in_flags.p, part_flags, n_parts * 4, hipMemcpyHostToDevice, c->stream));
     TK_HIP(c, hipMemcpyAsync(c->jn_in_conv.p, conv_offsets, (n_convs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    // (the small path's ids and offsets are mapped pinned memory: the kernels read them there)
     tk_join j;
     rc = run_join(c, dev.ids, dev.id_offs, n_parts, n_ids, (const uint32_t*)c->jn_in_ctrl.p, part_flags ? (const uint32_t*)c->jn_in_flags.p : nullptr,
                   (const uint64_t*)c->jn_in_conv.p, n_convs, false, opts, c->stream, &j);
     if (rc != TK_OK) return rc;
-    // (an unselected output: no device source, an empty block that is given back at once)
-    CopyOut h[4] = {{j.n_ids ? j.ids : nullptr, (j.n_ids ? j.n_ids : 1) * 4, nullptr}, {j.offsets, (n_convs + 1) * 8, nullptr},
-                    {j.n_ids ? j.labels : nullptr, j.labels ? (j.n_ids ? j.n_ids : 1) * 4 : 0, nullptr},
-                    {j.n_ids ? j.part_index : nullptr, j.part_index ? (j.n_ids ? j.n_ids : 1) * 4 : 0, nullptr}};
+    const uint64_t n4 = (j.n_ids ? j.n_ids : 1) * 4;     // (no id: no device source, the block alone)
+    CopyOut h[4] = {{j.n_ids ? j.ids : nullptr, n4, nullptr}, {j.offsets, (n_convs + 1) * 8, nullptr},
+                    {j.n_ids ? j.labels : nullptr, n4, nullptr, j.labels != nullptr},
+                    {j.n_ids ? j.part_index : nullptr, n4, nullptr, j.part_index != nullptr}};
     if ((rc = copy_out(c, h, 4, "join")) != TK_OK) return rc;
     *out = j;
     out->ids = (uint32_t*)h[0].host;
     out->offsets = (uint64_t*)h[1].host;
-    if (j.labels) out->labels = (int32_t*)h[2].host; else tk_pinned_put(h[2].host);
-    if (j.part_index) out->part_index = (uint32_t*)h[3].host; else tk_pinned_put(h[3].host);
+    out->labels = (int32_t*)h[2].host;
+    out->part_index = (uint32_t*)h[3].host;
     return TK_OK;
 }

@@ -3,15 +3,13 @@
 #include "tk_ctx.h"
 
 #define TK_SEQPACK_ALL_FLAGS (TK_SEQPACK_I64 | TK_SEQPACK_POSITIONS | TK_SEQPACK_SEGMENTS | TK_SEQPACK_CU_SEQLENS | TK_SEQPACK_DROP_LAST)
-#define TK_SEQPACK_MAX_ROW 0x7FFFFFFFull        /* seq_len stays below 2^31 */
-#define TK_SEQPACK_MAX_ELEMS (1ull << 36)       /* n_rows * seq_len, as the dense tensor */
 
 // the options that can be refused before the number of ids is known (step 8 of the definition)
 static int seqpack_check_opts(tk_ctx* c, const tk_seqpack_opts* o) {
     if (!o) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
     if (o->flags & ~(uint32_t)TK_SEQPACK_ALL_FLAGS) { c->err = "unknown seqpack flag"; return TK_ERR_INVALID_ARG; }
     if (o->seq_len == 0) { c->err = "seqpack needs a seq_len"; return TK_ERR_INVALID_ARG; }
-    if (o->seq_len > TK_SEQPACK_MAX_ROW) { c->err = "seq_len " + std::to_string(o->seq_len) + " is beyond 2^31 - 1"; return TK_ERR_INVALID_ARG; }
+    if (o->seq_len > TK_LAYOUT_MAX_ROW) { c->err = "seq_len " + std::to_string(o->seq_len) + " is beyond 2^31 - 1"; return TK_ERR_INVALID_ARG; }
     return TK_OK;
 }
 
@@ -29,7 +27,7 @@ static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_of
                want_seg = (o->flags & TK_SEQPACK_SEGMENTS) != 0, want_cu = (o->flags & TK_SEQPACK_CU_SEQLENS) != 0;
     const uint64_t n_rows = (o->flags & TK_SEQPACK_DROP_LAST) ? n_ids / L : n_ids / L + (n_ids % L != 0);
     const uint64_t n_used = n_ids < n_rows * L ? n_ids : n_rows * L;
-    if (n_rows > TK_SEQPACK_MAX_ELEMS / L) {
+    if (n_rows > TK_LAYOUT_MAX_ELEMS / L) {
         c->err = "seqpack: " + std::to_string(n_rows) + " rows of " + std::to_string(L) + " elements are beyond what one tensor can hold";
         return TK_ERR_INVALID_ARG;
     }
@@ -53,7 +51,7 @@ static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_of
         TK_HIP(c, c->sp_apos.reserve((n_docs + 1) * 8));
         TK_HIP(c, c->sp_starts.reserve((n_docs + 1) * 8));
         TK_HIP(c, c->sp_aligned.reserve((n_docs + 1) * 8));
-        TK_HIP(c, c->sp_bsum.reserve((n_docs / 2048 + 4) * 8));
+        TK_HIP(c, c->sp_bsum.reserve(scan_workspace_bytes(n_docs)));
         TkSeqpackArgs a;
         memset(&a, 0, sizeof(a));
         a.ids = d_ids;
@@ -76,8 +74,8 @@ static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_of
         a.stat = (unsigned long long*)c->sp_stat.p;
         TK_HIP(c, hipMemsetAsync(a.stat, 0, 16, s));
         TK_HIP(c, tk_launch_seqpack_flags(a, s));
-        TK_HIP(c, tk_launch_scan(a.flags, n_docs, (uint64_t*)c->sp_fpos.p, (uint64_t*)c->sp_bsum.p, s));
-        TK_HIP(c, tk_launch_scan(a.aflags, n_docs, (uint64_t*)c->sp_apos.p, (uint64_t*)c->sp_bsum.p, s));
+        if ((rc = scan_u32(c, c->sp_bsum, a.flags, n_docs, (uint64_t*)c->sp_fpos.p, s)) != TK_OK) return rc;
+        if ((rc = scan_u32(c, c->sp_bsum, a.aflags, n_docs, (uint64_t*)c->sp_apos.p, s)) != TK_OK) return rc;
         TK_HIP(c, tk_launch_seqpack_starts(a, s));
         TK_HIP(c, tk_launch_seqpack(a, i64, s));
         TK_HIP(c, tk_launch_seqpack_cu(a, s));
@@ -109,10 +107,8 @@ extern "C" int tk_encode_batch_device_seqpack(tk_ctx* c, const void* d_bytes, co
                                               uint64_t n_bytes, int add_bos, int add_eos, int checks, const tk_seqpack_opts* opts,
                                               void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_seqpack* out) {
     TK_ENTRY(c);
-    if (checks & ~(TK_CHECK_OFFSETS | TK_CHECK_UTF8)) { c->err = "unknown check flag"; return TK_ERR_INVALID_ARG; }
-    if (!opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    int rc = seqpack_check_opts(c, opts);
-    if (rc != TK_OK) return rc;
+    int rc = check_flags_and_args(c, checks, TK_CHECK_OFFSETS | TK_CHECK_UTF8, !opts || !out);
+    if (rc != TK_OK || (rc = seqpack_check_opts(c, opts)) != TK_OK) return rc;
     rc = encode_device_checked(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, hip_stream, d_ids, d_out_offsets, n_ids);
     if (rc != TK_OK) return rc;
     return run_seqpack(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, *n_ids, opts, (hipStream_t)hip_stream, out);
@@ -134,27 +130,21 @@ extern "C" int tk_encode_batch_seqpack(tk_ctx* c, const uint8_t* bytes, const ui
     memset(out, 0, sizeof(*out));
     int rc = seqpack_check_opts(c, opts);
     if (rc != TK_OK) return rc;
-    tk_result res;
     DevBatch dev;
-    rc = encode_batch(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &res, &dev);
-    if (rc != TK_OK) return rc;
-    const uint64_t n_ids = res.n_ids;
-    tk_free_result(&res);   // (the host copy of the ragged ids is not part of this entry's result)
-    // (the small path's ids and offsets are mapped pinned memory: the kernels read them there)
+    uint64_t n_ids;
+    if ((rc = encode_batch_for_layout(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &dev, &n_ids)) != TK_OK) return rc;
     tk_seqpack p;
     rc = run_seqpack(c, dev.ids, dev.id_offs, n_docs, n_ids, opts, c->stream, &p);
     if (rc != TK_OK) return rc;
     const uint64_t bytes_t = p.n_rows * p.row_len * ((opts->flags & TK_SEQPACK_I64) ? 8 : 4);
-    // (an unselected output: no device source, an empty block that is given back at once)
-    CopyOut h[4] = {{p.input_ids, bytes_t, nullptr}, {p.position_ids, p.position_ids ? bytes_t : 0, nullptr},
-                    {p.segment_ids, p.segment_ids ? bytes_t : 0, nullptr}, {p.cu_seqlens, p.cu_seqlens ? (p.n_segments + 1) * 4 : 0, nullptr}};
+    CopyOut h[4] = {{p.input_ids, bytes_t, nullptr}, {p.position_ids, bytes_t, nullptr, p.position_ids != nullptr},
+                    {p.segment_ids, bytes_t, nullptr, p.segment_ids != nullptr},
+                    {p.cu_seqlens, (p.n_segments + 1) * 4, nullptr, p.cu_seqlens != nullptr}};
     if ((rc = copy_out(c, h, 4, "seqpack")) != TK_OK) return rc;
     *out = p;
     out->input_ids = h[0].host;
-    void** dst[3] = {&out->position_ids, &out->segment_ids, (void**)&out->cu_seqlens};
-    for (int i = 0; i < 3; ++i) {
-        if (*dst[i]) *dst[i] = h[i + 1].host;
-        else tk_pinned_put(h[i + 1].host);
-    }
+    out->position_ids = h[1].host;
+    out->segment_ids = h[2].host;
+    out->cu_seqlens = (int32_t*)h[3].host;
     return TK_OK;
 }

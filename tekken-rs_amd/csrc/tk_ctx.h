@@ -109,7 +109,6 @@ struct tk_ctx {
     // the dense layout (tk_dense.hip): the tensor, its mask, lengths and the two statistics words; the ragged ids / offsets / row
     // lengths of the inverse.  Apart from every encode / spans / decode buffer, allocated at the first dense call
     DevBuf dn_ids, dn_mask, dn_len, dn_stat, dn_rids, dn_roffs, dn_rlens;
-    int dense_nt = -1;         // non-temporal stores of the dense kernel (TK_DENSE_NT: A / B; read at the first dense call, -1 = not yet)
     // the packed training rows (tk_seqpack.hip): the three tensors, cu_seqlens and the two statistics words; the work arrays
     // (flags and their scans, the compacted starts, the scan workspace).  Apart from every other buffer, allocated at the first packed call
     DevBuf sp_ids, sp_pos, sp_seg, sp_cu, sp_stat, sp_flags, sp_aflags, sp_fpos, sp_apos, sp_starts, sp_aligned, sp_bsum;
@@ -186,11 +185,21 @@ int upload(tk_ctx* c, DevBuf& b, const void* src, size_t bytes);
 int check_n_docs(tk_ctx* c, uint64_t n_docs);
 int enter_device(tk_ctx* c, uint64_t n_docs);
 // Result copy-out: pinned blocks from the process-wide pool for n arrays (an array of 0 bytes gets a block too; dev == nullptr: the
-// block alone), the device -> host copies on c->stream, ONE wait.  On a failure every block is back in the pool, c->err is
-// "hipHostMalloc failed" or "<what> copy failed: ..." and host[] is all null.
-struct CopyOut { const void* dev; size_t bytes; void* host; };
+// block alone; !selected -- an output the caller did not ask for --: no block, host stays null), the device -> host copies on
+// c->stream, ONE wait.  On a failure every block is back in the pool, c->err is "hipHostMalloc failed" or
+// "<what> copy failed: ..." and host[] is all null.
+struct CopyOut { const void* dev; size_t bytes; void* host; bool selected = true; };
 int pinned_blocks(tk_ctx* c, CopyOut* a, int n);
 int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what);
+// ---- what the layout passes share (tk_capi_dense / _seqpack / _join.cpp) ----
+#define TK_LAYOUT_MAX_ROW 0x7FFFFFFFull         /* a row of a tensor stays below 2^31 elements */
+#define TK_LAYOUT_MAX_ELEMS (1ull << 36)        /* rows * row length: 256 GiB of int32, more than the part holds */
+// how an entry with check flags opens: an unknown flag is refused first, then a null argument
+int check_flags_and_args(tk_ctx* c, int checks, int known, bool null_arg);
+// offs[0 .. n] = the exclusive prefix sums of counts[0 .. n) on s.  `workspace` is sized for it here, which allocates only where
+// the caller has not reserved scan_workspace_bytes(n) with its other buffers, before its first launch
+static inline size_t scan_workspace_bytes(uint64_t n) { return (n / 2048 + 4) * 8; }
+int scan_u32(tk_ctx* c, DevBuf& workspace, const uint32_t* counts, uint64_t n, uint64_t* offs, hipStream_t s);
 // tk_pipeline.cpp: the batch pipeline over text on the device; the ids end in c->out_ids, their offsets in c->out_offs
 int run_pipeline(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs, uint64_t n_docs, uint64_t n_bytes, int add_bos,
                  int add_eos, hipStream_t s, uint64_t* n_ids);
@@ -208,6 +217,10 @@ struct DevBatch {
 };
 int encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
                  int validate_utf8, tk_result* out, DevBatch* dev);
+// tk_capi.cpp: encode_batch for a layout pass, which reads the ids where *dev says (the small path's are mapped pinned memory: the
+// kernels read them there) and whose result does not hold the ragged ids: their host copy is freed, their number kept
+int encode_batch_for_layout(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                            int validate_utf8, DevBatch* dev, uint64_t* n_ids);
 // tk_capi_decode.cpp: the decode kernels' tables (also what the spans kernel reads), built at the first call that needs them
 int token_tables(tk_ctx* c);
 template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // ... as the decode and spans kernels take them

@@ -131,8 +131,8 @@ struct TkDenseArgs {
     unsigned long long* stat;  // [0] longest document (tk_launch_dense_maxlen), [1] += truncated documents (tk_launch_dense)
     uint32_t units, rb, magic; // the launch shape (set by the launcher): units a row, rows a block, 2^32 / units rounded up
 };
-// row_len == 0 or n_docs == 0: nothing is launched (the caller zeroes lengths).  nontemporal: the vector stores bypass the caches
-hipError_t tk_launch_dense(const TkDenseArgs& a, int i64, int nontemporal, hipStream_t s);
+// row_len == 0 or n_docs == 0: nothing is launched (the caller zeroes lengths)
+hipError_t tk_launch_dense(const TkDenseArgs& a, int i64, hipStream_t s);
 hipError_t tk_launch_dense_maxlen(const uint64_t* id_offs, uint64_t n_docs, unsigned long long* stat, hipStream_t s);
 struct TkRaggedArgs {
     const void* dense;         // [n_docs * row_len] int32 or int64

@@ -12,12 +12,12 @@
 //   2. tk_seqpack_starts_kernel: the starts of the non-empty documents, compacted into a strictly increasing array starts[M]
 //      (+ the sentinel starts[M] = N), and beside each the number of aligned starts before it.  Runs of empty documents cost
 //      nothing from here on.
-//   3. tk_seqpack_kernel: a block takes a tile of TKS_TILE consecutive stream positions.  Three of its waves find, each with
+//   3. tk_seqpack_kernel: a block takes a tile of TKY_TILE consecutive stream positions.  Three of its waves find, each with
 //      one 64-ary search (every lane probes, a ballot narrows the range 64 times a step: 4 dependent loads for a million
 //      documents), how many starts lie at or before the tile's first id, its last id and the start of its first row.  The
 //      starts inside the tile go to LDS relative to the tile; a unit (4 consecutive elements of one row where L % 4 == 0 --
 //      one 16-byte store for each int32 output, two for int64 --, one element otherwise) resolves its document there with a
-//      binary search and walks forward over its elements.  A tile with more than TKS_CAP starts (many one-id documents) reads
+//      binary search and walks forward over its elements.  A tile with more than TKY_CAP starts (many one-id documents) reads
 //      the same values from global memory instead: decided per block.  Every output element is written exactly once, pads
 //      included; an unselected output is not touched.
 //   4. tk_seqpack_cu_kernel: one item per compacted start, per row and one terminal.  The rank of a segment start in
@@ -28,18 +28,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "tk_dpp_scan.h"
 #include "tk_kernels.h"
-#include "tk_wave_search.h"
+#include "tk_layout.h"
 
-#define TKS_BLOCK 256
-#define TKS_TILE 4096u     /* stream positions of a block's tile (16 a thread) */
-#define TKS_CAP 1024u      /* document starts of a tile that LDS holds (4 KiB) */
-
-typedef uint32_t __attribute__((ext_vector_type(4))) tks_u32x4;
-
-__global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_flags_kernel(TkSeqpackArgs a) {
-    for (uint64_t d = (uint64_t)blockIdx.x * TKS_BLOCK + threadIdx.x; d < a.n_docs; d += (uint64_t)gridDim.x * TKS_BLOCK) {
+__global__ __launch_bounds__(TKY_BLOCK) void tk_seqpack_flags_kernel(TkSeqpackArgs a) {
+    for (uint64_t d = (uint64_t)blockIdx.x * TKY_BLOCK + threadIdx.x; d < a.n_docs; d += (uint64_t)gridDim.x * TKY_BLOCK) {
         const uint64_t o = a.id_offs[d];
         const bool has = a.id_offs[d + 1] > o;
         a.flags[d] = has;
@@ -47,8 +40,8 @@ __global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_flags_kernel(TkSeqpackAr
     }
 }
 
-__global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_starts_kernel(TkSeqpackArgs a) {
-    for (uint64_t d = (uint64_t)blockIdx.x * TKS_BLOCK + threadIdx.x; d <= a.n_docs; d += (uint64_t)gridDim.x * TKS_BLOCK) {
+__global__ __launch_bounds__(TKY_BLOCK) void tk_seqpack_starts_kernel(TkSeqpackArgs a) {
+    for (uint64_t d = (uint64_t)blockIdx.x * TKY_BLOCK + threadIdx.x; d <= a.n_docs; d += (uint64_t)gridDim.x * TKY_BLOCK) {
         if (d < a.n_docs && !a.flags[d]) continue;      // (d == n_docs: the sentinel behind the last start)
         const uint64_t i = a.fpos[d];
         a.starts[i] = a.id_offs[d];
@@ -56,90 +49,37 @@ __global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_starts_kernel(TkSeqpackA
     }
 }
 
-// entries of a[0 .. n) that are < key, one lane on its own (the cu_seqlens kernel: once a row)
-__device__ __forceinline__ uint64_t tks_count_lt(const uint64_t* a, uint64_t n, uint64_t key) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 template <int I64, int VEC>
-__device__ __forceinline__ void tks_store(void* base, uint64_t at, const uint32_t* v) {
-    if (VEC) {
-        if (I64) {
-            tks_u32x4* p = reinterpret_cast<tks_u32x4*>(reinterpret_cast<uint64_t*>(base) + at);
-            const tks_u32x4 lo = {v[0], 0u, v[1], 0u}, hi = {v[2], 0u, v[3], 0u};
-            p[0] = lo; p[1] = hi;
-        } else {
-            const tks_u32x4 x = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<tks_u32x4*>(reinterpret_cast<uint32_t*>(base) + at) = x;
-        }
-    } else {
-        if (I64) reinterpret_cast<uint64_t*>(base)[at] = v[0];
-        else reinterpret_cast<uint32_t*>(base)[at] = v[0];
-    }
-}
-
-template <int I64, int VEC>
-__global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_kernel(TkSeqpackArgs a) {
+__global__ __launch_bounds__(TKY_BLOCK) void tk_seqpack_kernel(TkSeqpackArgs a) {
     constexpr uint32_t W = VEC ? 4u : 1u;
-    __shared__ uint32_t s_rel[TKS_CAP];                 // starts inside the tile, relative to its first position
-    __shared__ uint64_t s_cnt[3];
     const uint32_t L = a.row_len;
     const uint64_t total = a.n_rows * L, n_used = a.n_used;
-    const uint64_t n_tiles = (total + TKS_TILE - 1) / TKS_TILE;
+    const uint64_t n_tiles = (total + TKY_TILE - 1) / TKY_TILE;
     const bool side = a.out_pos || a.out_seg;
     const uint64_t M = side ? a.fpos[a.n_docs] : 0;     // non-empty documents
-    const uint32_t wave = threadIdx.x >> 6;
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const uint64_t g0 = t * TKS_TILE;
-        const uint64_t g1 = total - g0 < TKS_TILE ? total : g0 + TKS_TILE;
+        const uint64_t g0 = t * TKY_TILE;
+        const uint64_t g1 = total - g0 < TKY_TILE ? total : g0 + TKY_TILE;
         const uint64_t u1 = g1 < n_used ? g1 : n_used;  // behind the tile's last id (the rest is pad)
         const bool search = side && g0 < n_used;        // (block-uniform, as everything up to the unit loop)
         const uint64_t r0 = g0 / L;
         const uint32_t c0 = (uint32_t)(g0 - r0 * L);    // column of the tile's first position
-        // starts at or before: the tile's first id (>= 1: starts[0] == 0) | its last id | the start of its first row
-        uint64_t n_lo = 0, n_row = 0, start_lo = 0;
-        uint32_t cnt = 0;
-        bool lds = true;
+        TkyTile<3> tile(a.starts, g0);
+        uint64_t n_row = 0;                             // starts at or before the start of the tile's first row
         if (search) {
-            __syncthreads();                            // (the previous tile's readers of s_rel / s_cnt are done)
-            if (wave < 3u) {
-                const uint64_t key = wave == 0u ? g0 : wave == 1u ? u1 - 1u : r0 * L;
-                const uint64_t c = tks_wave_count_le(a.starts, M, key);
-                if ((threadIdx.x & 63u) == 0u) s_cnt[wave] = c;
-            }
-            __syncthreads();
-            n_lo = s_cnt[0];
-            n_row = s_cnt[2];
-            cnt = (uint32_t)(s_cnt[1] - n_lo);          // starts in (g0, u1): < TKS_TILE
-            lds = cnt <= TKS_CAP;
-            if (lds) {
-                for (uint32_t j = threadIdx.x; j < cnt; j += TKS_BLOCK) s_rel[j] = (uint32_t)(a.starts[n_lo + j] - g0);
-                __syncthreads();
-            }
-            start_lo = a.starts[n_lo - 1u];
+            tile.search(M, g0, u1 - 1u, r0 * L);         // starts at or before: the tile's first id (>= 1: starts[0] == 0) | its last id | n_row
+            const uint64_t n_lo = tile.found(0);
+            n_row = tile.found(2);
+            tile.open(n_lo, (uint32_t)(tile.found(1) - n_lo));   // starts in (g0, u1): < TKY_TILE
+            tile.stage();
         }
-        const uint64_t* gst = a.starts + n_lo;
-        auto rel = [&](uint32_t j) -> uint32_t { return lds ? s_rel[j] : (uint32_t)(gst[j] - g0); };
-        auto count_le = [&](uint32_t x) -> uint32_t {   // staged starts at or before relative position x
-            uint32_t lo = 0, hi = cnt;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (rel(mid) <= x) lo = mid + 1u; else hi = mid;
-            }
-            return lo;
-        };
         const uint32_t units = (uint32_t)(g1 - g0) / W; // (VEC: total and g0 are multiples of 4)
-        for (uint32_t u = threadIdx.x; u < units; u += TKS_BLOCK) {
+        for (uint32_t u = threadIdx.x; u < units; u += TKY_BLOCK) {
             const uint32_t l = u * W;
             const uint64_t g = g0 + l;
             uint32_t v[4], p[4] = {0u, 0u, 0u, 0u}, sg[4] = {0u, 0u, 0u, 0u};
             if (VEC && a.ids_al16 && g + 4u <= n_used) {
-                const tks_u32x4 x = *reinterpret_cast<const tks_u32x4*>(a.ids + g);
+                const tky_u32x4 x = *reinterpret_cast<const tky_u32x4*>(a.ids + g);
                 v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
             } else {
 #pragma unroll
@@ -149,33 +89,33 @@ __global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_kernel(TkSeqpackArgs a) 
                 const uint32_t cabs = c0 + l;           // column counted from the tile's first row (c0 < L < 2^31)
                 const uint32_t rr = cabs / L, col = cabs - rr * L;
                 const int64_t rowrel = (int64_t)l - (int64_t)col;     // the row's start relative to the tile (rr > 0: inside it)
-                const uint64_t n_rowstart = rr == 0u ? n_row : n_lo + count_le((uint32_t)rowrel);
-                uint32_t k = count_le(l);
+                const uint64_t n_rowstart = rr == 0u ? n_row : tile.n_lo + tile.count_le((uint32_t)rowrel);
+                uint32_t k = tile.count_le(l);
 #pragma unroll
                 for (uint32_t q = 0; q < W; ++q) {
                     if (g + q >= n_used) break;
                     const uint32_t lq = l + q;
-                    while (k < cnt && rel(k) <= lq) ++k;
-                    const int64_t docrel = k ? (int64_t)rel(k - 1u) : -(int64_t)(g0 - start_lo);
+                    while (k < tile.count && tile.rel(k) <= lq) ++k;
+                    const int64_t docrel = tile.start_of(k);
                     p[q] = (uint32_t)((int64_t)lq - (docrel > rowrel ? docrel : rowrel));
-                    sg[q] = (uint32_t)(n_lo + k - n_rowstart) + 1u;
+                    sg[q] = (uint32_t)(tile.n_lo + k - n_rowstart) + 1u;
                 }
             }
-            tks_store<I64, VEC>(a.out_ids, g, v);
-            if (a.out_pos) tks_store<I64, VEC>(a.out_pos, g, p);
-            if (a.out_seg) tks_store<I64, VEC>(a.out_seg, g, sg);
+            tky_store<I64, VEC>(a.out_ids, g, v);
+            if (a.out_pos) tky_store<I64, VEC>(a.out_pos, g, p);
+            if (a.out_seg) tky_store<I64, VEC>(a.out_seg, g, sg);
         }
     }
 }
 
-__global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_cu_kernel(TkSeqpackArgs a) {
+__global__ __launch_bounds__(TKY_BLOCK) void tk_seqpack_cu_kernel(TkSeqpackArgs a) {
     const uint32_t L = a.row_len;
     const uint64_t D = a.n_docs, n_used = a.n_used, M = a.fpos[D];
     const uint64_t n_items = D + a.n_rows + 1u;         // [0, D): compacted starts (the first M) | rows | the terminal
-    const uint64_t n_iter = (n_items + (uint64_t)gridDim.x * TKS_BLOCK - 1u) / ((uint64_t)gridDim.x * TKS_BLOCK);
+    const uint64_t n_iter = (n_items + (uint64_t)gridDim.x * TKY_BLOCK - 1u) / ((uint64_t)gridDim.x * TKY_BLOCK);
     uint32_t longest = 0;
     for (uint64_t it = 0; it < n_iter; ++it) {
-        const uint64_t t = (it * gridDim.x + blockIdx.x) * TKS_BLOCK + threadIdx.x;
+        const uint64_t t = (it * gridDim.x + blockIdx.x) * TKY_BLOCK + threadIdx.x;
         if (t < D) {
             if (t >= M) continue;
             const uint64_t s = a.starts[t];
@@ -188,36 +128,30 @@ __global__ __launch_bounds__(TKS_BLOCK) void tk_seqpack_cu_kernel(TkSeqpackArgs 
             if (a.cu) a.cu[t + r + 1u - a.n_aligned[t]] = (int32_t)s;
         } else if (t < D + a.n_rows) {
             const uint64_t r = t - D, s = r * L;
-            const uint64_t j = tks_count_lt(a.starts, M, s);
+            const uint64_t j = tky_count_lt(a.starts, M, s);
             uint64_t end = a.starts[j] == s ? a.starts[j + 1u] : a.starts[j];   // (starts[M] = N: the sentinel)
             if (end > s + L) end = s + L;
             if (end > n_used) end = n_used;
             longest = max(longest, (uint32_t)(end - s));
             if (a.cu) a.cu[r + j - a.n_aligned[j]] = (int32_t)s;
         } else if (t == D + a.n_rows) {
-            const uint64_t j = tks_count_lt(a.starts, M, n_used);
+            const uint64_t j = tky_count_lt(a.starts, M, n_used);
             const uint64_t n_seg = a.n_rows + j - a.n_aligned[j];
             if (a.cu) a.cu[n_seg] = (int32_t)n_used;
             a.stat[0] = n_seg;
         }
     }
-    longest = (uint32_t)__builtin_amdgcn_readlane((int)tkd_scan_max(longest), 63);
-    if ((threadIdx.x & 63u) == 0u && longest) atomicMax(a.stat + 1, (unsigned long long)longest);
-}
-
-static uint32_t tks_blocks(uint64_t n, uint64_t cap) {
-    const uint64_t b = (n + TKS_BLOCK - 1) / TKS_BLOCK;
-    return (uint32_t)(b < cap ? b : cap);
+    tky_wave_max(a.stat + 1, longest);
 }
 
 hipError_t tk_launch_seqpack_flags(const TkSeqpackArgs& a, hipStream_t s) {
     if (a.n_docs == 0) return hipSuccess;
-    hipLaunchKernelGGL(tk_seqpack_flags_kernel, dim3(tks_blocks(a.n_docs, 1u << 16)), dim3(TKS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tk_seqpack_flags_kernel, dim3(tky_blocks(a.n_docs, 1u << 16)), dim3(TKY_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t tk_launch_seqpack_starts(const TkSeqpackArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(tk_seqpack_starts_kernel, dim3(tks_blocks(a.n_docs + 1u, 1u << 16)), dim3(TKS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tk_seqpack_starts_kernel, dim3(tky_blocks(a.n_docs + 1u, 1u << 16)), dim3(TKY_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
@@ -225,17 +159,16 @@ hipError_t tk_launch_seqpack(const TkSeqpackArgs& args, int i64, hipStream_t s) 
     if (args.n_rows == 0) return hipSuccess;
     TkSeqpackArgs a = args;
     a.ids_al16 = ((uintptr_t)a.ids & 15u) == 0u;
-    const uint64_t n_tiles = (a.n_rows * a.row_len + TKS_TILE - 1) / TKS_TILE;
-    const dim3 grid((uint32_t)(n_tiles < (1ull << 20) ? n_tiles : (1ull << 20)));
+    const dim3 grid(tky_blocks(a.n_rows * a.row_len, 1u << 20, TKY_TILE));
     const bool vec = a.row_len % 4u == 0u;
-    if (i64 && vec) hipLaunchKernelGGL((tk_seqpack_kernel<1, 1>), grid, dim3(TKS_BLOCK), 0, s, a);
-    else if (i64) hipLaunchKernelGGL((tk_seqpack_kernel<1, 0>), grid, dim3(TKS_BLOCK), 0, s, a);
-    else if (vec) hipLaunchKernelGGL((tk_seqpack_kernel<0, 1>), grid, dim3(TKS_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((tk_seqpack_kernel<0, 0>), grid, dim3(TKS_BLOCK), 0, s, a);
+    if (i64 && vec) hipLaunchKernelGGL((tk_seqpack_kernel<1, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
+    else if (i64) hipLaunchKernelGGL((tk_seqpack_kernel<1, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
+    else if (vec) hipLaunchKernelGGL((tk_seqpack_kernel<0, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((tk_seqpack_kernel<0, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t tk_launch_seqpack_cu(const TkSeqpackArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(tk_seqpack_cu_kernel, dim3(tks_blocks(a.n_docs + a.n_rows + 1u, 2048u)), dim3(TKS_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tk_seqpack_cu_kernel, dim3(tky_blocks(a.n_docs + a.n_rows + 1u, 2048u)), dim3(TKY_BLOCK), 0, s, a);
     return hipGetLastError();
 }

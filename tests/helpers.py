@@ -58,3 +58,49 @@ def oracle_for(v):
 def starts_to_pieces(doc, starts):
     s = list(starts) + [len(doc)]
     return [doc[s[i]:s[i + 1]] for i in range(len(s) - 1)]
+
+
+# ---- what the GPU tests of the layout passes share (test_gpu_dense / _seqpack / _join.py) ----
+
+def to_host(view, shape, dtype):
+    """A DeviceView as a numpy array of `shape` (an int: one dimension); an unselected output (None) stays None, and an empty
+    tensor has nothing behind its pointer to look at."""
+    import torch
+    shape = shape if isinstance(shape, tuple) else (shape,)
+    if view is None:
+        return None
+    if 0 in shape:
+        return np.zeros(shape, dtype)
+    return torch.as_tensor(view, device="cuda").cpu().numpy().view(dtype).reshape(shape)
+
+
+def dev(a, dtype):
+    """A host array on the device, seen as `dtype` (uint32 / uint64 go up as the signed type of the same width)."""
+    import torch
+    a = np.ascontiguousarray(a, dtype)
+    if len(a) == 0:
+        a = np.zeros(1, dtype)
+    return torch.from_numpy(a.view({np.uint32: np.int32, np.uint64: np.int64, np.uint8: np.uint8}[dtype])).cuda()
+
+
+def on_device(ids, oo):
+    """Ragged ids and their offsets on the device."""
+    return dev(ids, np.uint32), dev(oo, np.uint64)
+
+
+def assert_array_same(got, exp, what=""):
+    """Shape, dtype and every element; an unselected output is None on both sides."""
+    assert (got is None) == (exp is None), what
+    if exp is None:
+        return
+    assert got.shape == exp.shape and got.dtype == exp.dtype, (what, got.shape, exp.shape, got.dtype)
+    bad = np.argwhere(got != exp)
+    assert len(bad) == 0, (what, "first differing element", bad[0].tolist(), int(got[tuple(bad[0])]), int(exp[tuple(bad[0])]))
+
+
+def assert_same(got, exp, what="", counts=(), arrays=()):
+    """Two result dicts: the counts equal, the arrays element by element."""
+    for k in counts:
+        assert got[k] == exp[k], (what, k, got[k], exp[k])
+    for k in arrays:
+        assert_array_same(got[k], exp[k], (what, k))

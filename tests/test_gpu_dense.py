@@ -8,49 +8,30 @@ import pytest
 
 import corpus
 import helpers
+from helpers import on_device, to_host
 from test_dense_cpu import FIXED, I64, MASK, PAD_LEFT, TRUNC_LEFT, expected_dense, expected_ragged
 from test_gpu_spans import pack, sweep_docs
 
 pytestmark = pytest.mark.gpu
 
 
-def to_host(tk, view, shape, dtype):
-    """A DeviceView as a numpy array (an empty tensor has nothing behind its pointer to look at)."""
-    import torch
-    if view is None:
-        return None
-    if 0 in shape:
-        return np.zeros(shape, dtype)
-    return torch.as_tensor(view, device="cuda").cpu().numpy().view(dtype).reshape(shape)
-
-
 def fetch(tk, res):
     """DenseResult -> dict like expected_dense's."""
     v_ids, v_mask, v_len = res.views()
     D, L = res.n_docs, res.row_len
-    return {"dense": to_host(tk, v_ids, (D, L), np.int64 if res.typestr == "<i8" else np.int32),
-            "mask": to_host(tk, v_mask, (D, L), np.uint8), "lengths": to_host(tk, v_len, (D,), np.uint32),
+    return {"dense": to_host(v_ids, (D, L), np.int64 if res.typestr == "<i8" else np.int32),
+            "mask": to_host(v_mask, (D, L), np.uint8), "lengths": to_host(v_len, (D,), np.uint32),
             "row_len": L, "n_truncated": res.n_truncated}
 
 
 def assert_same(got, exp, what=""):
-    assert got["row_len"] == exp["row_len"] and got["dense"].shape == exp["dense"].shape, (what, got["dense"].shape, exp["dense"].shape)
-    assert got["dense"].dtype == exp["dense"].dtype, what
-    bad = np.argwhere(got["dense"] != exp["dense"])
-    assert len(bad) == 0, (what, "first differing element", bad[0].tolist(), int(got["dense"][tuple(bad[0])]), int(exp["dense"][tuple(bad[0])]))
+    assert got["row_len"] == exp["row_len"], (what, got["row_len"], exp["row_len"])
+    helpers.assert_array_same(got["dense"], exp["dense"], what)
     assert (got["mask"] is None) == (exp["mask"] is None), what
     if exp["mask"] is not None:
         assert np.array_equal(got["mask"], exp["mask"]), what
     assert np.array_equal(got["lengths"], exp["lengths"]), what
     assert got["n_truncated"] == exp["n_truncated"], what
-
-
-def on_device(ids, oo):
-    import torch
-    ids = np.ascontiguousarray(ids, np.uint32).view(np.int32)
-    d_ids = torch.from_numpy(ids if len(ids) else np.zeros(1, np.int32)).cuda()
-    d_oo = torch.from_numpy(np.asarray(oo, np.int64)).cuda()
-    return d_ids, d_oo
 
 
 def dense_of(tk, eng, ids, oo, **kw):
@@ -69,9 +50,9 @@ def ragged_of(tk, eng, dense, lengths, pad_id, pad_left):
     flags = (I64 if dense.dtype == np.int64 else 0) | (PAD_LEFT if pad_left else 0)
     p_ids, p_oo, n = eng.ragged_from_dense_device(d.data_ptr() if D * L else 0, D, L, flags, d_len.data_ptr() if d_len is not None else 0, pad_id,
                                                   torch.cuda.current_stream().cuda_stream)
-    oo = to_host(tk, tk.DeviceView(p_oo, D + 1, "<i8"), (D + 1,), np.uint64)
+    oo = to_host(tk.DeviceView(p_oo, D + 1, "<i8"), (D + 1,), np.uint64)
     assert int(oo[-1]) == n
-    return to_host(tk, tk.DeviceView(p_ids, n, "<i4"), (n,), np.uint32), oo
+    return to_host(tk.DeviceView(p_ids, n, "<i4"), (n,), np.uint32), oo
 
 
 @pytest.fixture(scope="module")
@@ -156,8 +137,8 @@ def test_property_sweep(tk, vocabs, vname):
                     continue
                 p_ids, p_oo, n_ids, res = eng.encode_batch_device_dense(d_bytes.data_ptr(), d_offs.data_ptr(), D, len(data), bos, eos,
                                                                         pad_id=P, checks=tk.CHECK_OFFSETS, stream=stream, **opt)
-                ids = to_host(tk, tk.DeviceView(p_ids, n_ids, "<i4"), (n_ids,), np.uint32)
-                oo = to_host(tk, tk.DeviceView(p_oo, D + 1, "<i8"), (D + 1,), np.uint64)
+                ids = to_host(tk.DeviceView(p_ids, n_ids, "<i4"), (n_ids,), np.uint32)
+                oo = to_host(tk.DeviceView(p_oo, D + 1, "<i8"), (D + 1,), np.uint64)
                 assert np.array_equal(oo, eoo) and np.array_equal(ids, eids)
                 exp = expected_dense(eids, eoo, opt["max_length"], opt.get("multiple_of", 0), P, int(bos), int(eos), opt["flags"])
                 assert_same(fetch(tk, res), exp, (vname, bos, eos, opt))
@@ -210,8 +191,8 @@ def test_encode_and_spans_outputs_outlive_a_dense_call(tk, eng_bench, bench_voca
     p_ids, p_oo, p_sp, n = eng_bench.encode_batch_device_spans(d_bytes.data_ptr(), d_offs.data_ptr(), D, len(data), True, True, stream=stream)
 
     def snapshot():
-        return (to_host(tk, tk.DeviceView(p_ids, n, "<i4"), (n,), np.uint32).copy(), to_host(tk, tk.DeviceView(p_oo, D + 1, "<i8"), (D + 1,), np.uint64).copy(),
-                to_host(tk, tk.DeviceView(p_sp, 2 * n, "<i4"), (2 * n,), np.uint32).copy())
+        return (to_host(tk.DeviceView(p_ids, n, "<i4"), (n,), np.uint32).copy(), to_host(tk.DeviceView(p_oo, D + 1, "<i8"), (D + 1,), np.uint64).copy(),
+                to_host(tk.DeviceView(p_sp, 2 * n, "<i4"), (2 * n,), np.uint32).copy())
 
     before = snapshot()
     eids, eoo = helpers.oracle_for(bench_vocab).encode_batch(data, offs, True, True, threads=8)
@@ -229,7 +210,7 @@ def test_encode_and_spans_outputs_outlive_a_dense_call(tk, eng_bench, bench_voca
     for a, b in zip(before, after):
         assert np.array_equal(a, b)
     assert n2 == n and p_ids2 != p_ids
-    assert np.array_equal(to_host(tk, tk.DeviceView(p_ids2, n2, "<i4"), (n2,), np.uint32), eids)
+    assert np.array_equal(to_host(tk.DeviceView(p_ids2, n2, "<i4"), (n2,), np.uint32), eids)
 
 
 def test_errors_and_empty_shapes(tk, test_vocab):

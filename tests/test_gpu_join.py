@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import helpers
+from helpers import dev, to_host
 from test_gpu_spans import pack, sweep_docs
 from test_join_cpu import ALL, CHECK_PARTS, IGN, LABEL_CTRL, LABEL_TEXT, LABELS, NONE, PART_INDEX, TABLE, expected_joined, parts_table
 
@@ -13,17 +14,7 @@ pytestmark = pytest.mark.gpu
 
 ARRAYS = ("ids", "offsets", "labels", "part_index")
 COUNTS = ("n_ids", "n_ctrl", "n_labelled")
-TILE, CAP = 4096, 1024          # csrc/tk_join.hip: TKJ_TILE output positions a block, TKJ_CAP part starts its LDS array holds
-
-
-def to_host(view, n, dtype):
-    """A DeviceView as a numpy array (an empty array has nothing behind its pointer to look at)."""
-    import torch
-    if view is None:
-        return None
-    if n == 0:
-        return np.zeros(0, dtype)
-    return torch.as_tensor(view, device="cuda").cpu().numpy().view(dtype)
+TILE, CAP = 4096, 1024          # csrc/tk_layout.h: TKY_TILE output positions a block, TKY_CAP part starts its LDS array holds
 
 
 def fetch(res):
@@ -36,24 +27,7 @@ def fetch(res):
 
 
 def assert_same(got, exp, what=""):
-    for k in COUNTS:
-        assert got[k] == exp[k], (what, k, got[k], exp[k])
-    for k in ARRAYS:
-        assert (got[k] is None) == (exp[k] is None), (what, k)
-        if exp[k] is None:
-            continue
-        assert got[k].shape == exp[k].shape and got[k].dtype == exp[k].dtype, (what, k, got[k].shape, exp[k].shape, got[k].dtype)
-        bad = np.flatnonzero(got[k] != exp[k])
-        assert len(bad) == 0, (what, k, "first differing element", int(bad[0]), int(got[k][bad[0]]), int(exp[k][bad[0]]))
-
-
-def dev(a, dtype):
-    """A host array on the device, seen as `dtype` (uint32 / uint64 go up as the signed type of the same width)."""
-    import torch
-    a = np.ascontiguousarray(a, dtype)
-    if len(a) == 0:
-        a = np.zeros(1, dtype)
-    return torch.from_numpy(a.view({np.uint32: np.int32, np.uint64: np.int64, np.uint8: np.uint8}[dtype])).cuda()
+    helpers.assert_same(got, exp, what, COUNTS, ARRAYS)
 
 
 class Parts:

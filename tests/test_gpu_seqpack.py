@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import helpers
+from helpers import on_device, to_host
 from test_gpu_spans import pack, sweep_docs
 from test_seqpack_cpu import ALL, CU_SEQLENS, DROP_LAST, I64, POSITIONS, SEGMENTS, expected_packed
 
@@ -14,16 +15,6 @@ pytestmark = pytest.mark.gpu
 
 TENSORS = ("input_ids", "position_ids", "segment_ids", "cu_seqlens")
 COUNTS = ("n_rows", "n_used", "n_left", "n_segments", "max_seqlen")
-
-
-def to_host(view, shape, dtype):
-    """A DeviceView as a numpy array (an empty tensor has nothing behind its pointer to look at)."""
-    import torch
-    if view is None:
-        return None
-    if 0 in shape:
-        return np.zeros(shape, dtype)
-    return torch.as_tensor(view, device="cuda").cpu().numpy().view(dtype).reshape(shape)
 
 
 def fetch(res):
@@ -38,23 +29,7 @@ def fetch(res):
 
 
 def assert_same(got, exp, what=""):
-    for k in COUNTS:
-        assert got[k] == exp[k], (what, k, got[k], exp[k])
-    for k in TENSORS:
-        assert (got[k] is None) == (exp[k] is None), (what, k)
-        if exp[k] is None:
-            continue
-        assert got[k].shape == exp[k].shape and got[k].dtype == exp[k].dtype, (what, k, got[k].shape, exp[k].shape, got[k].dtype)
-        bad = np.argwhere(got[k] != exp[k])
-        assert len(bad) == 0, (what, k, "first differing element", bad[0].tolist(), int(got[k][tuple(bad[0])]), int(exp[k][tuple(bad[0])]))
-
-
-def on_device(ids, oo):
-    import torch
-    ids = np.ascontiguousarray(ids, np.uint32).view(np.int32)
-    d_ids = torch.from_numpy(ids if len(ids) else np.zeros(1, np.int32)).cuda()
-    d_oo = torch.from_numpy(np.asarray(oo, np.int64)).cuda()
-    return d_ids, d_oo
+    helpers.assert_same(got, exp, what, COUNTS, TENSORS)
 
 
 def packed_of(eng, d_ids, d_oo, n_ids, seq_len, pad_id, flags):

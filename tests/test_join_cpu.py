@@ -183,7 +183,7 @@ def test_invariants_on_random_input():
 
 def test_wave_search_handles_ties():
     """The join kernel searches the parts' output starts, which repeat where a part has neither a control id nor text: the 64-ary
-    search (tools/seqpack_model.py restates tks_wave_count_le) returns the count of entries <= key -- one past the LAST such
+    search (tools/seqpack_model.py restates tky_wave_count_le) returns the count of entries <= key -- one past the LAST such
     entry -- on arrays with runs of equal entries, the ballot stays a prefix of the lanes, and it ends."""
     import bisect
     import seqpack_model

@@ -61,8 +61,7 @@ def main():
     eng = tk.Engine(toks, ns, bos, eos, device=0)
     stream = torch.cuda.current_stream()
     sp = stream.cuda_stream
-    out = {"tool": "tools/dense_time.py", "steps": args.steps, "warmup": args.warmup, "hbm_tbs": HBM_TBS,
-           "nontemporal_stores": os.environ.get("TK_DENSE_NT") == "1"}
+    out = {"tool": "tools/dense_time.py", "steps": args.steps, "warmup": args.warmup, "hbm_tbs": HBM_TBS}
     try:
         with open(os.path.join(ROOT, "tekken-rs_amd", "BUILD_INFO.json")) as f:
             out["build"] = json.load(f).get("git")

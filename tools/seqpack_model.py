@@ -1,9 +1,9 @@
-"""The 64-ary wave search of the packed-rows and join kernels (tks_wave_count_le, csrc/tk_wave_search.h) step for step in
+"""The 64-ary wave search of the packed-rows and join kernels (tky_wave_count_le, csrc/tk_layout.h) step for step in
 Python: the one piece of those kernels whose invariant and termination are not plain to see.  tests/test_seqpack_cpu.py checks it
 against bisect; everything else of the kernels is checked on the GPU (tests/test_gpu_seqpack.py)."""
 
 def wave_count_le(a, n, key):
-    """tks_wave_count_le: entries of the non-decreasing a[0 .. n) at or before key, 64 probes a step."""
+    """tky_wave_count_le: entries of the non-decreasing a[0 .. n) at or before key, 64 probes a step."""
     lo, hi = 0, n
     while hi > lo:
         step = (hi - lo + 63) // 64
