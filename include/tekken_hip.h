@@ -322,6 +322,62 @@ int tk_encode_batch_seqpack(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* d
                             int validate_utf8, const tk_seqpack_opts* opts, tk_seqpack* out);
 void tk_free_seqpack(tk_seqpack* out);
 
+/* ---- overlapping windows for long documents: max_length, stride, mapping (no reference equivalent: pad_id(),
+ * src/tekkenizer.rs:304, is all the reference has; HF tokenizers calls this return_overflowing_tokens with a stride and
+ * overflow_to_sample_mapping) ----
+ * A document that is longer than the model's context and must not be cut is split into windows of max_length ids that overlap by
+ * stride ids; every window carries the document's own head and tail (BOS / EOS).  Input: the ragged ids R_d = ids[oo[d] : oo[d+1]],
+ * n_d = len(R_d), d < D; options max_length T (required, > 0), stride s, multiple_of m (0 = none), pad_id, keep_head h, keep_tail t
+ * and the flags below.
+ *   1. Body capacity c = T - h - t; the step between windows is step = c - s.  c >= 1 and 0 <= s < c are required.
+ *   2. A document with n_d <= T gives ONE window: R_d as it lies (empty documents too: every document has at least one window).
+ *   3. A document with n_d > T is split.  Its body is B = R_d[h : n_d - t], b = n_d - h - t; it has w_d = 1 + ceil((b - c) / step)
+ *      windows, and window k is R_d[:h] + B[k * step : min(k * step + c, b)] + R_d[n_d - t :].  Consecutive windows share s body
+ *      ids; the last window may be shorter (it is not right-aligned, as in HF tokenizers).  The first h and last t ids are repeated
+ *      in every window (the fused entries set h = add_bos, t = add_eos).
+ *   4. Windows are numbered document by document: doc_windows (uint64, D + 1 entries) is the exclusive prefix sum of w_d, strictly
+ *      increasing, and W = doc_windows[D].
+ *   5. Row length: L = T with TK_WINDOW_FIXED, else L = min(max_d n_d, T) (0 for an empty batch or all-empty documents); then, if
+ *      m > 0, L is rounded up to a multiple of m.
+ *   6. Outputs, elements int32 or int64 with TK_WINDOW_I64: input_ids[W, L] is the window followed by pad_id (padding on the right
+ *      only); mask[W, L] (uint8, only with TK_WINDOW_MASK, else NULL) is 1 under the window; lengths[W] (uint32); window_doc[W]
+ *      (uint32) the document of every window (overflow_to_sample_mapping); window_start[W] (uint32) = min(h + k * step, n_d), the
+ *      index in R_d of the window's first body id; doc_windows as in 4; n_windows = W; n_split = the documents with w_d > 1.
+ *   7. With TK_WINDOW_SPANS, spans[W, L, 2] (uint32) holds the (start, end) byte span of the id under every element, taken from a
+ *      spans buffer with the layout of tk_token_spans_device's output (2 * n_ids uint32); a pad gets (0, 0).
+ *   8. TK_ERR_INVALID_ARG, nothing written, an earlier window result stays readable: T == 0; h + t >= T (in the fused entries
+ *      add_bos + add_eos >= T); s >= c; an unknown flag; T or the rounded L beyond 2^31 - 1; W >= 2^32; W * L > 2^36;
+ *      TK_WINDOW_SPANS without a spans buffer in the from-ids entry; n_docs == 0 with n_ids > 0; a document of 2^32 - 1 ids or more
+ *      (window_start is uint32).  A failed allocation is TK_ERR_RUNTIME.  D == 0 is valid and gives W == 0.
+ * The layout is a separate pass behind the unchanged encode pipeline (csrc/tk_window.hip): every element of every selected output is
+ * written once, pad included, in 16-byte stores where L is a multiple of 4 (element stores otherwise).  W is not known before the
+ * per-document counts have been summed: one small read (W and max_d n_d) sizes the tensor, and one wait ends the call. */
+#define TK_WINDOW_FIXED 1
+#define TK_WINDOW_I64 2
+#define TK_WINDOW_MASK 4
+#define TK_WINDOW_SPANS 8
+typedef struct tk_window_opts { uint32_t max_length, stride, multiple_of, pad_id, keep_head, keep_tail, flags; } tk_window_opts;
+typedef struct tk_window { void* input_ids; uint8_t* mask; uint32_t *lengths, *window_doc, *window_start; uint64_t* doc_windows;
+                           uint32_t* spans; uint64_t n_docs, n_windows, row_len, n_split; } tk_window;
+/* ids already on the device (encode's own outputs or the caller's; d_id_offsets: n_docs + 1 uint64, [0] = 0, non-decreasing,
+ * [n_docs] = n_ids -- NOT checked, as in tk_dense_from_ids_device: anything else is out-of-bounds indexing on the device) ->
+ * windows.  d_spans: 2 * n_ids uint32 as tk_token_spans_device returns them, NULL without TK_WINDOW_SPANS.  out's buffers are
+ * device buffers owned by the context, valid until the next window call on it, and SEPARATE from the encode, spans, dense, packed,
+ * join and decode outputs.  The work is enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_window_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                              const void* d_spans, const tk_window_opts* opts, void* hip_stream, tk_window* out);
+/* tk_encode_batch_device_ex + (with TK_WINDOW_SPANS) the spans pass + the window pass on the same stream.  keep_head / keep_tail
+ * of opts are ignored and set from add_bos / add_eos; checks: TK_CHECK_OFFSETS / TK_CHECK_UTF8 as in tk_encode_batch_device_dense;
+ * the ragged outputs (*d_ids / *d_out_offsets / *n_ids as tk_encode_batch_device) are returned as well. */
+int tk_encode_batch_device_window(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                  int add_bos, int add_eos, int checks, const tk_window_opts* opts, void* hip_stream,
+                                  void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_window* out);
+/* Host in / host out: tk_encode_batch + the window pass (batches of the one-launch small path included).  out's buffers are
+ * pinned host memory, released with tk_free_window (an unselected output is NULL). */
+int tk_encode_batch_window(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                           int validate_utf8, const tk_window_opts* opts, tk_window* out);
+void tk_free_window(tk_window* out);
+
 /* ---- chat batches: text parts joined with control ids, plus labels (no reference equivalent: the reference never makes a
  * control token out of text -- "[INST]" in the input stays plain text -- and get_control_token, src/tekkenizer.rs:331-341, only
  * hands out the id) ----

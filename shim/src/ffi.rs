@@ -90,6 +90,35 @@ pub struct TkSeqpack {
     pub n_segments: u64,
     pub max_seqlen: u64,
 }
+// overlapping windows for long documents (tk_window_opts.flags; include/tekken_hip.h has the definition)
+pub const TK_WINDOW_FIXED: u32 = 1;
+pub const TK_WINDOW_I64: u32 = 2;
+pub const TK_WINDOW_MASK: u32 = 4;
+pub const TK_WINDOW_SPANS: u32 = 8;
+#[repr(C)]
+pub struct TkWindowOpts {
+    pub max_length: u32,
+    pub stride: u32,
+    pub multiple_of: u32,
+    pub pad_id: u32,
+    pub keep_head: u32,
+    pub keep_tail: u32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkWindow {
+    pub input_ids: *mut c_void,
+    pub mask: *mut u8,
+    pub lengths: *mut u32,
+    pub window_doc: *mut u32,
+    pub window_start: *mut u32,
+    pub doc_windows: *mut u64,
+    pub spans: *mut u32,
+    pub n_docs: u64,
+    pub n_windows: u64,
+    pub row_len: u64,
+    pub n_split: u64,
+}
 // chat batches: parts joined with control ids, plus labels (include/tekken_hip.h has the definition)
 pub const TK_CHECK_PARTS: c_int = 16;
 pub const TK_JOIN_NONE: u32 = 0xFFFF_FFFF;
@@ -169,6 +198,16 @@ extern "C" {
     pub fn tk_encode_batch_seqpack(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
                                    validate_utf8: c_int, opts: *const TkSeqpackOpts, out: *mut TkSeqpack) -> c_int;
     pub fn tk_free_seqpack(out: *mut TkSeqpack);
+    // overlapping windows: documents longer than max_length split into windows that share `stride` ids (+ mask, spans, the mapping
+    // back to the documents), fused with encode, host form
+    pub fn tk_window_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                     d_spans: *const c_void, opts: *const TkWindowOpts, hip_stream: *mut c_void, out: *mut TkWindow) -> c_int;
+    pub fn tk_encode_batch_device_window(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                         add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkWindowOpts, hip_stream: *mut c_void,
+                                         d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkWindow) -> c_int;
+    pub fn tk_encode_batch_window(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                  validate_utf8: c_int, opts: *const TkWindowOpts, out: *mut TkWindow) -> c_int;
+    pub fn tk_free_window(out: *mut TkWindow);
     // chat batches: the ids of text parts joined with control ids per conversation (+ labels, part_index), fused with encode, host form
     pub fn tk_join_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_parts: u64, n_ids: u64,
                                    d_part_ctrl: *const c_void, d_part_flags: *const c_void, d_conv_offsets: *const c_void, n_convs: u64,

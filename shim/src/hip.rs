@@ -176,6 +176,36 @@ impl HipEngine {
         Ok(out)
     }
 
+    /// Overlapping windows for documents longer than the context (tk_encode_batch_window): `(input_ids [W * max_length] row-major,
+    /// attention_mask [W * max_length], lengths [W], window_doc [W], window_start [W])`.  A document of more than `max_length` ids is
+    /// split into windows whose text parts share `stride` ids, each with its own BOS / EOS; `window_doc[w]` is the document window w
+    /// came from (HF tokenizers' `overflow_to_sample_mapping`), `window_start[w]` the index of its first text id in that document.
+    pub fn encode_batch_windows(&self, docs: &[&str], add_bos: bool, add_eos: bool, max_length: u32, stride: u32, pad_id: u32)
+                                -> Result<(Vec<i32>, Vec<u8>, Vec<u32>, Vec<u32>, Vec<u32>), HipError> {
+        let (bytes, offs) = pack_docs(docs);
+        let opts = TkWindowOpts { max_length, stride, multiple_of: 0, pad_id, keep_head: 0, keep_tail: 0, flags: TK_WINDOW_FIXED | TK_WINDOW_MASK };
+        let mut w = TkWindow { input_ids: std::ptr::null_mut(), mask: std::ptr::null_mut(), lengths: std::ptr::null_mut(),
+                               window_doc: std::ptr::null_mut(), window_start: std::ptr::null_mut(), doc_windows: std::ptr::null_mut(),
+                               spans: std::ptr::null_mut(), n_docs: 0, n_windows: 0, row_len: 0, n_split: 0 };
+        let rc = unsafe {
+            tk_encode_batch_window(self.ctx, bytes.as_ptr(), offs.as_ptr(), docs.len() as u64, add_bos as c_int, add_eos as c_int, 0, &opts, &mut w)
+        };
+        if rc != TK_OK {
+            return Err(map_err(rc, unsafe { tk_last_error(self.ctx) }));
+        }
+        let (rows, n) = (w.n_windows as usize, (w.n_windows * w.row_len) as usize);
+        let out = unsafe {
+            let ids = std::slice::from_raw_parts(w.input_ids as *const i32, n).to_vec();
+            let mask = std::slice::from_raw_parts(w.mask as *const u8, n).to_vec();
+            let lengths = std::slice::from_raw_parts(w.lengths as *const u32, rows).to_vec();
+            let window_doc = std::slice::from_raw_parts(w.window_doc as *const u32, rows).to_vec();
+            let window_start = std::slice::from_raw_parts(w.window_start as *const u32, rows).to_vec();
+            tk_free_window(&mut w);
+            (ids, mask, lengths, window_doc, window_start)
+        };
+        Ok(out)
+    }
+
     /// Chat batch (tk_encode_parts_join): every part is `(control id or None, text, label the control id, label the text)`, a
     /// conversation is a slice of parts.  Returns `(ids, offsets [C + 1], labels)`: all conversations back to back, every text
     /// encoded on its own without BOS / EOS, its control id in front; `labels[i]` is the id or `ignore_index`.

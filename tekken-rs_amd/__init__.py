@@ -31,6 +31,7 @@ CHECK_OFFSETS, CHECK_UTF8 = 1, 2   # tk_encode_batch_device_ex
 SPANS_CHECK_COVER, SPANS_CHECK_BYTES = 4, 8   # the spans entries (tk_token_spans_device, tk_encode_batch_*spans)
 DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
 SEQPACK_I64, SEQPACK_POSITIONS, SEQPACK_SEGMENTS, SEQPACK_CU_SEQLENS, SEQPACK_DROP_LAST = 1, 2, 4, 8, 16   # tk_seqpack_opts.flags (the packed entries)
+WINDOW_FIXED, WINDOW_I64, WINDOW_MASK, WINDOW_SPANS = 1, 2, 4, 8   # tk_window_opts.flags (the window entries)
 CHECK_PARTS = 16   # the join entries: conv_offsets and the control ids are checked (beside CHECK_OFFSETS / CHECK_UTF8 in one word)
 JOIN_NONE = 0xFFFFFFFF   # part_ctrl: the part has no control id
 PART_LABEL_CTRL, PART_LABEL_TEXT = 1, 2   # part_flags
@@ -95,6 +96,17 @@ class _Seqpack(ctypes.Structure):
     _fields_ = [("input_ids", ctypes.c_void_p), ("position_ids", ctypes.c_void_p), ("segment_ids", ctypes.c_void_p),
                 ("cu_seqlens", ctypes.c_void_p), ("n_rows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_used", ctypes.c_uint64),
                 ("n_left", ctypes.c_uint64), ("n_segments", ctypes.c_uint64), ("max_seqlen", ctypes.c_uint64)]
+
+
+class _WindowOpts(ctypes.Structure):
+    _fields_ = [("max_length", ctypes.c_uint32), ("stride", ctypes.c_uint32), ("multiple_of", ctypes.c_uint32), ("pad_id", ctypes.c_uint32),
+                ("keep_head", ctypes.c_uint32), ("keep_tail", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class _Window(ctypes.Structure):
+    _fields_ = [("input_ids", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("window_doc", ctypes.c_void_p),
+                ("window_start", ctypes.c_void_p), ("doc_windows", ctypes.c_void_p), ("spans", ctypes.c_void_p),
+                ("n_docs", ctypes.c_uint64), ("n_windows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_split", ctypes.c_uint64)]
 
 
 class _JoinOpts(ctypes.Structure):
@@ -321,6 +333,17 @@ def lib():
         L.tk_encode_parts_join.argtypes = [vp, u8p, u64p, ctypes.c_uint64, u32p, u32p, u64p, ctypes.c_uint64, ctypes.c_int, op, jp]
         L.tk_free_join.restype = None
         L.tk_free_join.argtypes = [jp]
+    if hasattr(L, "tk_window_from_ids_device"):   # (overlapping windows: libraries built before them still load through TK_HIP_LIB)
+        op, wp = ctypes.POINTER(_WindowOpts), ctypes.POINTER(_Window)
+        L.tk_window_from_ids_device.restype = ctypes.c_int
+        L.tk_window_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, op, vp, wp]
+        L.tk_encode_batch_device_window.restype = ctypes.c_int
+        L.tk_encode_batch_device_window.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, wp]
+        L.tk_encode_batch_window.restype = ctypes.c_int
+        L.tk_encode_batch_window.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, wp]
+        L.tk_free_window.restype = None
+        L.tk_free_window.argtypes = [wp]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -435,6 +458,33 @@ class SeqpackResult:
                 DeviceView(self.position_ids_ptr, shape, self.typestr) if self.position_ids_ptr else None,
                 DeviceView(self.segment_ids_ptr, shape, self.typestr) if self.segment_ids_ptr else None,
                 DeviceView(self.cu_seqlens_ptr, self.n_segments + 1, "<i4") if self.cu_seqlens_ptr else None)
+
+
+def _window_opts(max_length, stride=0, multiple_of=0, pad_id=0, keep_head=0, keep_tail=0, flags=0):
+    return _WindowOpts(int(max_length or 0), int(stride or 0), int(multiple_of or 0), int(pad_id), int(keep_head), int(keep_tail), int(flags))
+
+
+class WindowResult:
+    """What the device window entries return (tk_window): raw device pointers of context-owned buffers, valid until the next
+    window call on the context.  input_ids_ptr: int32 or int64 [n_windows, row_len]; mask_ptr: uint8 [n_windows, row_len] or None;
+    lengths_ptr / window_doc_ptr / window_start_ptr: uint32 [n_windows] (views() shows them as int32: each is below 2^31 for every
+    batch a tensor can hold); doc_windows_ptr: uint64 [n_docs + 1]; spans_ptr: uint32 [n_windows, row_len, 2] or None."""
+
+    def __init__(self, w, flags):
+        self.input_ids_ptr, self.mask_ptr, self.spans_ptr = w.input_ids or 0, w.mask or None, w.spans or None
+        self.lengths_ptr, self.window_doc_ptr, self.window_start_ptr = w.lengths or 0, w.window_doc or 0, w.window_start or 0
+        self.doc_windows_ptr = w.doc_windows or 0
+        self.n_docs, self.n_windows, self.row_len, self.n_split = int(w.n_docs), int(w.n_windows), int(w.row_len), int(w.n_split)
+        self.typestr = "<i8" if flags & WINDOW_I64 else "<i4"
+
+    def views(self):
+        """(input_ids [n_windows, row_len], mask or None, lengths, window_doc, window_start as int32 [n_windows], doc_windows as
+        int64 [n_docs + 1], spans as int32 [n_windows, row_len, 2] or None) -- DeviceView objects."""
+        W, shape = self.n_windows, (self.n_windows, self.row_len)
+        return (DeviceView(self.input_ids_ptr, shape, self.typestr), DeviceView(self.mask_ptr, shape, "|u1") if self.mask_ptr else None,
+                DeviceView(self.lengths_ptr, W, "<i4"), DeviceView(self.window_doc_ptr, W, "<i4"), DeviceView(self.window_start_ptr, W, "<i4"),
+                DeviceView(self.doc_windows_ptr, self.n_docs + 1, "<i8"),
+                DeviceView(self.spans_ptr, shape + (2,), "<i4") if self.spans_ptr else None)
 
 
 class JoinResult:
@@ -729,6 +779,50 @@ class Engine:
                "max_seqlen": int(p.max_seqlen), "n_rows": R, "n_used": int(p.n_used), "n_left": int(p.n_left),
                "n_segments": int(p.n_segments)}
         lib().tk_free_seqpack(ctypes.byref(p))
+        return out
+
+    def window_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, max_length, stride=0, multiple_of=0, pad_id=0, keep_head=0,
+                               keep_tail=0, flags=0, d_spans_ptr=0, stream=0):
+        """tk_window_from_ids_device: ragged ids resident in HBM -> overlapping windows [n_windows, row_len] (+ mask with
+        WINDOW_MASK, spans with WINDOW_SPANS from d_spans_ptr, lengths, window_doc, window_start, doc_windows); the definition is
+        in include/tekken_hip.h.  Returns a WindowResult (context-owned device buffers, apart from every other output)."""
+        o, w = _window_opts(max_length, stride, multiple_of, pad_id, keep_head, keep_tail, flags), _Window()
+        self._call("tk_window_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                   ctypes.c_void_p(d_spans_ptr or None), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(w))
+        return WindowResult(w, int(flags))
+
+    def encode_batch_device_window(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, max_length, stride=0, add_bos=True, add_eos=True,
+                                   multiple_of=0, pad_id=0, flags=0, checks=0, stream=0):
+        """tk_encode_batch_device_window: encode_batch_device (+ the spans pass with WINDOW_SPANS) + the window pass on the same
+        stream; every window repeats BOS / EOS.  Returns (d_ids_ptr, d_out_offs_ptr, n_ids, WindowResult), all context-owned."""
+        o, w = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags), _Window()
+        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        self._call("tk_encode_batch_device_window", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(w))
+        return d_ids.value, d_oo.value, int(n.value), WindowResult(w, int(flags))
+
+    def encode_batch_window(self, data, offs, max_length, stride=0, add_bos=True, add_eos=True, validate_utf8=False, multiple_of=0,
+                            pad_id=0, flags=0):
+        """tk_encode_batch_window, host in / host out: a dict of numpy arrays (input_ids int32 or int64 [n_windows, row_len], mask
+        uint8 or None, lengths / window_doc / window_start uint32 [n_windows], doc_windows uint64 [n_docs + 1], spans uint32
+        [n_windows, row_len, 2] or None) and the counts n_windows, n_split."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        o, w = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags), _Window()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        self._call("tk_encode_batch_window", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(w))
+        W, L = int(w.n_windows), int(w.row_len)
+        dt = np.int64 if flags & WINDOW_I64 else np.int32
+
+        out = {"input_ids": _take(w.input_ids, W * L, dt).reshape(W, L),
+               "mask": _take(w.mask, W * L, np.uint8).reshape(W, L) if w.mask else None,
+               "lengths": _take(w.lengths, W, np.uint32), "window_doc": _take(w.window_doc, W, np.uint32),
+               "window_start": _take(w.window_start, W, np.uint32), "doc_windows": _take(w.doc_windows, int(w.n_docs) + 1, np.uint64),
+               "spans": _take(w.spans, W * L * 2, np.uint32).reshape(W, L, 2) if w.spans else None,
+               "n_windows": W, "n_split": int(w.n_split)}
+        lib().tk_free_window(ctypes.byref(w))
         return out
 
     def join_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, d_part_ctrl_ptr, d_part_flags_ptr, d_conv_offs_ptr, n_convs,
@@ -1158,6 +1252,53 @@ class Tekkenizer:
                 "segment_ids": _torch_wrap(v_seg, shape, tdt, copy),
                 "cu_seqlens": _torch_wrap(v_cu, (res.n_segments + 1,), torch.int32, copy), "max_seqlen": res.max_seqlen, "n_rows": res.n_rows,
                 "n_used": res.n_used, "n_left": res.n_left, "n_segments": res.n_segments}
+
+    def encode_batch_windows(self, docs, max_length, stride=0, add_bos=False, add_eos=False, padding="max_length", pad_to_multiple_of=None,
+                             pad_id=None, dtype="int64", return_attention_mask=True, return_offsets_mapping=False, return_tensors="pt",
+                             copy=True):
+        """Overlapping windows for documents longer than the context (tk_encode_batch_device_window / tk_encode_batch_window; the
+        definition is in include/tekken_hip.h): a document of more than max_length ids is split into windows whose text parts
+        overlap by `stride` ids, each with its own BOS / EOS; a shorter one is one window.
+        {"input_ids": [W, L] of `dtype` ("int64" | "int32"), "attention_mask": uint8 [W, L] or None, "lengths": int32 [W],
+        "overflow_to_sample_mapping": int32 [W] the document of every window, "window_start": int32 [W] the index in the document's
+        ids of the window's first text id, "doc_windows": int64 [D + 1] the first window of every document, "offset_mapping":
+        int32 [W, L, 2] the (start, end) byte span under every element ((0, 0) under a pad) or None, "n_windows", "n_split": int}.
+        padding "max_length": L = max_length, "longest": L = min(the longest document, max_length); then rounded up to
+        pad_to_multiple_of.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on the tokenizer's GPU (copy=False:
+        views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
+        eng = self._device_engine()
+        if padding not in ("longest", "max_length") or dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_windows: unknown padding / dtype / return_tensors value")
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        if not (0 <= int(max_length) < 2 ** 32 and 0 <= int(stride) < 2 ** 32):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_windows: max_length %r, stride %r" % (max_length, stride))
+        flags = (WINDOW_FIXED if padding == "max_length" else 0) | (WINDOW_I64 if dtype == "int64" else 0) \
+            | (WINDOW_MASK if return_attention_mask else 0) | (WINDOW_SPANS if return_offsets_mapping else 0)
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        if return_tensors == "np":
+            r = eng.encode_batch_window(data, offs, max_length, stride, add_bos, add_eos, False, pad_to_multiple_of, pad, flags)
+            return {"input_ids": r["input_ids"], "attention_mask": r["mask"], "lengths": r["lengths"].astype(np.int32),
+                    "overflow_to_sample_mapping": r["window_doc"].astype(np.int32), "window_start": r["window_start"].astype(np.int32),
+                    "doc_windows": r["doc_windows"].astype(np.int64),
+                    "offset_mapping": r["spans"].astype(np.int32) if r["spans"] is not None else None,
+                    "n_windows": r["n_windows"], "n_split": r["n_split"]}
+        import torch
+        d_bytes, d_offs, stream = _upload(data, offs)
+        _, _, _, res = eng.encode_batch_device_window(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), max_length, stride,
+                                                      add_bos, add_eos, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
+        W, L = res.n_windows, res.row_len
+        tdt = torch.int64 if dtype == "int64" else torch.int32
+        v_ids, v_mask, v_len, v_doc, v_start, v_dw, v_sp = res.views()
+        return {"input_ids": _torch_wrap(v_ids, (W, L), tdt, copy), "attention_mask": _torch_wrap(v_mask, (W, L), torch.uint8, copy),
+                "lengths": _torch_wrap(v_len, (W,), torch.int32, copy),
+                "overflow_to_sample_mapping": _torch_wrap(v_doc, (W,), torch.int32, copy),
+                "window_start": _torch_wrap(v_start, (W,), torch.int32, copy),
+                "doc_windows": _torch_wrap(v_dw, (res.n_docs + 1,), torch.int64, copy),
+                "offset_mapping": _torch_wrap(v_sp, (W, L, 2), torch.int32, copy), "n_windows": W, "n_split": res.n_split}
 
     CHAT_ROLES = {"user": ("[INST]", "[/INST]", False), "system": ("[SYSTEM_PROMPT]", "[/SYSTEM_PROMPT]", False),
                   "assistant": (None, "</s>", True)}

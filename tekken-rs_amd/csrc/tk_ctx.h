@@ -116,6 +116,10 @@ struct tk_ctx {
     // words; the work arrays (has-a-control-id and its scan, the parts' output starts and local indices, the scan workspace); the
     // host entry's copies of part_ctrl / part_flags / conv_offsets.  Apart from every other buffer, allocated at the first join call
     DevBuf jn_ids, jn_offs, jn_labels, jn_pidx, jn_stat, jn_has, jn_cb, jn_start, jn_plocal, jn_bsum, jn_in_ctrl, jn_in_flags, jn_in_conv;
+    // the overlapping windows (tk_window.hip): the tensor, its mask and spans, the per-window arrays, doc_windows; the work arrays
+    // (w_d, the scan that becomes doc_windows once the call is accepted, the scan workspace, the statistics words).  Apart from
+    // every other buffer, allocated at the first window call
+    DevBuf wn_ids, wn_mask, wn_spans, wn_len, wn_doc, wn_start, wn_dw, wn_dw_next, wn_cnt, wn_bsum, wn_stat;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -191,7 +195,7 @@ int enter_device(tk_ctx* c, uint64_t n_docs);
 struct CopyOut { const void* dev; size_t bytes; void* host; bool selected = true; };
 int pinned_blocks(tk_ctx* c, CopyOut* a, int n);
 int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what);
-// ---- what the layout passes share (tk_capi_dense / _seqpack / _join.cpp) ----
+// ---- what the layout passes share (tk_capi_dense / _seqpack / _join / _window.cpp) ----
 #define TK_LAYOUT_MAX_ROW 0x7FFFFFFFull         /* a row of a tensor stays below 2^31 elements */
 #define TK_LAYOUT_MAX_ELEMS (1ull << 36)        /* rows * row length: 256 GiB of int32, more than the part holds */
 // how an entry with check flags opens: an unknown flag is refused first, then a null argument
@@ -228,6 +232,9 @@ template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // .
     a.tok_inline = (const uint8_t*)c->t_inline.p; a.tok_len8 = (const uint8_t*)c->t_len8.p;
     a.n_ranks = c->host.n_ranks; a.num_special = c->host.num_special;
 }
+// tk_capi_spans.cpp: the spans pass over ids on the device into c->sp_spans, with the TK_SPANS_CHECK_* of `checks`
+int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const uint64_t* d_doc_offs,
+              const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc);
 // tk_capi_spans.cpp: the document whose id range holds id index idx (error paths)
 int doc_of_id(tk_ctx* c, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t idx, uint64_t* out);
 #pragma GCC visibility pop

@@ -171,6 +171,30 @@ hipError_t tk_launch_seqpack_starts(const TkSeqpackArgs& a, hipStream_t s);   //
 hipError_t tk_launch_seqpack(const TkSeqpackArgs& a, int i64, hipStream_t s); // the tensors; n_rows == 0: nothing is launched
 hipError_t tk_launch_seqpack_cu(const TkSeqpackArgs& a, hipStream_t s);       // cu_seqlens (a.cu != NULL), n_segments, max_seqlen
 
+// ---- overlapping windows for long documents (tk_window.hip) ----
+struct TkWindowArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const uint64_t* id_offs;   // [n_docs + 1]
+    const uint32_t* in_spans;  // [2 * n_ids] (start, end) per id, or NULL
+    uint64_t n_docs;
+    uint32_t max_len, step;    // T; c - s
+    uint32_t keep_head, keep_tail, pad_id;
+    uint32_t row_len;          // L (< 2^31; 0: only the per-row outputs are written)
+    uint64_t n_rows;           // W (< 2^32)
+    uint32_t* counts;          // [n_docs] w_d
+    const uint64_t* doc_windows;   // [n_docs + 1] exclusive scan of counts, strictly increasing
+    void* out;                 // [W * L] int32 or int64
+    uint8_t* mask;             // [W * L] or NULL
+    uint32_t* out_spans;       // [W * L * 2] or NULL
+    uint32_t* lengths;         // [W]
+    uint32_t* window_doc;      // [W]
+    uint32_t* window_start;    // [W]
+    unsigned long long* stat;  // [0] longest document, clamped to 2^32 - 1 (atomicMax), [1] += documents with w_d > 1: zeroed by the caller
+    uint32_t units, rb, magic; // the launch shape (set by the launcher): units a row, rows a block, 2^32 / units rounded up
+};
+hipError_t tk_launch_window_counts(const TkWindowArgs& a, hipStream_t s);   // counts, stat
+hipError_t tk_launch_window(const TkWindowArgs& a, int i64, hipStream_t s); // the outputs; n_rows == 0: nothing is launched
+
 // ---- chat batches: parts joined with control ids, plus labels (tk_join.hip) ----
 struct TkJoinArgs {
     const uint32_t* ids;       // [n_ids] packed token ids of all parts, encoded without BOS / EOS
