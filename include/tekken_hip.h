@@ -177,7 +177,8 @@ int tk_encode_batch_device_ex(tk_ctx* ctx, const void* d_bytes, const void* d_do
  *   - A document of 2^32 bytes or more makes the spans entries fail with TK_ERR_INVALID_ARG.  The encode entries are not
  *     affected.
  *   - Offsets are in BYTES, not characters: a token can end inside a UTF-8 character (the byte-fallback tokens of an emoji or a
- *     rare CJK character do).  Character offsets are not provided.
+ *     rare CJK character do).  Code-point and UTF-16 offsets come from the units entries below (tk_token_spans_units_device),
+ *     the tokens an annotated range covers from tk_spans_locate_device.
  * Encode is lossless (byte-level BPE tiles the text; the only specials it emits are BOS / EOS), so the spans of encode's ids
  * are a per-document exclusive prefix sum of the ids' byte lengths (a special id: 0) -- a separate pass behind the encode
  * pipeline (csrc/tk_spans.hip), which can check the ids against the text in the same pass.  `checks` is a bit field that sits
@@ -209,6 +210,54 @@ int tk_encode_batch_device_spans(tk_ctx* ctx, const void* d_bytes, const void* d
 int tk_encode_batch_spans(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
                           int add_eos, int validate_utf8, int checks, tk_result* out, uint32_t** spans, uint64_t* bad_doc);
 void tk_free_spans(uint32_t* spans);
+
+/* ---- spans in code points or UTF-16 units, and annotation -> token range (HF's offset_mapping over a str, char_to_token; no
+ * reference equivalent) ----
+ * The unit a caller's strings are indexed in: a Python str by code point, a JavaScript / Java / LSP string by UTF-16 unit.  The
+ * definition is by BYTES, so it holds for any input, valid UTF-8 or not.
+ *   - A document's text T is the concatenation of the token bytes of its non-special ids (for encode's output: the document).
+ *   - The weight of a byte b is u(b) = ((b & 0xC0) != 0x80); TK_UNIT_UTF16 adds 1 more when b >= 0xF0; TK_UNIT_BYTE: u = 1.
+ *   - U(p) = the sum of u(T[q]) over q < p.
+ *   - lead(p) = the largest q <= p with (T[q] & 0xC0) != 0x80, or 0 if there is none; TK_UNIT_BYTE: lead(p) = p.
+ * The unit span of an id with byte span (s, e):
+ *   - s == e (a special id): (U(s), U(s)).
+ *   - otherwise (U(lead(s)), U(e)): a token that begins or ends inside a character is widened to that whole character.  The four
+ *     byte-fallback tokens of an emoji at character c are all (c, c + 1) in code points and (c, c + 2) in UTF-16 units.
+ *   - Nothing carries across a document boundary: a document that begins with continuation bytes has lead = 0 there.
+ * Starts and ends are non-decreasing along a document.  A document of 2^32 units or more is TK_ERR_INVALID_ARG, an id outside
+ * the vocabulary TK_ERR_RUNTIME, as in the byte pass.  The pass reads no text: a per-rank table and two wave scans
+ * (csrc/tk_spans_units.hip). */
+#define TK_UNIT_BYTE 0
+#define TK_UNIT_CHAR 1    /* Unicode code points: the index of a Python str */
+#define TK_UNIT_UTF16 2   /* UTF-16 code units */
+/* Unit spans of ids already on the device (any ids).  *d_spans (2 * n_ids uint32) is a device buffer owned by the context, valid
+ * until the next units call on it, and a buffer of its OWN: the byte spans of an earlier tk_token_spans_device call and every
+ * encode output stay valid through this call.  TK_UNIT_BYTE gives what tk_token_spans_device gives.  An unknown unit is
+ * TK_ERR_INVALID_ARG.  The work is enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_token_spans_units_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids, int unit,
+                                void* hip_stream, void** d_spans);
+/* tk_encode_batch_device_ex + the units pass on the same stream.  checks takes TK_CHECK_OFFSETS / TK_CHECK_UTF8 only: a
+ * TK_SPANS_CHECK_* bit is TK_ERR_INVALID_ARG (those checks belong to the byte pass, which the caller can run as well). */
+int tk_encode_batch_device_spans_units(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                       int add_bos, int add_eos, int checks, int unit, void* hip_stream, void** d_ids,
+                                       void** d_out_offsets, void** d_spans, uint64_t* n_ids);
+/* Host in / host out: tk_encode_batch + the units pass (batches of the one-launch small path included).  *spans is pinned,
+ * 2 * n_ids entries, free with tk_free_spans; out as tk_encode_batch (tk_free_result). */
+int tk_encode_batch_spans_units(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
+                                int add_eos, int validate_utf8, int unit, tk_result* out, uint32_t** spans);
+/* Which ids does an annotated range cover?  d_spans: 2 * n_ids uint32 spans in any unit whose starts and ends are non-decreasing
+ * along a document (the byte or the units pass); d_ann_doc: uint32[n_ann], the document of every annotation; d_ann: uint32[n_ann, 2],
+ * (as, ae) in the unit of d_spans.  With (S_i, E_i) the spans of document d:
+ *     lo = #{i : E_i <= as},  hi = #{i : S_i < ae},  d_tok_range[a] = (lo, max(lo, hi))
+ * -- a pair of document-relative id indices (uint32[n_ann, 2], owned by the context, valid until the next locate call on it, apart
+ * from every other output).  For encode's output the ids whose span overlaps [as, ae) are exactly lo .. hi - 1; HF's
+ * char_to_token(c) is the annotation (c, c + 1); BOS and EOS are never inside a non-empty range.  One lane per annotation, two
+ * binary searches; every probe stays inside [id_offsets[d], id_offsets[d + 1]), whatever the spans hold.
+ * ann_doc >= n_docs or as > ae is TK_ERR_INVALID_ARG: the first such annotation is written to *bad_ann (optional), nothing else is
+ * checked, and the result of an earlier call stays readable.  n_ann == 0 and documents without ids are valid. */
+int tk_spans_locate_device(tk_ctx* ctx, const void* d_spans, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                           const void* d_ann_doc, const void* d_ann, uint64_t n_ann, void* hip_stream, void** d_tok_range,
+                           uint64_t* bad_ann);
 
 /* ---- model-ready dense batches: truncation, padding, mask, and back (no reference equivalent: pad_id(), src/tekkenizer.rs:304,
  * is all the reference has) ----

@@ -40,6 +40,10 @@ pub const TK_ERR_SPECIAL_POLICY: c_int = -10;
 // the checks of the spans entries (above TK_CHECK_OFFSETS = 1 / TK_CHECK_UTF8 = 2: one word can carry all four)
 pub const TK_SPANS_CHECK_COVER: c_int = 4;
 pub const TK_SPANS_CHECK_BYTES: c_int = 8;
+// the unit of the units entries' spans
+pub const TK_UNIT_BYTE: c_int = 0;
+pub const TK_UNIT_CHAR: c_int = 1;
+pub const TK_UNIT_UTF16: c_int = 2;
 
 // model-ready dense batches (tk_dense_opts.flags; include/tekken_hip.h has the definition)
 pub const TK_DENSE_PAD_LEFT: u32 = 1;
@@ -173,6 +177,19 @@ extern "C" {
     pub fn tk_encode_batch_spans(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
                                  validate_utf8: c_int, checks: c_int, out: *mut TkResult, spans: *mut *mut u32, bad_doc: *mut u64) -> c_int;
     pub fn tk_free_spans(spans: *mut u32);
+    // the same spans in code points or UTF-16 units (unit: TK_UNIT_*), in a context-owned buffer of their own
+    pub fn tk_token_spans_units_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                       unit: c_int, hip_stream: *mut c_void, d_spans: *mut *mut c_void) -> c_int;
+    pub fn tk_encode_batch_device_spans_units(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                              add_bos: c_int, add_eos: c_int, checks: c_int, unit: c_int, hip_stream: *mut c_void,
+                                              d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, d_spans: *mut *mut c_void,
+                                              n_ids: *mut u64) -> c_int;
+    pub fn tk_encode_batch_spans_units(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                       validate_utf8: c_int, unit: c_int, out: *mut TkResult, spans: *mut *mut u32) -> c_int;
+    // annotation (as, ae) of document ann_doc -> the document-relative id range (lo, hi) its span covers
+    pub fn tk_spans_locate_device(ctx: *mut TkCtx, d_spans: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                  d_ann_doc: *const c_void, d_ann: *const c_void, n_ann: u64, hip_stream: *mut c_void,
+                                  d_tok_range: *mut *mut c_void, bad_ann: *mut u64) -> c_int;
     // tokenizer level, one string: Tekkenizer::encode + offsets (*ids and *spans malloc'ed, both freed with tk_free_ids)
     pub fn tk_tokenizer_encode_with_spans(t: *mut TkTokenizer, text: *const c_char, len: usize, add_bos: c_int, add_eos: c_int,
                                           ids: *mut *mut u32, spans: *mut *mut u32, n_ids: *mut usize) -> c_int;

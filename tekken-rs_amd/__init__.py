@@ -29,6 +29,8 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 TK_OK = 0
 CHECK_OFFSETS, CHECK_UTF8 = 1, 2   # tk_encode_batch_device_ex
 SPANS_CHECK_COVER, SPANS_CHECK_BYTES = 4, 8   # the spans entries (tk_token_spans_device, tk_encode_batch_*spans)
+UNIT_BYTE, UNIT_CHAR, UNIT_UTF16 = 0, 1, 2   # the unit of the units entries' spans (tk_token_spans_units_device)
+_UNITS = {"byte": UNIT_BYTE, "char": UNIT_CHAR, "utf16": UNIT_UTF16}   # the offsets_unit keyword of the Tekkenizer methods
 DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
 SEQPACK_I64, SEQPACK_POSITIONS, SEQPACK_SEGMENTS, SEQPACK_CU_SEQLENS, SEQPACK_DROP_LAST = 1, 2, 4, 8, 16   # tk_seqpack_opts.flags (the packed entries)
 WINDOW_FIXED, WINDOW_I64, WINDOW_MASK, WINDOW_SPANS = 1, 2, 4, 8   # tk_window_opts.flags (the window entries)
@@ -298,6 +300,17 @@ def lib():
         L.tk_tokenizer_encode_with_spans.restype = ctypes.c_int
         L.tk_tokenizer_encode_with_spans.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(u32p),
                                                      ctypes.POINTER(u32p), ctypes.POINTER(ctypes.c_size_t)]
+    if hasattr(L, "tk_token_spans_units_device"):   # (spans in code points / UTF-16 units, annotation -> token range)
+        L.tk_token_spans_units_device.restype = ctypes.c_int
+        L.tk_token_spans_units_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, ctypes.POINTER(vp)]
+        L.tk_encode_batch_device_spans_units.restype = ctypes.c_int
+        L.tk_encode_batch_device_spans_units.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), u64p]
+        L.tk_encode_batch_spans_units.restype = ctypes.c_int
+        L.tk_encode_batch_spans_units.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.POINTER(_Result), ctypes.POINTER(u32p)]
+        L.tk_spans_locate_device.restype = ctypes.c_int
+        L.tk_spans_locate_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp, ctypes.POINTER(vp), u64p]
     if hasattr(L, "tk_dense_from_ids_device"):   # (dense batches: libraries built before them still load through TK_HIP_LIB)
         op, dp = ctypes.POINTER(_DenseOpts), ctypes.POINTER(_Dense)
         L.tk_dense_from_ids_device.restype = ctypes.c_int
@@ -697,6 +710,55 @@ class Engine:
             e.bad_doc = int(bad.value)
             raise e
         return d_ids.value, d_oo.value, d_sp.value, int(n.value)
+
+    def token_spans_units_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, unit=UNIT_CHAR, stream=0):
+        """tk_token_spans_units_device: spans of ids resident in HBM in `unit` (UNIT_BYTE | UNIT_CHAR | UNIT_UTF16; the definition is
+        in include/tekken_hip.h).  Returns the context-owned d_spans pointer (uint32[2 * n_ids]), a buffer apart from the byte
+        spans and every encode output."""
+        d_sp = ctypes.c_void_p()
+        self._call("tk_token_spans_units_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                   int(unit), ctypes.c_void_p(stream), ctypes.byref(d_sp))
+        return d_sp.value
+
+    def encode_batch_device_spans_units(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, unit=UNIT_CHAR,
+                                        checks=0, stream=0):
+        """tk_encode_batch_device_spans_units: encode_batch_device + the units pass.  checks: CHECK_OFFSETS | CHECK_UTF8 only.
+        Returns (d_ids_ptr, d_out_offs_ptr, d_spans_ptr, n_ids), context-owned."""
+        d_ids, d_oo, d_sp, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        self._call("tk_encode_batch_device_spans_units", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                   int(add_bos), int(add_eos), int(checks), int(unit), ctypes.c_void_p(stream), ctypes.byref(d_ids), ctypes.byref(d_oo),
+                   ctypes.byref(d_sp), ctypes.byref(n))
+        return d_ids.value, d_oo.value, d_sp.value, int(n.value)
+
+    def encode_batch_spans_units(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, unit=UNIT_CHAR):
+        """tk_encode_batch_spans_units: (ids uint32[T], out_offsets uint64[D+1], spans uint32[T, 2]) -- spans[i] = (start, end) of
+        id i in `unit`, relative to the start of its document (include/tekken_hip.h)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        res = _Result()
+        sp = ctypes.POINTER(ctypes.c_uint32)()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        self._call("tk_encode_batch_spans_units", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                   int(add_eos), int(validate_utf8), int(unit), ctypes.byref(res), ctypes.byref(sp))
+        n = int(res.n_ids)
+        spans = np.ctypeslib.as_array(sp, shape=(max(2 * n, 1),))[:2 * n].copy().reshape(n, 2)
+        lib().tk_free_spans(sp)
+        ids, oo = _take_result(res)
+        return ids, oo, spans
+
+    def spans_locate_device(self, d_spans_ptr, d_id_offs_ptr, n_docs, n_ids, d_ann_doc_ptr, d_ann_ptr, n_ann, stream=0):
+        """tk_spans_locate_device: for every annotation (as, ae) of document ann_doc, in the unit of the spans, the
+        document-relative id range (lo, hi) whose spans overlap it.  Returns the context-owned d_tok_range pointer (uint32[n_ann, 2]);
+        a bad annotation raises TokenizerError with .bad_ann set."""
+        d_out, bad = ctypes.c_void_p(), ctypes.c_uint64(0)
+        rc = _need("tk_spans_locate_device")(self._h, ctypes.c_void_p(d_spans_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                                             ctypes.c_void_p(d_ann_doc_ptr or None), ctypes.c_void_p(d_ann_ptr or None), n_ann,
+                                             ctypes.c_void_p(stream), ctypes.byref(d_out), ctypes.byref(bad))
+        if rc != TK_OK:
+            e = self._err(rc)
+            e.bad_ann = int(bad.value)
+            raise e
+        return d_out.value
 
     def dense_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, max_length=0, multiple_of=0, pad_id=0, keep_head=0,
                               keep_tail=0, flags=0, stream=0):
@@ -1143,9 +1205,19 @@ class Tekkenizer:
         lib().tk_free_ids(ids)
         return out
 
-    def encode_with_offsets(self, text, add_bos=False, add_eos=False):
-        """Tekkenizer::encode + the byte span of every id: (ids, [(start, end), ...]) -- offsets in BYTES of the UTF-8 text
-        (a byte-fallback token can end inside a character; BOS / EOS get zero-length spans at 0 / len)."""
+    def _unit(self, offsets_unit):
+        if offsets_unit not in _UNITS:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "offsets_unit %r is none of 'byte', 'char', 'utf16'" % (offsets_unit,))
+        return _UNITS[offsets_unit]
+
+    def encode_with_offsets(self, text, add_bos=False, add_eos=False, offsets_unit="byte"):
+        """Tekkenizer::encode + the span of every id: (ids, [(start, end), ...]).  offsets_unit "byte": offsets in BYTES of the
+        UTF-8 text (a byte-fallback token can end inside a character; BOS / EOS get zero-length spans at 0 / len); "char": code
+        points, the indices of a Python str; "utf16": UTF-16 units.  In the last two a token that begins or ends inside a
+        character covers that whole character (the definition is in include/tekken_hip.h), and the spans come from the units pass
+        on the tokenizer's GPU."""
+        if self._unit(offsets_unit) != UNIT_BYTE:
+            return self.encode_batch_with_offsets([text], add_bos, add_eos, offsets_unit=offsets_unit)[0]
         raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
         ids = ctypes.POINTER(ctypes.c_uint32)()
         sp = ctypes.POINTER(ctypes.c_uint32)()
@@ -1160,17 +1232,24 @@ class Tekkenizer:
         lib().tk_free_ids(sp)
         return out, spans
 
-    def encode_batch_with_offsets(self, docs, add_bos=False, add_eos=False, checks=0):
-        """Batch form on the tokenizer's engine context (tk_encode_batch_spans): [(ids, [(start, end), ...]) per document]."""
+    def encode_batch_with_offsets(self, docs, add_bos=False, add_eos=False, checks=0, offsets_unit="byte"):
+        """Batch form on the tokenizer's engine context (tk_encode_batch_spans; with offsets_unit "char" / "utf16"
+        tk_encode_batch_spans_units, which takes no SPANS_CHECK_*): [(ids, [(start, end), ...]) per document]."""
         eng = self.engine()
         if eng is None:
             raise TokenizerError(TK_ERR_NO_DEVICE, "tokenizer was created without a device (host-only object)")
+        unit = self._unit(offsets_unit)
+        if unit != UNIT_BYTE and checks:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_with_offsets: the spans checks belong to the byte pass (offsets_unit='byte')")
         if add_bos:
             self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
         if add_eos:
             self.eos_id()
         data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
-        ids, oo, spans = eng.encode_batch_spans(data, offs, add_bos, add_eos, checks=checks)
+        if unit != UNIT_BYTE:
+            ids, oo, spans = eng.encode_batch_spans_units(data, offs, add_bos, add_eos, unit=unit)
+        else:
+            ids, oo, spans = eng.encode_batch_spans(data, offs, add_bos, add_eos, checks=checks)
         return [(ids[int(oo[d]):int(oo[d + 1])].tolist(), [tuple(x) for x in spans[int(oo[d]):int(oo[d + 1])].tolist()])
                 for d in range(len(docs))]
 
@@ -1255,18 +1334,21 @@ class Tekkenizer:
 
     def encode_batch_windows(self, docs, max_length, stride=0, add_bos=False, add_eos=False, padding="max_length", pad_to_multiple_of=None,
                              pad_id=None, dtype="int64", return_attention_mask=True, return_offsets_mapping=False, return_tensors="pt",
-                             copy=True):
+                             copy=True, offsets_unit="byte"):
         """Overlapping windows for documents longer than the context (tk_encode_batch_device_window / tk_encode_batch_window; the
         definition is in include/tekken_hip.h): a document of more than max_length ids is split into windows whose text parts
         overlap by `stride` ids, each with its own BOS / EOS; a shorter one is one window.
         {"input_ids": [W, L] of `dtype` ("int64" | "int32"), "attention_mask": uint8 [W, L] or None, "lengths": int32 [W],
         "overflow_to_sample_mapping": int32 [W] the document of every window, "window_start": int32 [W] the index in the document's
         ids of the window's first text id, "doc_windows": int64 [D + 1] the first window of every document, "offset_mapping":
-        int32 [W, L, 2] the (start, end) byte span under every element ((0, 0) under a pad) or None, "n_windows", "n_split": int}.
+        int32 [W, L, 2] the (start, end) span under every element ((0, 0) under a pad) or None -- in bytes, or with offsets_unit
+        "char" / "utf16" in code points / UTF-16 units (encode, the units pass and the window pass over its spans) --, "n_windows",
+        "n_split": int}.
         padding "max_length": L = max_length, "longest": L = min(the longest document, max_length); then rounded up to
         pad_to_multiple_of.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on the tokenizer's GPU (copy=False:
         views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
         eng = self._device_engine()
+        unit = self._unit(offsets_unit)
         if padding not in ("longest", "max_length") or dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
             raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_windows: unknown padding / dtype / return_tensors value")
         if add_bos:
@@ -1279,7 +1361,8 @@ class Tekkenizer:
         flags = (WINDOW_FIXED if padding == "max_length" else 0) | (WINDOW_I64 if dtype == "int64" else 0) \
             | (WINDOW_MASK if return_attention_mask else 0) | (WINDOW_SPANS if return_offsets_mapping else 0)
         data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
-        if return_tensors == "np":
+        in_units = unit != UNIT_BYTE and return_offsets_mapping
+        if return_tensors == "np" and not in_units:
             r = eng.encode_batch_window(data, offs, max_length, stride, add_bos, add_eos, False, pad_to_multiple_of, pad, flags)
             return {"input_ids": r["input_ids"], "attention_mask": r["mask"], "lengths": r["lengths"].astype(np.int32),
                     "overflow_to_sample_mapping": r["window_doc"].astype(np.int32), "window_start": r["window_start"].astype(np.int32),
@@ -1288,17 +1371,70 @@ class Tekkenizer:
                     "n_windows": r["n_windows"], "n_split": r["n_split"]}
         import torch
         d_bytes, d_offs, stream = _upload(data, offs)
-        _, _, _, res = eng.encode_batch_device_window(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), max_length, stride,
-                                                      add_bos, add_eos, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
+        if in_units:
+            # three calls on the stream: encode, the units pass, the window pass over the unit spans (every window repeats BOS / EOS)
+            p_ids, p_oo, p_sp, n = eng.encode_batch_device_spans_units(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos,
+                                                                       add_eos, unit, CHECK_OFFSETS, stream)
+            res = eng.window_from_ids_device(p_ids, p_oo, len(docs), n, max_length, stride, pad_to_multiple_of or 0, pad, int(bool(add_bos)),
+                                             int(bool(add_eos)), flags, p_sp, stream)
+        else:
+            _, _, _, res = eng.encode_batch_device_window(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), max_length, stride,
+                                                          add_bos, add_eos, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
         W, L = res.n_windows, res.row_len
         tdt = torch.int64 if dtype == "int64" else torch.int32
         v_ids, v_mask, v_len, v_doc, v_start, v_dw, v_sp = res.views()
-        return {"input_ids": _torch_wrap(v_ids, (W, L), tdt, copy), "attention_mask": _torch_wrap(v_mask, (W, L), torch.uint8, copy),
-                "lengths": _torch_wrap(v_len, (W,), torch.int32, copy),
-                "overflow_to_sample_mapping": _torch_wrap(v_doc, (W,), torch.int32, copy),
-                "window_start": _torch_wrap(v_start, (W,), torch.int32, copy),
-                "doc_windows": _torch_wrap(v_dw, (res.n_docs + 1,), torch.int64, copy),
-                "offset_mapping": _torch_wrap(v_sp, (W, L, 2), torch.int32, copy), "n_windows": W, "n_split": res.n_split}
+        out = {"input_ids": _torch_wrap(v_ids, (W, L), tdt, copy), "attention_mask": _torch_wrap(v_mask, (W, L), torch.uint8, copy),
+               "lengths": _torch_wrap(v_len, (W,), torch.int32, copy),
+               "overflow_to_sample_mapping": _torch_wrap(v_doc, (W,), torch.int32, copy),
+               "window_start": _torch_wrap(v_start, (W,), torch.int32, copy),
+               "doc_windows": _torch_wrap(v_dw, (res.n_docs + 1,), torch.int64, copy),
+               "offset_mapping": _torch_wrap(v_sp, (W, L, 2), torch.int32, copy), "n_windows": W, "n_split": res.n_split}
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
+        return out
+
+    def encode_batch_with_alignment(self, docs, annotations, offsets_unit="char", add_bos=False, add_eos=False, return_tensors="np"):
+        """Encode + the spans in offsets_unit + which ids every annotated range covers (tk_encode_batch_device_spans_units,
+        tk_spans_locate_device; the definitions are in include/tekken_hip.h).  annotations: per document a list of (start, end) in
+        offsets_unit ("char": indices of the str, as a QA answer_start / a NER range).
+        {"ids": int32 [T], "id_offsets": int64 [D + 1], "offset_mapping": int32 [T, 2], "ann_offsets": int64 [D + 1] the first
+        annotation of every document in the flattened list, "token_ranges": int32 [A, 2] per annotation the document-relative id
+        indices (lo, hi): ids id_offsets[d] + lo .. id_offsets[d] + hi - 1 overlap the range; hi == lo: none does}.
+        return_tensors "np": numpy; "pt": torch tensors on the tokenizer's GPU (copies)."""
+        eng = self._device_engine()
+        unit = self._unit(offsets_unit)
+        if return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_with_alignment: unknown return_tensors value")
+        if len(annotations) != len(docs):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_with_alignment: %d documents, %d annotation lists" % (len(docs), len(annotations)))
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        ann_offs = np.zeros(len(docs) + 1, np.int64)
+        ann_offs[1:] = np.cumsum([len(a) for a in annotations])
+        flat = [(int(s), int(e)) for a in annotations for s, e in a]
+        if any(not (0 <= s < 2 ** 32 and 0 <= e < 2 ** 32) for s, e in flat):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_with_alignment: an annotation is outside 0 .. 2^32 - 1")
+        ann = np.array(flat, np.uint32).reshape(len(flat), 2)
+        ann_doc = np.repeat(np.arange(len(docs), dtype=np.uint32), np.diff(ann_offs))
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        import torch
+        d_bytes, d_offs, stream = _upload(data, offs)
+        p_ids, p_oo, p_sp, n = eng.encode_batch_device_spans_units(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos,
+                                                                   add_eos, unit, CHECK_OFFSETS, stream)
+        A = len(flat)
+        d_ann = torch.from_numpy(ann.view(np.int32) if A else np.zeros((1, 2), np.int32)).cuda()
+        d_ann_doc = torch.from_numpy(ann_doc.view(np.int32) if A else np.zeros(1, np.int32)).cuda()
+        p_rng = eng.spans_locate_device(p_sp, p_oo, len(docs), n, d_ann_doc.data_ptr(), d_ann.data_ptr(), A, stream)
+        out = {"ids": _torch_wrap(DeviceView(p_ids, n, "<i4"), (n,), torch.int32, True),
+               "id_offsets": _torch_wrap(DeviceView(p_oo, len(docs) + 1, "<i8"), (len(docs) + 1,), torch.int64, True),
+               "offset_mapping": _torch_wrap(DeviceView(p_sp, (n, 2), "<i4"), (n, 2), torch.int32, True),
+               "ann_offsets": torch.from_numpy(ann_offs).cuda(),
+               "token_ranges": _torch_wrap(DeviceView(p_rng, (A, 2), "<i4"), (A, 2), torch.int32, True)}
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        return out
 
     CHAT_ROLES = {"user": ("[INST]", "[/INST]", False), "system": ("[SYSTEM_PROMPT]", "[/SYSTEM_PROMPT]", False),
                   "assistant": (None, "</s>", True)}

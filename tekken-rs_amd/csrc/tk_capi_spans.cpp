@@ -16,9 +16,11 @@ int doc_of_id(tk_ctx* c, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t id
 }
 
 // The spans pass over ids on the device: (start, end) of every id into c->sp_spans, the checks of `checks` (TK_SPANS_CHECK_*
-// only) in the same pass, one host wait for the error words.  The caller holds c->mu.  (Also the window entries' spans pass.)
+// only) in the same pass, one host wait for the error words.  The caller holds c->mu.  (Also the window entries' spans pass, and
+// -- into its own buffer -- the units pass in bytes.)
 int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids,
-              const uint64_t* d_doc_offs, const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc) {
+              const uint64_t* d_doc_offs, const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc, DevBuf* into) {
+    DevBuf& spans = into ? *into : c->sp_spans;
     if (checks & TK_SPANS_CHECK_BYTES) checks |= TK_SPANS_CHECK_COVER;
     if (((checks & TK_SPANS_CHECK_COVER) && !d_doc_offs) || ((checks & TK_SPANS_CHECK_BYTES) && !d_bytes)) {
         c->err = "the spans checks need the document offsets (COVER) and the text (BYTES)";
@@ -26,7 +28,7 @@ int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint6
     }
     int rc = token_tables(c);
     if (rc != TK_OK) return rc;
-    TK_HIP(c, c->sp_spans.reserve(n_ids * 8 + 16));
+    TK_HIP(c, spans.reserve(n_ids * 8 + 16));
     TK_HIP(c, c->sp_err.reserve(64));
     TkSpansArgs a;
     memset(&a, 0, sizeof(a));
@@ -35,7 +37,7 @@ int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint6
     a.n_docs = n_docs;
     a.doc_offs = d_doc_offs;
     a.bytes = d_bytes;
-    a.spans = (uint32_t*)c->sp_spans.p;
+    a.spans = (uint32_t*)spans.p;
     a.err = (unsigned long long*)c->sp_err.p;
     token_args(c, a);
     unsigned long long err[4] = {~0ull, ~0ull, ~0ull, ~0ull};

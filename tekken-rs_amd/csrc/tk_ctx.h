@@ -106,6 +106,10 @@ struct tk_ctx {
     DevBuf dec_lens, dec_bytes, dec_offs, dec_bits, dec_err, dec_in_ids, dec_in_offs, dec_hi, dec_glens, dec_goffs;
     DevBuf t_inline, t_len8;   // decode: 16-byte inline entries and one-byte lengths by rank (built at the first decode / spans call)
     DevBuf sp_spans, sp_err;   // tk_token_spans_device: (start, end) per id, the error words (apart from every encode / decode buffer)
+    // the units pass and the annotation look-up (tk_spans_units.hip): the per-rank entries of tk_units_table.h (built at the first
+    // units call), the spans in the unit, the token ranges (lc_next: written first, swapped in once the call is accepted) and the
+    // error words.  Apart from every other buffer
+    DevBuf t_units, su_spans, su_err, lc_range, lc_next, lc_err;
     // the dense layout (tk_dense.hip): the tensor, its mask, lengths and the two statistics words; the ragged ids / offsets / row
     // lengths of the inverse.  Apart from every encode / spans / decode buffer, allocated at the first dense call
     DevBuf dn_ids, dn_mask, dn_len, dn_stat, dn_rids, dn_roffs, dn_rlens;
@@ -233,8 +237,9 @@ template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // .
     a.n_ranks = c->host.n_ranks; a.num_special = c->host.num_special;
 }
 // tk_capi_spans.cpp: the spans pass over ids on the device into c->sp_spans, with the TK_SPANS_CHECK_* of `checks`
+// (into: the buffer the spans go to instead -- the units pass with TK_UNIT_BYTE)
 int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const uint64_t* d_doc_offs,
-              const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc);
+              const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc, DevBuf* into = nullptr);
 // tk_capi_spans.cpp: the document whose id range holds id index idx (error paths)
 int doc_of_id(tk_ctx* c, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t idx, uint64_t* out);
 #pragma GCC visibility pop

@@ -116,6 +116,31 @@ struct TkSpansArgs {
 };
 hipError_t tk_launch_spans(const TkSpansArgs& a, int checks, hipStream_t s);
 
+// ---- per-token spans in code points / UTF-16 units, annotation -> token range (tk_spans_units.hip) ----
+struct TkSpansUnitsArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const uint64_t* id_offs;   // [n_docs + 1]
+    uint64_t n_docs;
+    uint32_t* spans;           // [2 * n_ids] (start, end) per id in the unit, relative to the start of its document
+    unsigned long long* err;   // [4] see tk_spans_units.hip ([2] and [3], as the byte pass numbers them)
+    const uint8_t* tok_blob;   // token bytes by rank
+    const uint32_t* tok_offs;  // [n_ranks + 1]
+    const uint16_t* tok_units; // [n_ranks] the entries of tk_units_table.h
+    uint32_t n_ranks, num_special;
+};
+hipError_t tk_launch_spans_units(const TkSpansUnitsArgs& a, int unit, hipStream_t s);   // unit: TK_UNIT_CHAR or TK_UNIT_UTF16
+struct TkLocateArgs {
+    const uint32_t* spans;     // [2 * n_ids] (start, end) per id, non-decreasing along a document
+    const uint64_t* id_offs;   // [n_docs + 1]
+    uint64_t n_docs, n_ids;
+    const uint32_t* ann_doc;   // [n_ann] the document of every annotation
+    const uint32_t* ann;       // [2 * n_ann] (as, ae) in the unit of spans
+    uint64_t n_ann;
+    uint32_t* out;             // [2 * n_ann] (lo, hi) document-relative id indices
+    unsigned long long* err;   // [1] first annotation with ann_doc >= n_docs or as > ae (atomicMin: ~0 from the caller)
+};
+hipError_t tk_launch_spans_locate(const TkLocateArgs& a, hipStream_t s);   // n_ann == 0: nothing is launched
+
 // ---- model-ready dense layout (tk_dense.hip) ----
 struct TkDenseArgs {
     const uint32_t* ids;       // [n_ids] packed token ids of all documents
