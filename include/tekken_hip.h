@@ -488,6 +488,84 @@ int tk_encode_parts_join(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_
                          const tk_join_opts* opts, tk_join* out);
 void tk_free_join(tk_join* out);
 
+/* ---- whole documents packed into rows without cutting them (next-fit), with labels (no reference equivalent: pad_id(),
+ * src/tekkenizer.rs:304, is all the reference has) ----
+ * Supervised fine-tuning packs conversations into rows of seq_len but never cuts one: labels, position_ids and the attention
+ * segments must all describe one whole sample.  Input: the ragged ids R_d = ids[oo[d] : oo[d+1]] with n_d ids each, d < D;
+ * N = oo[D]; optionally a second int32 stream lab with the SAME offsets; options seq_len = L (required, > 0), pad_id,
+ * ignore_index, keep_tail and the flags below.
+ *   1. e_d = min(n_d, L).  A document with n_d > L is truncated on the right to L elements of which the last keep_tail are its
+ *      last ids: element k of the placed document is R_d[k] for k < L - keep_tail and R_d[n_d - (L - k)] for k >= L - keep_tail.
+ *      Documents that fit are never changed.  n_truncated = the documents with n_d > L.  lab is truncated the same way.
+ *   2. Next-fit in the caller's order: r = -1, fill = L; for d = 0 .. D-1: if e_d > 0 and fill + e_d > L then r += 1, fill = 0;
+ *      doc_start[d] = r * L + fill; fill += e_d.  n_rows = r + 1.  An empty document opens no row and takes no space; its
+ *      doc_start is where the next id would go (possibly (r + 1) * L; 0 before the first row).  row = doc_start / L and
+ *      col = doc_start % L for every non-empty document; documents keep their order, doc_start is non-decreasing.
+ *   3. input_ids[n_rows, L]: document d occupies the flattened positions doc_start[d] .. doc_start[d] + e_d, every other
+ *      position holds pad_id.  n_pad = n_rows * L - sum(e_d).
+ *   4. labels[n_rows, L] (TK_ROWFIT_LABELS, needs lab; always int32): lab in the same positions, ignore_index under pads.
+ *   5. position_ids (TK_ROWFIT_POSITIONS): the distance to the document's start, 0 under pads.  segment_ids
+ *      (TK_ROWFIT_SEGMENTS): 1, 2, 3, ... over the non-empty documents of a row, 0 under pads.
+ *   6. cu_seqlens (TK_ROWFIT_CU_SEQLENS, int32): the sorted starts of every non-empty document and of every row's pad run
+ *      (where the row has pads), followed by n_rows * L.  It tiles the whole flattened tensor: a variable-length attention call
+ *      takes the tensor as it is, every pad run a segment of its own.  n_segments = its length - 1; max_seqlen = max diff, pad
+ *      runs included (an attention kernel needs a bound over every segment).  n_rows == 0: [0], n_segments = max_seqlen = 0.
+ *      n_segments and max_seqlen are filled whether or not the array is selected.
+ *   7. doc_start (TK_ROWFIT_DOC_START): uint64 [D], as defined in 2.
+ *   8. input_ids, position_ids and segment_ids are int32, or int64 with TK_ROWFIT_I64; labels and cu_seqlens are int32.  An
+ *      unselected output is NULL.
+ *   9. TK_ERR_INVALID_ARG, nothing written, an earlier rowfit result stays readable: L == 0; L >= 2^31; an unknown flag;
+ *      keep_tail > L; TK_ROWFIT_LABELS without a labels pointer when N > 0; n_docs == 0 with n_ids > 0; n_rows * L > 2^36;
+ *      TK_ROWFIT_CU_SEQLENS with n_rows * L >= 2^31.  The last two are known once n_rows is, behind the placement and before
+ *      any output buffer is touched (offsets that do not end at n_ids are refused at the same point).  A failed allocation is
+ *      TK_ERR_RUNTIME.  D == 0 or N == 0 is valid and gives n_rows == 0.
+ * Next-fit trades padding for order and parallelism: best-fit-decreasing packs tighter, but it reorders the samples and is
+ * sequential.  A caller who wants less padding sorts or buckets the documents before the call; n_pad makes the cost visible.
+ * The layout is a separate pass behind the unchanged encode pipeline (csrc/tk_rowfit.hip).  The placement is not sequential
+ * either: with E the exclusive prefix sum of e, the row opened at document i ends in front of nxt(i), the largest j with
+ * E[j] <= E[i] + L; pointer doubling over the chain 0, nxt(0), nxt(nxt(0)), ... marks the row openers and numbers the rows in
+ * ceil(log2(n_rows)) + 1 rounds.  One host read (48 bytes: n_rows, n_truncated, sum e, the end of the offsets) sizes the tensors; every element is then written
+ * once, pad included, in 16-byte stores where L is a multiple of 4, and one more wait ends the call. */
+#define TK_ROWFIT_I64 1
+#define TK_ROWFIT_POSITIONS 2
+#define TK_ROWFIT_SEGMENTS 4
+#define TK_ROWFIT_CU_SEQLENS 8
+#define TK_ROWFIT_LABELS 16
+#define TK_ROWFIT_DOC_START 32
+typedef struct tk_rowfit_opts { uint32_t seq_len, pad_id, keep_tail, flags; int32_t ignore_index; } tk_rowfit_opts;
+typedef struct tk_rowfit { void* input_ids; int32_t* labels; void *position_ids, *segment_ids; int32_t* cu_seqlens; uint64_t* doc_start;
+                           uint64_t n_rows, row_len, n_segments, max_seqlen, n_truncated, n_pad; } tk_rowfit;
+/* ids already on the device (encode's own outputs, a join's ids / offsets, or the caller's; d_id_offsets: n_docs + 1 uint64,
+ * [0] = 0, non-decreasing, [n_docs] = n_ids -- only the last is checked) -> whole-document rows.  d_labels: NULL or int32[n_ids]
+ * (a join's labels).  out's buffers are device buffers owned by the context, valid until the next rowfit call on it, and
+ * SEPARATE from the encode, spans, dense, packed, join, window and decode outputs.  The work is enqueued on hip_stream and the
+ * call returns after the stream has drained. */
+int tk_rowfit_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                              const void* d_labels, const tk_rowfit_opts* opts, void* hip_stream, tk_rowfit* out);
+/* tk_encode_batch_device_ex + the rowfit pass on the same stream (text has no labels stream: TK_ROWFIT_LABELS is refused before
+ * anything is encoded, here and in tk_encode_batch_rowfit); the ragged outputs (*d_ids / *d_out_offsets / *n_ids as tk_encode_batch_device) are returned as well. */
+int tk_encode_batch_device_rowfit(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                  int add_bos, int add_eos, int checks, const tk_rowfit_opts* opts, void* hip_stream,
+                                  void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_rowfit* out);
+/* tk_encode_parts_device_join + the rowfit pass over the conversations' ids, labels (with TK_JOIN_LABELS) and offsets on the same
+ * stream: a conversation is a document of the placement.  *joined is the join's result, as tk_encode_parts_device_join gives it.
+ * TK_ROWFIT_LABELS without TK_JOIN_LABELS is refused before anything is encoded. */
+int tk_encode_parts_device_rowfit(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
+                                  const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                                  int checks, const tk_join_opts* join_opts, const tk_rowfit_opts* opts, void* hip_stream,
+                                  tk_join* joined, tk_rowfit* out);
+/* Host in / host out: tk_encode_batch + the rowfit pass (batches of the one-launch small path included).  out's buffers are
+ * pinned host memory, released with tk_free_rowfit (an unselected output is NULL). */
+int tk_encode_batch_rowfit(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                           int validate_utf8, const tk_rowfit_opts* opts, tk_rowfit* out);
+void tk_free_rowfit(tk_rowfit* out);
+/* Not in the list of entries the pass was asked to have: the measurement needs the placement and the fill kernel apart
+ * (tools/rowfit_time.py), and only the library sees the boundary between them.  It costs six event records a call.
+ * GPU time of the stages of the context's last rowfit pass, from events on its stream: the placement (lengths, scans, nxt,
+ * doubling rounds, doc_start; the host read between them is not counted), the fill kernel, the cu_seqlens kernel.  All 0 when
+ * the pass launched nothing (n_ids == 0) or was refused.  A NULL pointer is skipped. */
+void tk_last_rowfit_ms(const tk_ctx* ctx, float* placement_ms, float* fill_ms, float* cu_ms);
+
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token
  * at POSITION i of the reference's all_special_tokens vector (src/tekkenizer.rs:108-116, 536-540);

@@ -147,6 +147,36 @@ pub struct TkJoin {
     pub n_ctrl: u64,
     pub n_labelled: u64,
 }
+// whole documents packed into rows without cutting them (tk_rowfit_opts.flags; include/tekken_hip.h has the definition)
+pub const TK_ROWFIT_I64: u32 = 1;
+pub const TK_ROWFIT_POSITIONS: u32 = 2;
+pub const TK_ROWFIT_SEGMENTS: u32 = 4;
+pub const TK_ROWFIT_CU_SEQLENS: u32 = 8;
+pub const TK_ROWFIT_LABELS: u32 = 16;
+pub const TK_ROWFIT_DOC_START: u32 = 32;
+#[repr(C)]
+pub struct TkRowfitOpts {
+    pub seq_len: u32,
+    pub pad_id: u32,
+    pub keep_tail: u32,
+    pub flags: u32,
+    pub ignore_index: i32,
+}
+#[repr(C)]
+pub struct TkRowfit {
+    pub input_ids: *mut c_void,
+    pub labels: *mut i32,
+    pub position_ids: *mut c_void,
+    pub segment_ids: *mut c_void,
+    pub cu_seqlens: *mut i32,
+    pub doc_start: *mut u64,
+    pub n_rows: u64,
+    pub row_len: u64,
+    pub n_segments: u64,
+    pub max_seqlen: u64,
+    pub n_truncated: u64,
+    pub n_pad: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -236,6 +266,20 @@ extern "C" {
                                 part_flags: *const u32, conv_offsets: *const u64, n_convs: u64, validate_utf8: c_int,
                                 opts: *const TkJoinOpts, out: *mut TkJoin) -> c_int;
     pub fn tk_free_join(out: *mut TkJoin);
+    // whole-document rows (next-fit, never cut) behind encode or a join: ids, labels, positions, segments, cu_seqlens, doc_start
+    pub fn tk_rowfit_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                     d_labels: *const c_void, opts: *const TkRowfitOpts, hip_stream: *mut c_void, out: *mut TkRowfit) -> c_int;
+    pub fn tk_encode_batch_device_rowfit(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                         add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkRowfitOpts, hip_stream: *mut c_void,
+                                         d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkRowfit) -> c_int;
+    pub fn tk_encode_parts_device_rowfit(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_parts: u64, n_bytes: u64,
+                                         d_part_ctrl: *const c_void, d_part_flags: *const c_void, d_conv_offsets: *const c_void, n_convs: u64,
+                                         checks: c_int, join_opts: *const TkJoinOpts, opts: *const TkRowfitOpts, hip_stream: *mut c_void,
+                                         joined: *mut TkJoin, out: *mut TkRowfit) -> c_int;
+    pub fn tk_encode_batch_rowfit(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                  validate_utf8: c_int, opts: *const TkRowfitOpts, out: *mut TkRowfit) -> c_int;
+    pub fn tk_free_rowfit(out: *mut TkRowfit);
+    pub fn tk_last_rowfit_ms(ctx: *const TkCtx, placement_ms: *mut f32, fill_ms: *mut f32, cu_ms: *mut f32);
     // memo of merged pieces (round 4): a device table {unknown piece of 2..16 bytes -> its <= 4 ids}; never changes an id
     pub fn tk_ctx_set_memo(ctx: *mut TkCtx, log2_entries: c_int, policy: c_int) -> c_int;
     pub fn tk_ctx_memo_clear(ctx: *mut TkCtx) -> c_int;

@@ -38,6 +38,7 @@ CHECK_PARTS = 16   # the join entries: conv_offsets and the control ids are chec
 JOIN_NONE = 0xFFFFFFFF   # part_ctrl: the part has no control id
 PART_LABEL_CTRL, PART_LABEL_TEXT = 1, 2   # part_flags
 JOIN_LABELS, JOIN_PART_INDEX = 1, 2   # tk_join_opts.flags (the join entries)
+ROWFIT_I64, ROWFIT_POSITIONS, ROWFIT_SEGMENTS, ROWFIT_CU_SEQLENS, ROWFIT_LABELS, ROWFIT_DOC_START = 1, 2, 4, 8, 16, 32   # tk_rowfit_opts.flags (the rowfit entries)
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
 TK_ERR_INVALID_UTF8 = -3
@@ -119,6 +120,17 @@ class _Join(ctypes.Structure):
     _fields_ = [("ids", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("part_index", ctypes.c_void_p),
                 ("n_convs", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_ids", ctypes.c_uint64), ("n_ctrl", ctypes.c_uint64),
                 ("n_labelled", ctypes.c_uint64)]
+
+
+class _RowfitOpts(ctypes.Structure):
+    _fields_ = [("seq_len", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("keep_tail", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("ignore_index", ctypes.c_int32)]
+
+
+class _Rowfit(ctypes.Structure):
+    _fields_ = [("input_ids", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("position_ids", ctypes.c_void_p), ("segment_ids", ctypes.c_void_p),
+                ("cu_seqlens", ctypes.c_void_p), ("doc_start", ctypes.c_void_p), ("n_rows", ctypes.c_uint64), ("row_len", ctypes.c_uint64),
+                ("n_segments", ctypes.c_uint64), ("max_seqlen", ctypes.c_uint64), ("n_truncated", ctypes.c_uint64), ("n_pad", ctypes.c_uint64)]
 
 
 _LIB = None
@@ -357,6 +369,22 @@ def lib():
         L.tk_encode_batch_window.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, wp]
         L.tk_free_window.restype = None
         L.tk_free_window.argtypes = [wp]
+    if hasattr(L, "tk_rowfit_from_ids_device"):   # (whole-document rows: libraries built before them still load through TK_HIP_LIB)
+        op, rp, jop, jp = ctypes.POINTER(_RowfitOpts), ctypes.POINTER(_Rowfit), ctypes.POINTER(_JoinOpts), ctypes.POINTER(_Join)
+        L.tk_rowfit_from_ids_device.restype = ctypes.c_int
+        L.tk_rowfit_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, op, vp, rp]
+        L.tk_encode_batch_device_rowfit.restype = ctypes.c_int
+        L.tk_encode_batch_device_rowfit.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, rp]
+        L.tk_encode_parts_device_rowfit.restype = ctypes.c_int
+        L.tk_encode_parts_device_rowfit.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, jop,
+                                                    op, vp, jp, rp]
+        L.tk_encode_batch_rowfit.restype = ctypes.c_int
+        L.tk_encode_batch_rowfit.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, rp]
+        L.tk_free_rowfit.restype = None
+        L.tk_free_rowfit.argtypes = [rp]
+        L.tk_last_rowfit_ms.restype = None
+        L.tk_last_rowfit_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -516,6 +544,49 @@ class JoinResult:
         return (DeviceView(self.ids_ptr, self.n_ids, "<i4"), DeviceView(self.offsets_ptr, self.n_convs + 1, "<i8"),
                 DeviceView(self.labels_ptr, self.n_ids, "<i4") if self.labels_ptr else None,
                 DeviceView(self.part_index_ptr, self.n_ids, "<i4") if self.part_index_ptr else None)
+
+
+class RowfitResult:
+    """What the device rowfit entries return (tk_rowfit): raw device pointers of context-owned buffers, valid until the next
+    rowfit call on the context.  input_ids_ptr / position_ids_ptr / segment_ids_ptr: int32 or int64 [n_rows, row_len];
+    labels_ptr: int32 [n_rows, row_len]; cu_seqlens_ptr: int32 [n_segments + 1]; doc_start_ptr: uint64 [n_docs] (an unselected
+    one: None)."""
+
+    def __init__(self, p, flags, n_docs):
+        self.input_ids_ptr, self.labels_ptr = p.input_ids or 0, p.labels or None
+        self.position_ids_ptr, self.segment_ids_ptr = p.position_ids or None, p.segment_ids or None
+        self.cu_seqlens_ptr, self.doc_start_ptr = p.cu_seqlens or None, p.doc_start or None
+        self.n_docs, self.n_rows, self.row_len = int(n_docs), int(p.n_rows), int(p.row_len)
+        self.n_segments, self.max_seqlen, self.n_truncated, self.n_pad = int(p.n_segments), int(p.max_seqlen), int(p.n_truncated), int(p.n_pad)
+        self.typestr = "<i8" if flags & ROWFIT_I64 else "<i4"
+
+    def counts(self):
+        return {"max_seqlen": self.max_seqlen, "n_rows": self.n_rows, "n_segments": self.n_segments, "n_truncated": self.n_truncated,
+                "n_pad": self.n_pad}
+
+    def views(self):
+        """(input_ids, labels (int32) or None, position_ids or None, segment_ids or None -- views [n_rows, row_len] --, cu_seqlens
+        view [n_segments + 1] or None, doc_start view as int64 [n_docs] or None) -- DeviceView objects."""
+        shape = (self.n_rows, self.row_len)
+        return (DeviceView(self.input_ids_ptr, shape, self.typestr),
+                DeviceView(self.labels_ptr, shape, "<i4") if self.labels_ptr else None,
+                DeviceView(self.position_ids_ptr, shape, self.typestr) if self.position_ids_ptr else None,
+                DeviceView(self.segment_ids_ptr, shape, self.typestr) if self.segment_ids_ptr else None,
+                DeviceView(self.cu_seqlens_ptr, self.n_segments + 1, "<i4") if self.cu_seqlens_ptr else None,
+                DeviceView(self.doc_start_ptr, self.n_docs, "<i8") if self.doc_start_ptr else None)
+
+    def tensors(self, copy=True):
+        """The views as torch tensors on the GPU (copy: clones of them) and the counts, as the Tekkenizer methods return them."""
+        import torch
+        tdt = torch.int64 if self.typestr == "<i8" else torch.int32
+        v_ids, v_lab, v_pos, v_seg, v_cu, v_ds = self.views()
+        shape = (self.n_rows, self.row_len)
+        out = {"input_ids": _torch_wrap(v_ids, shape, tdt, copy), "labels": _torch_wrap(v_lab, shape, torch.int32, copy),
+               "position_ids": _torch_wrap(v_pos, shape, tdt, copy), "segment_ids": _torch_wrap(v_seg, shape, tdt, copy),
+               "cu_seqlens": _torch_wrap(v_cu, (self.n_segments + 1,), torch.int32, copy),
+               "doc_start": _torch_wrap(v_ds, (self.n_docs,), torch.int64, copy)}
+        out.update(self.counts())
+        return out
 
 
 class Engine:
@@ -842,6 +913,66 @@ class Engine:
                "n_segments": int(p.n_segments)}
         lib().tk_free_seqpack(ctypes.byref(p))
         return out
+
+    def rowfit_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, seq_len, pad_id=0, keep_tail=0, flags=0, d_labels_ptr=0,
+                               ignore_index=-100, stream=0):
+        """tk_rowfit_from_ids_device: ragged ids resident in HBM -> whole documents placed next-fit into rows of seq_len, never cut
+        (+ labels from d_labels_ptr, position_ids, segment_ids, cu_seqlens, doc_start as flags select); the definition is in
+        include/tekken_hip.h.  Returns a RowfitResult (context-owned device buffers, apart from every other output)."""
+        o, p = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), int(ignore_index)), _Rowfit()
+        self._call("tk_rowfit_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                   ctypes.c_void_p(d_labels_ptr or None), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(p))
+        return RowfitResult(p, int(flags), n_docs)
+
+    def encode_batch_device_rowfit(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, seq_len, add_bos=True, add_eos=True, pad_id=0, keep_tail=0,
+                                   flags=0, checks=0, stream=0):
+        """tk_encode_batch_device_rowfit: encode_batch_device + the rowfit pass on the same stream.
+        Returns (d_ids_ptr, d_out_offs_ptr, n_ids, RowfitResult), all context-owned."""
+        o, p = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), -100), _Rowfit()
+        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        self._call("tk_encode_batch_device_rowfit", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(p))
+        return d_ids.value, d_oo.value, int(n.value), RowfitResult(p, int(flags), n_docs)
+
+    def encode_batch_rowfit(self, data, offs, seq_len, add_bos=True, add_eos=True, validate_utf8=False, pad_id=0, keep_tail=0, flags=0):
+        """tk_encode_batch_rowfit, host in / host out: a dict of numpy arrays (input_ids, position_ids, segment_ids [n_rows, seq_len]
+        int32 or int64, cu_seqlens int32 [n_segments + 1], doc_start uint64 [n_docs]; an unselected one: None; labels: None, text
+        has none) and the counts n_rows, n_segments, max_seqlen, n_truncated, n_pad."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        o, p = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), -100), _Rowfit()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        self._call("tk_encode_batch_rowfit", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(p))
+        R, L = int(p.n_rows), int(p.row_len)
+        dt = np.int64 if flags & ROWFIT_I64 else np.int32
+        out = {"input_ids": _take(p.input_ids, R * L, dt).reshape(R, L), "labels": None,
+               "position_ids": _take(p.position_ids, R * L, dt).reshape(R, L) if p.position_ids else None,
+               "segment_ids": _take(p.segment_ids, R * L, dt).reshape(R, L) if p.segment_ids else None,
+               "cu_seqlens": _take(p.cu_seqlens, int(p.n_segments) + 1, np.int32) if p.cu_seqlens else None,
+               "doc_start": _take(p.doc_start, len(offs) - 1, np.uint64) if p.doc_start else None,
+               "max_seqlen": int(p.max_seqlen), "n_rows": R, "n_segments": int(p.n_segments), "n_truncated": int(p.n_truncated),
+               "n_pad": int(p.n_pad)}
+        lib().tk_free_rowfit(ctypes.byref(p))
+        return out
+
+    def last_rowfit_ms(self):
+        """tk_last_rowfit_ms: GPU time of the stages of the last rowfit pass on this context."""
+        a, b, c = ctypes.c_float(0), ctypes.c_float(0), ctypes.c_float(0)
+        _need("tk_last_rowfit_ms")(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
+        return {"placement_ms": a.value, "fill_ms": b.value, "cu_ms": c.value}
+
+    def encode_parts_device_rowfit(self, d_bytes_ptr, d_offs_ptr, n_parts, n_bytes, d_part_ctrl_ptr, d_part_flags_ptr, d_conv_offs_ptr, n_convs,
+                                   seq_len, pad_id=0, keep_tail=0, flags=0, ignore_index=-100, join_flags=JOIN_LABELS, checks=0, stream=0):
+        """tk_encode_parts_device_rowfit: encode_parts_device_join + the rowfit pass over the conversations' ids, labels and offsets
+        on the same stream.  Returns (JoinResult, RowfitResult), both context-owned."""
+        jo, j = _JoinOpts(int(ignore_index), int(join_flags)), _Join()
+        o, p = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), int(ignore_index)), _Rowfit()
+        self._call("tk_encode_parts_device_rowfit", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_parts, n_bytes,
+                   ctypes.c_void_p(d_part_ctrl_ptr or None), ctypes.c_void_p(d_part_flags_ptr or None), ctypes.c_void_p(d_conv_offs_ptr or None),
+                   n_convs, int(checks), ctypes.byref(jo), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(j), ctypes.byref(p))
+        return JoinResult(j), RowfitResult(p, int(flags), n_convs)
 
     def window_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, max_length, stride=0, multiple_of=0, pad_id=0, keep_head=0,
                                keep_tail=0, flags=0, d_spans_ptr=0, stream=0):
@@ -1332,6 +1463,43 @@ class Tekkenizer:
                 "cu_seqlens": _torch_wrap(v_cu, (res.n_segments + 1,), torch.int32, copy), "max_seqlen": res.max_seqlen, "n_rows": res.n_rows,
                 "n_used": res.n_used, "n_left": res.n_left, "n_segments": res.n_segments}
 
+    @staticmethod
+    def _rowfit_flags(dtype, return_position_ids, return_segment_ids, return_cu_seqlens, return_doc_start):
+        return (ROWFIT_I64 if dtype == "int64" else 0) | (ROWFIT_POSITIONS if return_position_ids else 0) \
+            | (ROWFIT_SEGMENTS if return_segment_ids else 0) | (ROWFIT_CU_SEQLENS if return_cu_seqlens else 0) \
+            | (ROWFIT_DOC_START if return_doc_start else 0)
+
+    def encode_batch_packed_whole(self, docs, seq_len, add_bos=True, add_eos=True, pad_id=None, dtype="int64", return_position_ids=True,
+                                  return_segment_ids=True, return_cu_seqlens=True, return_doc_start=True, return_tensors="pt", copy=True):
+        """Whole documents packed into rows of seq_len without cutting one (tk_encode_batch_device_rowfit / tk_encode_batch_rowfit;
+        the definition is in include/tekken_hip.h): next-fit in the given order, a document that does not fit the current row
+        opens the next one, one of more than seq_len ids is truncated on the right (its EOS survives with add_eos).
+        {"input_ids", "position_ids", "segment_ids": [n_rows, seq_len] of `dtype` ("int64" | "int32"), "cu_seqlens": int32
+        [n_segments + 1] (offsets into the flattened tensor that tile it, every pad run a segment of its own), "doc_start": [D]
+        where every document went (row * seq_len + column), "labels": None, "max_seqlen", "n_rows", "n_segments", "n_truncated",
+        "n_pad": int}; an unselected tensor is None.  Next-fit keeps the order and pays for it in padding (n_pad): sort or bucket
+        the documents by length before the call to pad less.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on
+        the tokenizer's GPU (copy=False: views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
+        eng = self._device_engine()
+        if dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed_whole: unknown dtype / return_tensors value")
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        if not 0 <= int(seq_len) < 2 ** 32:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed_whole: seq_len %r" % (seq_len,))
+        flags = self._rowfit_flags(dtype, return_position_ids, return_segment_ids, return_cu_seqlens, return_doc_start)
+        keep_tail = min(1, int(seq_len)) if add_eos else 0
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        if return_tensors == "np":
+            return eng.encode_batch_rowfit(data, offs, seq_len, add_bos, add_eos, False, pad, keep_tail, flags)
+        d_bytes, d_offs, stream = _upload(data, offs)
+        _, _, _, res = eng.encode_batch_device_rowfit(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), seq_len, add_bos, add_eos,
+                                                      pad, keep_tail, flags, CHECK_OFFSETS, stream)
+        return res.tensors(copy)
+
     def encode_batch_windows(self, docs, max_length, stride=0, add_bos=False, add_eos=False, padding="max_length", pad_to_multiple_of=None,
                              pad_id=None, dtype="int64", return_attention_mask=True, return_offsets_mapping=False, return_tensors="pt",
                              copy=True, offsets_unit="byte"):
@@ -1557,6 +1725,38 @@ class Tekkenizer:
         _, labels, _, _ = dense(res.labels_ptr, int(ignore_index) & 0xFFFFFFFF, flags, torch.int32, False)
         return {"input_ids": ids, "attention_mask": mask, "labels": labels.to(torch.int64) if i64 else labels, "lengths": lengths,
                 "n_truncated": d.n_truncated, "n_labelled": res.n_labelled}
+
+    def encode_chat_packed(self, conversations, seq_len, roles=None, add_bos=True, ignore_index=-100, pad_id=None, dtype="int64",
+                           return_position_ids=True, return_segment_ids=True, return_cu_seqlens=True, return_doc_start=True,
+                           return_tensors="pt", copy=True):
+        """encode_chat packed for fine-tuning: whole conversations placed next-fit into rows of seq_len, never cut (a conversation of
+        more than seq_len ids simply ends there).  One upload, the join pass and the rowfit pass over its ids, labels and offsets,
+        nothing through the host in between.  -> what encode_batch_packed_whole returns, with "labels": [n_rows, seq_len]
+        (ignore_index under the padding and under everything that is not trained; widened for dtype "int64") and "n_labelled"
+        (before truncation)."""
+        eng = self._device_engine()
+        if dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_chat_packed: unknown dtype / return_tensors value")
+        if not 0 <= int(seq_len) < 2 ** 32:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_chat_packed: seq_len %r" % (seq_len,))
+        import torch
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        flags = self._rowfit_flags(dtype, return_position_ids, return_segment_ids, return_cu_seqlens, return_doc_start) | ROWFIT_LABELS
+        data, offs, ctrl, pf, conv = self._parts_of(self._chat_parts(conversations, roles, add_bos))
+        d_bytes, d_offs, stream = _upload(data, offs)
+        up = [torch.from_numpy(x).cuda() for x in ((ctrl if len(ctrl) else np.zeros(1, np.uint32)).view(np.int32),
+                                                    (pf if len(pf) else np.zeros(1, np.uint32)).view(np.int32), conv.astype(np.int64))]
+        res, fit = eng.encode_parts_device_rowfit(d_bytes.data_ptr(), d_offs.data_ptr(), len(ctrl), len(data), up[0].data_ptr(), up[1].data_ptr(),
+                                                  up[2].data_ptr(), len(conv) - 1, seq_len, pad, 0, flags, ignore_index, JOIN_LABELS,
+                                                  CHECK_OFFSETS | CHECK_PARTS, stream)
+        out = fit.tensors(copy)
+        # (the labels are int32 with negative values: int32 elements through the pass, widened here -- which sign-extends)
+        if dtype == "int64":
+            out["labels"] = out["labels"].to(torch.int64)
+        out["n_labelled"] = res.n_labelled
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() if torch.is_tensor(v) else v for k, v in out.items()}
+        return out
 
     def decode_batch_padded(self, input_ids, lengths=None, policy=SpecialTokenPolicy.Ignore, pad_id=None, padding_side="right"):
         """Batch decode of dense rows (tk_ragged_from_dense_device + tk_decode_batch_device): input_ids [B, L], int32 or int64, a

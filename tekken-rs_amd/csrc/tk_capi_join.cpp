@@ -142,10 +142,9 @@ extern "C" int tk_join_from_ids_device(tk_ctx* c, const void* d_ids, const void*
                     (hipStream_t)hip_stream, out);
 }
 
-extern "C" int tk_encode_parts_device_join(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
-                                           const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
-                                           int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out) {
-    TK_ENTRY(c);
+int encode_parts_device_join(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
+                             const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                             int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out) {
     int rc = check_flags_and_args(c, checks, TK_CHECK_OFFSETS | TK_CHECK_UTF8 | TK_CHECK_PARTS,
                                   !d_doc_offsets || (!d_bytes && n_bytes) || (!d_part_ctrl && n_parts) || !d_conv_offsets || !opts || !out);
     if (rc != TK_OK || (rc = join_check_args(c, n_parts, n_convs, opts)) != TK_OK) return rc;
@@ -160,6 +159,14 @@ extern "C" int tk_encode_parts_device_join(tk_ctx* c, const void* d_bytes, const
     if (rc != TK_OK) return rc;
     return run_join(c, (const uint32_t*)d_ids, (const uint64_t*)d_oo, n_parts, n_ids, (const uint32_t*)d_part_ctrl, (const uint32_t*)d_part_flags,
                     (const uint64_t*)d_conv_offsets, n_convs, false, opts, (hipStream_t)hip_stream, out);
+}
+
+extern "C" int tk_encode_parts_device_join(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
+                                           const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                                           int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out) {
+    TK_ENTRY(c);
+    return encode_parts_device_join(c, d_bytes, d_doc_offsets, n_parts, n_bytes, d_part_ctrl, d_part_flags, d_conv_offsets, n_convs, checks,
+                                    opts, hip_stream, out);
 }
 
 extern "C" void tk_free_join(tk_join* r) {

@@ -124,6 +124,14 @@ struct tk_ctx {
     // (w_d, the scan that becomes doc_windows once the call is accepted, the scan workspace, the statistics words).  Apart from
     // every other buffer, allocated at the first window call
     DevBuf wn_ids, wn_mask, wn_spans, wn_len, wn_doc, wn_start, wn_dw, wn_dw_next, wn_cnt, wn_bsum, wn_stat;
+    // the whole-document rows (tk_rowfit.hip): the four tensors, cu_seqlens, doc_start and the statistics words; the work arrays
+    // (lengths and their scans, the jump tables, the row marks, the row openers, the per-document segment numbers, the per-row
+    // pad flags and their scan, the scan workspace).  Apart from every other buffer, allocated at the first rowfit call
+    DevBuf rf_ids, rf_lab, rf_pos, rf_seg, rf_cu, rf_dstart, rf_stat, rf_e, rf_nz, rf_E, rf_nzp, rf_ja, rf_jb, rf_row, rf_open, rf_segno,
+           rf_padf, rf_padp, rf_bsum;
+    Event rf_ev[5];                // the stages of the last rowfit call (tk_last_rowfit_ms), created at the first one
+    float rf_ms[3] = {0.f, 0.f, 0.f};   // placement | fill kernel | cu_seqlens kernel
+    float rf_ms_chain = 0.f;       // the placement's part in front of the host read
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -229,6 +237,10 @@ int encode_batch(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, u
 // kernels read them there) and whose result does not hold the ragged ids: their host copy is freed, their number kept
 int encode_batch_for_layout(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
                             int validate_utf8, DevBatch* dev, uint64_t* n_ids);
+// tk_capi_join.cpp: the body of tk_encode_parts_device_join (tk_capi_rowfit.cpp runs the rowfit pass behind it under one lock)
+int encode_parts_device_join(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
+                             const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
+                             int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out);
 // tk_capi_decode.cpp: the decode kernels' tables (also what the spans kernel reads), built at the first call that needs them
 int token_tables(tk_ctx* c);
 template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // ... as the decode and spans kernels take them

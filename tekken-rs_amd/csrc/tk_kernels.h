@@ -246,6 +246,41 @@ hipError_t tk_launch_join_has(const TkJoinArgs& a, hipStream_t s);     // has
 hipError_t tk_launch_join_parts(const TkJoinArgs& a, hipStream_t s);   // start, plocal, out_offs, n_labelled (behind the scan of has)
 hipError_t tk_launch_join(const TkJoinArgs& a, hipStream_t s);         // ids, labels, part_index; n_parts == 0: nothing is launched
 
+// ---- whole documents placed next-fit into rows, never cut (tk_rowfit.hip) ----
+struct TkRowfitArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const int32_t* lab;        // [n_ids] a second stream with the same offsets, or NULL
+    const uint64_t* id_offs;   // [n_docs + 1]
+    uint64_t n_docs;
+    uint32_t row_len, pad_id;  // L (0 < L < 2^31)
+    uint32_t keep_tail;        // ids of an over-long document's end that survive (<= L)
+    int32_t ignore;            // ignore_index
+    uint64_t n_rows;           // known behind the chain: tk_launch_rowfit_place and later
+    uint32_t* e;               // [n_docs] min(n_d, L)
+    uint32_t* nz;              // [n_docs] the document has ids
+    const uint64_t* E;         // [n_docs + 1] exclusive scan of e
+    const uint64_t* nzp;       // [n_docs + 1] exclusive scan of nz
+    uint64_t *jump_a, *jump_b; // [n_docs + 1] the jump table and its square: target | steps << 32
+    uint32_t* row;             // [n_docs + 1] the row a document opens, 0xFFFFFFFF = none; [n_docs] = n_rows
+    uint64_t* open;            // [n_rows + 1] (at most n_docs + 1) the documents that open a row, increasing; [n_rows] = n_docs
+    uint32_t* padf;            // [n_rows] the row has pads
+    const uint64_t* padp;      // [n_rows + 1] exclusive scan of padf
+    uint64_t* dstart;          // [n_docs + 1] doc_start, non-decreasing; [n_docs] = n_rows * L
+    uint32_t* segno;           // [n_docs] the document's number inside its row, from 1
+    void* out_ids;             // [n_rows * L] int32 or int64
+    int32_t* out_lab;          // the same shape, int32, or NULL
+    void* out_pos;             // the shape and type of out_ids, or NULL
+    void* out_seg;             // the shape and type of out_ids, or NULL
+    int32_t* cu;               // [n_segments + 1] (at most n_docs + n_rows + 1), or NULL
+    unsigned long long* stat;  // [0] += n_truncated, [1] = n_segments, [2] = max_seqlen (atomicMax): zeroed by the caller;
+                               // [3] = n_rows, [4] = sum e, [5] = id_offs[n_docs] (tk_launch_rowfit_chain)
+};
+hipError_t tk_launch_rowfit_len(const TkRowfitArgs& a, hipStream_t s);     // e, nz, n_truncated (n_docs > 0)
+hipError_t tk_launch_rowfit_chain(const TkRowfitArgs& a, uint32_t rounds, hipStream_t s);   // jump, row, open (behind the scan of e)
+hipError_t tk_launch_rowfit_place(const TkRowfitArgs& a, hipStream_t s);   // dstart, segno, padf (n_rows known)
+hipError_t tk_launch_rowfit(const TkRowfitArgs& a, int i64, hipStream_t s);   // the tensors; n_rows == 0: nothing is launched
+hipError_t tk_launch_rowfit_cu(const TkRowfitArgs& a, hipStream_t s);      // cu_seqlens (a.cu != NULL), n_segments, max_seqlen (behind the scan of padf)
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
