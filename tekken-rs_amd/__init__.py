@@ -323,66 +323,36 @@ def lib():
                                                   ctypes.POINTER(_Result), ctypes.POINTER(u32p)]
         L.tk_spans_locate_device.restype = ctypes.c_int
         L.tk_spans_locate_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp, ctypes.POINTER(vp), u64p]
-    if hasattr(L, "tk_dense_from_ids_device"):   # (dense batches: libraries built before them still load through TK_HIP_LIB)
-        op, dp = ctypes.POINTER(_DenseOpts), ctypes.POINTER(_Dense)
-        L.tk_dense_from_ids_device.restype = ctypes.c_int
-        L.tk_dense_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, op, vp, dp]
-        L.tk_encode_batch_device_dense.restype = ctypes.c_int
-        L.tk_encode_batch_device_dense.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                   op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, dp]
-        L.tk_encode_batch_dense.restype = ctypes.c_int
-        L.tk_encode_batch_dense.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, dp]
-        L.tk_free_dense.restype = None
-        L.tk_free_dense.argtypes = [dp]
-        L.tk_ragged_from_dense_device.restype = ctypes.c_int
-        L.tk_ragged_from_dense_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, ctypes.c_uint32, vp,
-                                                  ctypes.POINTER(vp), ctypes.POINTER(vp), u64p]
-    if hasattr(L, "tk_seqpack_from_ids_device"):   # (packed training rows: libraries built before them still load through TK_HIP_LIB)
-        op, pp = ctypes.POINTER(_SeqpackOpts), ctypes.POINTER(_Seqpack)
-        L.tk_seqpack_from_ids_device.restype = ctypes.c_int
-        L.tk_seqpack_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, op, vp, pp]
-        L.tk_encode_batch_device_seqpack.restype = ctypes.c_int
-        L.tk_encode_batch_device_seqpack.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                     op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, pp]
-        L.tk_encode_batch_seqpack.restype = ctypes.c_int
-        L.tk_encode_batch_seqpack.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, pp]
-        L.tk_free_seqpack.restype = None
-        L.tk_free_seqpack.argtypes = [pp]
+    # the layout passes whose three entries take the same arguments (extra: the second input stream of the pass over ids).  A
+    # library built before a pass still loads through TK_HIP_LIB
+    u64, ci, vpp = ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(vp)
+    for R, opts, extra in ((DenseResult, _DenseOpts, []), (SeqpackResult, _SeqpackOpts, []), (WindowResult, _WindowOpts, [vp]),
+                           (RowfitResult, _RowfitOpts, [vp])):
+        if not hasattr(L, "tk_%s_from_ids_device" % R.PASS):
+            continue
+        op, rp = ctypes.POINTER(opts), ctypes.POINTER(R.STRUCT)
+        for name, args in (("tk_%s_from_ids_device", [vp, vp, vp, u64, u64] + extra + [op, vp, rp]),
+                           ("tk_encode_batch_device_%s", [vp, vp, vp, u64, u64, ci, ci, ci, op, vp, vpp, vpp, u64p, rp]),
+                           ("tk_encode_batch_%s", [vp, u8p, u64p, u64, ci, ci, ci, op, rp]), ("tk_free_%s", [rp])):
+            fn = getattr(L, name % R.PASS)
+            fn.restype, fn.argtypes = (None if name == "tk_free_%s" else ci), args
+    jop, jp = ctypes.POINTER(_JoinOpts), ctypes.POINTER(_Join)
+    if hasattr(L, "tk_ragged_from_dense_device"):
+        L.tk_ragged_from_dense_device.restype = ci
+        L.tk_ragged_from_dense_device.argtypes = [vp, vp, u64, u64, ci, vp, ctypes.c_uint32, vp, vpp, vpp, u64p]
     if hasattr(L, "tk_join_from_ids_device"):   # (chat batches: libraries built before them still load through TK_HIP_LIB)
-        op, jp = ctypes.POINTER(_JoinOpts), ctypes.POINTER(_Join)
-        L.tk_join_from_ids_device.restype = ctypes.c_int
-        L.tk_join_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, op, vp, jp]
-        L.tk_encode_parts_device_join.restype = ctypes.c_int
-        L.tk_encode_parts_device_join.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, op, vp, jp]
-        L.tk_encode_parts_join.restype = ctypes.c_int
-        L.tk_encode_parts_join.argtypes = [vp, u8p, u64p, ctypes.c_uint64, u32p, u32p, u64p, ctypes.c_uint64, ctypes.c_int, op, jp]
+        L.tk_join_from_ids_device.restype = ci
+        L.tk_join_from_ids_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, u64, ci, jop, vp, jp]
+        L.tk_encode_parts_device_join.restype = ci
+        L.tk_encode_parts_device_join.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, u64, ci, jop, vp, jp]
+        L.tk_encode_parts_join.restype = ci
+        L.tk_encode_parts_join.argtypes = [vp, u8p, u64p, u64, u32p, u32p, u64p, u64, ci, jop, jp]
         L.tk_free_join.restype = None
         L.tk_free_join.argtypes = [jp]
-    if hasattr(L, "tk_window_from_ids_device"):   # (overlapping windows: libraries built before them still load through TK_HIP_LIB)
-        op, wp = ctypes.POINTER(_WindowOpts), ctypes.POINTER(_Window)
-        L.tk_window_from_ids_device.restype = ctypes.c_int
-        L.tk_window_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, op, vp, wp]
-        L.tk_encode_batch_device_window.restype = ctypes.c_int
-        L.tk_encode_batch_device_window.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                    op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, wp]
-        L.tk_encode_batch_window.restype = ctypes.c_int
-        L.tk_encode_batch_window.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, wp]
-        L.tk_free_window.restype = None
-        L.tk_free_window.argtypes = [wp]
-    if hasattr(L, "tk_rowfit_from_ids_device"):   # (whole-document rows: libraries built before them still load through TK_HIP_LIB)
-        op, rp, jop, jp = ctypes.POINTER(_RowfitOpts), ctypes.POINTER(_Rowfit), ctypes.POINTER(_JoinOpts), ctypes.POINTER(_Join)
-        L.tk_rowfit_from_ids_device.restype = ctypes.c_int
-        L.tk_rowfit_from_ids_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, op, vp, rp]
-        L.tk_encode_batch_device_rowfit.restype = ctypes.c_int
-        L.tk_encode_batch_device_rowfit.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                    op, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, rp]
-        L.tk_encode_parts_device_rowfit.restype = ctypes.c_int
-        L.tk_encode_parts_device_rowfit.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, jop,
-                                                    op, vp, jp, rp]
-        L.tk_encode_batch_rowfit.restype = ctypes.c_int
-        L.tk_encode_batch_rowfit.argtypes = [vp, u8p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_int, op, rp]
-        L.tk_free_rowfit.restype = None
-        L.tk_free_rowfit.argtypes = [rp]
+    if hasattr(L, "tk_encode_parts_device_rowfit"):
+        L.tk_encode_parts_device_rowfit.restype = ci
+        L.tk_encode_parts_device_rowfit.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, u64, ci, jop, ctypes.POINTER(_RowfitOpts), vp, jp,
+                                                    ctypes.POINTER(_Rowfit)]
         L.tk_last_rowfit_ms.restype = None
         L.tk_last_rowfit_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
@@ -421,13 +391,14 @@ def _take(ptr, n, dtype):
     return np.frombuffer(raw, dtype=dtype, count=n).copy()
 
 
-def _torch_wrap(view, shape, dtype, copy):
+def _torch_wrap(view, copy):
     """A DeviceView as a torch tensor on the GPU (copy: a clone of it); an unselected output (None) stays None."""
     import torch
     if view is None:
         return None
-    if 0 in shape:            # (nothing behind the pointer to look at)
-        return torch.empty(shape, dtype=dtype, device="cuda")
+    cai = view.__cuda_array_interface__
+    if 0 in cai["shape"]:     # (nothing behind the pointer to look at)
+        return torch.empty(cai["shape"], dtype={"<i4": torch.int32, "<i8": torch.int64, "|u1": torch.uint8}[cai["typestr"]], device="cuda")
     t = torch.as_tensor(view, device="cuda")
     return t.clone() if copy else t
 
@@ -462,131 +433,142 @@ def _dense_opts(max_length=0, multiple_of=0, pad_id=0, keep_head=0, keep_tail=0,
     return _DenseOpts(int(max_length or 0), int(multiple_of or 0), int(pad_id), int(keep_head), int(keep_tail), int(flags))
 
 
-class DenseResult:
+class _LayoutResult:
+    """What the five layout results share.  A result class declares its outputs ONCE, in the order of the C struct's pointer
+    fields (tests/test_layout_binding_cpu.py holds them against include/tekken_hip.h), and everything that walks them is here:
+    the *_ptr attributes, views(), tensors() and the host copy.
+    OUTPUTS: (name, typestr of views() -- None: the tensors' dtype, self.typestr --, shape(self), numpy dtype of the host entry's
+    array -- None: the tensors' dtype --, optional: an unselected one is None) per output; COUNTS: the uint64 members of the
+    struct, attributes of the same name; DICT_COUNTS: the ones the dicts of the host entries and tensors() carry; STRUCT / PASS /
+    I64: the ctypes struct, the name in the C entries, the flag that widens the tensors (None: no tensor of the pass has a dtype
+    to choose, and no typestr attribute)."""
+    OUTPUTS, COUNTS, DICT_COUNTS, STRUCT, PASS, I64 = (), (), (), None, "", None
+
+    def __init__(self, st, flags=0, n_docs=None):
+        """n_docs: only for the result whose struct does not carry it (RowfitResult)."""
+        for name, _, _, _, optional in self.OUTPUTS:
+            setattr(self, name + "_ptr", getattr(st, name) or (None if optional else 0))
+        for k in self.COUNTS:
+            setattr(self, k, int(getattr(st, k)))
+        if self.I64 is not None:
+            self.typestr = "<i8" if flags & self.I64 else "<i4"
+
+    def _ptrs(self):
+        return [getattr(self, o[0] + "_ptr") for o in self.OUTPUTS]
+
+    def views(self):
+        """One DeviceView per output, in the order of OUTPUTS (an unselected one: None)."""
+        return tuple(None if p is None else DeviceView(p, shape(self), ts or self.typestr)
+                     for p, (_, ts, shape, _, _) in zip(self._ptrs(), self.OUTPUTS))
+
+    def _counts(self):
+        return {k: getattr(self, k) for k in self.DICT_COUNTS}
+
+    def tensors(self, copy=True):
+        """The views as torch tensors on the GPU (copy: clones of them) by output name, and the counts, as the Tekkenizer methods
+        return them."""
+        out = {o[0]: _torch_wrap(v, copy) for o, v in zip(self.OUTPUTS, self.views())}
+        out.update(self._counts())
+        return out
+
+    @classmethod
+    def take(cls, st, flags=0, n_docs=None):
+        """The result of a host entry (pinned host blocks) as numpy copies by output name, and the counts; st is freed."""
+        r = cls(st, flags, n_docs)
+        out = {}
+        for p, (name, _, shape, hdt, _) in zip(r._ptrs(), cls.OUTPUTS):
+            out[name] = None if p is None else _take(p, int(np.prod(shape(r))), hdt or (np.int64 if r.typestr == "<i8" else np.int32)).reshape(shape(r))
+        out.update(r._counts())
+        getattr(lib(), "tk_free_" + cls.PASS)(ctypes.byref(st))
+        return r, out
+
+
+def _rows(r):
+    return (r.n_rows, r.row_len)
+
+
+class DenseResult(_LayoutResult):
     """What the device dense entries return (tk_dense): raw device pointers of context-owned buffers, valid until the next dense
     call on the context.  ids_ptr: int32 or int64 [n_docs, row_len]; mask_ptr: uint8 [n_docs, row_len] or None;
-    lengths_ptr: uint32 [n_docs] (views() shows it as int32: a length is at most row_len < 2^31)."""
-
-    def __init__(self, d, flags):
-        self.ids_ptr, self.mask_ptr, self.lengths_ptr = d.ids or 0, d.mask or None, d.lengths or 0
-        self.n_docs, self.row_len, self.n_truncated = int(d.n_docs), int(d.row_len), int(d.n_truncated)
-        self.typestr = "<i8" if flags & DENSE_I64 else "<i4"
-
-    def views(self):
-        """(ids view [n_docs, row_len], mask view or None, lengths view as int32 [n_docs]) -- DeviceView objects."""
-        shape = (self.n_docs, self.row_len)
-        return (DeviceView(self.ids_ptr, shape, self.typestr), DeviceView(self.mask_ptr, shape, "|u1") if self.mask_ptr else None,
-                DeviceView(self.lengths_ptr, self.n_docs, "<i4"))
+    lengths_ptr: uint32 [n_docs] (views() shows it as int32: a length is at most row_len < 2^31).
+    views(): (ids view [n_docs, row_len], mask view or None, lengths view as int32 [n_docs])."""
+    STRUCT, PASS, I64 = _Dense, "dense", DENSE_I64
+    OUTPUTS = (("ids", None, lambda r: (r.n_docs, r.row_len), None, False),
+               ("mask", "|u1", lambda r: (r.n_docs, r.row_len), np.uint8, True),
+               ("lengths", "<i4", lambda r: (r.n_docs,), np.uint32, False))
+    COUNTS = ("n_docs", "row_len", "n_truncated")
+    DICT_COUNTS = ("n_truncated",)
 
 
-class SeqpackResult:
+class SeqpackResult(_LayoutResult):
     """What the device packed entries return (tk_seqpack): raw device pointers of context-owned buffers, valid until the next
     packed call on the context.  input_ids_ptr / position_ids_ptr / segment_ids_ptr: int32 or int64 [n_rows, row_len] (an
-    unselected one: None); cu_seqlens_ptr: int32 [n_segments + 1] or None."""
-
-    def __init__(self, p, flags):
-        self.input_ids_ptr, self.position_ids_ptr, self.segment_ids_ptr = p.input_ids or 0, p.position_ids or None, p.segment_ids or None
-        self.cu_seqlens_ptr = p.cu_seqlens or None
-        self.n_rows, self.row_len, self.n_used, self.n_left = int(p.n_rows), int(p.row_len), int(p.n_used), int(p.n_left)
-        self.n_segments, self.max_seqlen = int(p.n_segments), int(p.max_seqlen)
-        self.typestr = "<i8" if flags & SEQPACK_I64 else "<i4"
-
-    def views(self):
-        """(input_ids, position_ids or None, segment_ids or None -- views [n_rows, row_len] --, cu_seqlens view [n_segments + 1]
-        or None) -- DeviceView objects."""
-        shape = (self.n_rows, self.row_len)
-        return (DeviceView(self.input_ids_ptr, shape, self.typestr),
-                DeviceView(self.position_ids_ptr, shape, self.typestr) if self.position_ids_ptr else None,
-                DeviceView(self.segment_ids_ptr, shape, self.typestr) if self.segment_ids_ptr else None,
-                DeviceView(self.cu_seqlens_ptr, self.n_segments + 1, "<i4") if self.cu_seqlens_ptr else None)
+    unselected one: None); cu_seqlens_ptr: int32 [n_segments + 1] or None.
+    views(): (input_ids, position_ids or None, segment_ids or None -- views [n_rows, row_len] --, cu_seqlens view
+    [n_segments + 1] or None)."""
+    STRUCT, PASS, I64 = _Seqpack, "seqpack", SEQPACK_I64
+    OUTPUTS = (("input_ids", None, _rows, None, False), ("position_ids", None, _rows, None, True), ("segment_ids", None, _rows, None, True),
+               ("cu_seqlens", "<i4", lambda r: (r.n_segments + 1,), np.int32, True))
+    COUNTS = ("n_rows", "row_len", "n_used", "n_left", "n_segments", "max_seqlen")
+    DICT_COUNTS = ("max_seqlen", "n_rows", "n_used", "n_left", "n_segments")
 
 
 def _window_opts(max_length, stride=0, multiple_of=0, pad_id=0, keep_head=0, keep_tail=0, flags=0):
     return _WindowOpts(int(max_length or 0), int(stride or 0), int(multiple_of or 0), int(pad_id), int(keep_head), int(keep_tail), int(flags))
 
 
-class WindowResult:
+class WindowResult(_LayoutResult):
     """What the device window entries return (tk_window): raw device pointers of context-owned buffers, valid until the next
     window call on the context.  input_ids_ptr: int32 or int64 [n_windows, row_len]; mask_ptr: uint8 [n_windows, row_len] or None;
     lengths_ptr / window_doc_ptr / window_start_ptr: uint32 [n_windows] (views() shows them as int32: each is below 2^31 for every
-    batch a tensor can hold); doc_windows_ptr: uint64 [n_docs + 1]; spans_ptr: uint32 [n_windows, row_len, 2] or None."""
-
-    def __init__(self, w, flags):
-        self.input_ids_ptr, self.mask_ptr, self.spans_ptr = w.input_ids or 0, w.mask or None, w.spans or None
-        self.lengths_ptr, self.window_doc_ptr, self.window_start_ptr = w.lengths or 0, w.window_doc or 0, w.window_start or 0
-        self.doc_windows_ptr = w.doc_windows or 0
-        self.n_docs, self.n_windows, self.row_len, self.n_split = int(w.n_docs), int(w.n_windows), int(w.row_len), int(w.n_split)
-        self.typestr = "<i8" if flags & WINDOW_I64 else "<i4"
-
-    def views(self):
-        """(input_ids [n_windows, row_len], mask or None, lengths, window_doc, window_start as int32 [n_windows], doc_windows as
-        int64 [n_docs + 1], spans as int32 [n_windows, row_len, 2] or None) -- DeviceView objects."""
-        W, shape = self.n_windows, (self.n_windows, self.row_len)
-        return (DeviceView(self.input_ids_ptr, shape, self.typestr), DeviceView(self.mask_ptr, shape, "|u1") if self.mask_ptr else None,
-                DeviceView(self.lengths_ptr, W, "<i4"), DeviceView(self.window_doc_ptr, W, "<i4"), DeviceView(self.window_start_ptr, W, "<i4"),
-                DeviceView(self.doc_windows_ptr, self.n_docs + 1, "<i8"),
-                DeviceView(self.spans_ptr, shape + (2,), "<i4") if self.spans_ptr else None)
+    batch a tensor can hold); doc_windows_ptr: uint64 [n_docs + 1]; spans_ptr: uint32 [n_windows, row_len, 2] or None.
+    views(): (input_ids [n_windows, row_len], mask or None, lengths, window_doc, window_start as int32 [n_windows], doc_windows as
+    int64 [n_docs + 1], spans as int32 [n_windows, row_len, 2] or None)."""
+    STRUCT, PASS, I64 = _Window, "window", WINDOW_I64
+    OUTPUTS = (("input_ids", None, lambda r: (r.n_windows, r.row_len), None, False),
+               ("mask", "|u1", lambda r: (r.n_windows, r.row_len), np.uint8, True),
+               ("lengths", "<i4", lambda r: (r.n_windows,), np.uint32, False),
+               ("window_doc", "<i4", lambda r: (r.n_windows,), np.uint32, False),
+               ("window_start", "<i4", lambda r: (r.n_windows,), np.uint32, False),
+               ("doc_windows", "<i8", lambda r: (r.n_docs + 1,), np.uint64, False),
+               ("spans", "<i4", lambda r: (r.n_windows, r.row_len, 2), np.uint32, True))
+    COUNTS = ("n_docs", "n_windows", "row_len", "n_split")
+    DICT_COUNTS = ("n_windows", "n_split")
 
 
-class JoinResult:
+class JoinResult(_LayoutResult):
     """What the device join entries return (tk_join): raw device pointers of context-owned buffers, valid until the next join call
     on the context.  ids_ptr: uint32 [n_ids]; offsets_ptr: uint64 [n_convs + 1]; labels_ptr: int32 [n_ids] or None;
-    part_index_ptr: uint32 [n_ids] or None."""
-
-    def __init__(self, j):
-        self.ids_ptr, self.offsets_ptr, self.labels_ptr, self.part_index_ptr = j.ids or 0, j.offsets or 0, j.labels or None, j.part_index or None
-        self.n_convs, self.n_parts, self.n_ids = int(j.n_convs), int(j.n_parts), int(j.n_ids)
-        self.n_ctrl, self.n_labelled = int(j.n_ctrl), int(j.n_labelled)
-
-    def views(self):
-        """(ids as int32 [n_ids], offsets as int64 [n_convs + 1], labels int32 [n_ids] or None, part_index as int32 [n_ids] or
-        None) -- DeviceView objects."""
-        return (DeviceView(self.ids_ptr, self.n_ids, "<i4"), DeviceView(self.offsets_ptr, self.n_convs + 1, "<i8"),
-                DeviceView(self.labels_ptr, self.n_ids, "<i4") if self.labels_ptr else None,
-                DeviceView(self.part_index_ptr, self.n_ids, "<i4") if self.part_index_ptr else None)
+    part_index_ptr: uint32 [n_ids] or None.
+    views(): (ids as int32 [n_ids], offsets as int64 [n_convs + 1], labels int32 [n_ids] or None, part_index as int32 [n_ids] or
+    None)."""
+    STRUCT, PASS = _Join, "join"
+    OUTPUTS = (("ids", "<i4", lambda r: (r.n_ids,), np.uint32, False), ("offsets", "<i8", lambda r: (r.n_convs + 1,), np.uint64, False),
+               ("labels", "<i4", lambda r: (r.n_ids,), np.int32, True), ("part_index", "<i4", lambda r: (r.n_ids,), np.uint32, True))
+    COUNTS = ("n_convs", "n_parts", "n_ids", "n_ctrl", "n_labelled")
+    DICT_COUNTS = ("n_ids", "n_ctrl", "n_labelled")
 
 
-class RowfitResult:
+class RowfitResult(_LayoutResult):
     """What the device rowfit entries return (tk_rowfit): raw device pointers of context-owned buffers, valid until the next
     rowfit call on the context.  input_ids_ptr / position_ids_ptr / segment_ids_ptr: int32 or int64 [n_rows, row_len];
     labels_ptr: int32 [n_rows, row_len]; cu_seqlens_ptr: int32 [n_segments + 1]; doc_start_ptr: uint64 [n_docs] (an unselected
-    one: None)."""
+    one: None).  n_docs is the caller's: the struct does not carry it.
+    views(): (input_ids, labels (int32) or None, position_ids or None, segment_ids or None -- views [n_rows, row_len] --,
+    cu_seqlens view [n_segments + 1] or None, doc_start view as int64 [n_docs] or None)."""
+    STRUCT, PASS, I64 = _Rowfit, "rowfit", ROWFIT_I64
+    OUTPUTS = (("input_ids", None, _rows, None, False), ("labels", "<i4", _rows, np.int32, True), ("position_ids", None, _rows, None, True),
+               ("segment_ids", None, _rows, None, True), ("cu_seqlens", "<i4", lambda r: (r.n_segments + 1,), np.int32, True),
+               ("doc_start", "<i8", lambda r: (r.n_docs,), np.uint64, True))
+    COUNTS = ("n_rows", "row_len", "n_segments", "max_seqlen", "n_truncated", "n_pad")
+    DICT_COUNTS = ("max_seqlen", "n_rows", "n_segments", "n_truncated", "n_pad")
 
-    def __init__(self, p, flags, n_docs):
-        self.input_ids_ptr, self.labels_ptr = p.input_ids or 0, p.labels or None
-        self.position_ids_ptr, self.segment_ids_ptr = p.position_ids or None, p.segment_ids or None
-        self.cu_seqlens_ptr, self.doc_start_ptr = p.cu_seqlens or None, p.doc_start or None
-        self.n_docs, self.n_rows, self.row_len = int(n_docs), int(p.n_rows), int(p.row_len)
-        self.n_segments, self.max_seqlen, self.n_truncated, self.n_pad = int(p.n_segments), int(p.max_seqlen), int(p.n_truncated), int(p.n_pad)
-        self.typestr = "<i8" if flags & ROWFIT_I64 else "<i4"
+    def __init__(self, st, flags=0, n_docs=0):
+        super().__init__(st, flags)
+        self.n_docs = int(n_docs)
 
     def counts(self):
-        return {"max_seqlen": self.max_seqlen, "n_rows": self.n_rows, "n_segments": self.n_segments, "n_truncated": self.n_truncated,
-                "n_pad": self.n_pad}
-
-    def views(self):
-        """(input_ids, labels (int32) or None, position_ids or None, segment_ids or None -- views [n_rows, row_len] --, cu_seqlens
-        view [n_segments + 1] or None, doc_start view as int64 [n_docs] or None) -- DeviceView objects."""
-        shape = (self.n_rows, self.row_len)
-        return (DeviceView(self.input_ids_ptr, shape, self.typestr),
-                DeviceView(self.labels_ptr, shape, "<i4") if self.labels_ptr else None,
-                DeviceView(self.position_ids_ptr, shape, self.typestr) if self.position_ids_ptr else None,
-                DeviceView(self.segment_ids_ptr, shape, self.typestr) if self.segment_ids_ptr else None,
-                DeviceView(self.cu_seqlens_ptr, self.n_segments + 1, "<i4") if self.cu_seqlens_ptr else None,
-                DeviceView(self.doc_start_ptr, self.n_docs, "<i8") if self.doc_start_ptr else None)
-
-    def tensors(self, copy=True):
-        """The views as torch tensors on the GPU (copy: clones of them) and the counts, as the Tekkenizer methods return them."""
-        import torch
-        tdt = torch.int64 if self.typestr == "<i8" else torch.int32
-        v_ids, v_lab, v_pos, v_seg, v_cu, v_ds = self.views()
-        shape = (self.n_rows, self.row_len)
-        out = {"input_ids": _torch_wrap(v_ids, shape, tdt, copy), "labels": _torch_wrap(v_lab, shape, torch.int32, copy),
-               "position_ids": _torch_wrap(v_pos, shape, tdt, copy), "segment_ids": _torch_wrap(v_seg, shape, tdt, copy),
-               "cu_seqlens": _torch_wrap(v_cu, (self.n_segments + 1,), torch.int32, copy),
-               "doc_start": _torch_wrap(v_ds, (self.n_docs,), torch.int64, copy)}
-        out.update(self.counts())
-        return out
+        return self._counts()
 
 
 class Engine:
@@ -831,131 +813,98 @@ class Engine:
             raise e
         return d_out.value
 
+    # ---- the three entries around a layout pass (dense, seqpack, window, rowfit): R the result class, o the pass's options
+    def _from_ids_device(self, R, o, flags, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, extra, stream):
+        """tk_<pass>_from_ids_device; extra: the pass's second input stream on the device, if its entry takes one."""
+        st = R.STRUCT()
+        self._call("tk_%s_from_ids_device" % R.PASS, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                   *[ctypes.c_void_p(x or None) for x in extra], ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(st))
+        return R(st, int(flags), n_docs)
+
+    def _encode_device(self, R, o, flags, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream):
+        """tk_encode_batch_device_<pass> -> (d_ids_ptr, d_out_offs_ptr, n_ids, R)."""
+        st, d_ids, d_oo, n = R.STRUCT(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        self._call("tk_encode_batch_device_" + R.PASS, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(st))
+        return d_ids.value, d_oo.value, int(n.value), R(st, int(flags), n_docs)
+
+    def _encode_host(self, R, o, flags, data, offs, add_bos, add_eos, validate_utf8):
+        """tk_encode_batch_<pass>, host in / host out -> (R with the counts, its numpy arrays and counts by name)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        st = R.STRUCT()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        self._call("tk_encode_batch_" + R.PASS, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(st))
+        return R.take(st, int(flags), len(offs) - 1)
+
     def dense_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, max_length=0, multiple_of=0, pad_id=0, keep_head=0,
                               keep_tail=0, flags=0, stream=0):
         """tk_dense_from_ids_device: ragged ids resident in HBM -> dense[n_docs, row_len] (+ mask with DENSE_MASK, lengths, the
         truncated count); the definition is in include/tekken_hip.h.  Returns a DenseResult (context-owned device buffers,
         apart from the encode and spans outputs)."""
-        o, d = _dense_opts(max_length, multiple_of, pad_id, keep_head, keep_tail, flags), _Dense()
-        self._call("tk_dense_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
-                   ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(d))
-        return DenseResult(d, int(flags))
+        o = _dense_opts(max_length, multiple_of, pad_id, keep_head, keep_tail, flags)
+        return self._from_ids_device(DenseResult, o, flags, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, (), stream)
 
     def encode_batch_device_dense(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, max_length=0, multiple_of=0,
                                   pad_id=0, flags=0, checks=0, stream=0):
         """tk_encode_batch_device_dense: encode_batch_device + the dense pass on the same stream; BOS / EOS survive truncation.
         Returns (d_ids_ptr, d_out_offs_ptr, n_ids, DenseResult), all context-owned."""
-        o, d = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags), _Dense()
-        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
-        self._call("tk_encode_batch_device_dense", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
-                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
-                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(d))
-        return d_ids.value, d_oo.value, int(n.value), DenseResult(d, int(flags))
+        o = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags)
+        return self._encode_device(DenseResult, o, flags, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream)
 
     def encode_batch_dense(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, max_length=0, multiple_of=0, pad_id=0,
                            flags=0):
         """tk_encode_batch_dense, host in / host out: (dense int32 or int64 [D, L], mask uint8 [D, L] or None, lengths uint32 [D]);
         .n_truncated of the call is kept in self.last_n_truncated."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        o, d = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags), _Dense()
-        dbuf = data if len(data) else np.zeros(1, np.uint8)
-        self._call("tk_encode_batch_dense", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
-                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(d))
-        D, L = int(d.n_docs), int(d.row_len)
-        dt = np.int64 if flags & DENSE_I64 else np.int32
-
-        dense = _take(d.ids, D * L, dt).reshape(D, L)
-        mask = _take(d.mask, D * L, np.uint8).reshape(D, L) if d.mask else None
-        lengths = _take(d.lengths, D, np.uint32)
-        self.last_n_truncated = int(d.n_truncated)
-        lib().tk_free_dense(ctypes.byref(d))
-        return dense, mask, lengths
+        o = _dense_opts(max_length, multiple_of, pad_id, 0, 0, flags)
+        r, out = self._encode_host(DenseResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)
+        self.last_n_truncated = r.n_truncated
+        return out["ids"], out["mask"], out["lengths"]
 
     def seqpack_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, seq_len, pad_id=0, flags=0, stream=0):
         """tk_seqpack_from_ids_device: ragged ids resident in HBM -> the id stream cut into rows of seq_len (+ position_ids,
         segment_ids, cu_seqlens as flags select); the definition is in include/tekken_hip.h.  Returns a SeqpackResult
         (context-owned device buffers, apart from the encode, spans and dense outputs)."""
-        o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
-        self._call("tk_seqpack_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
-                   ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(p))
-        return SeqpackResult(p, int(flags))
+        o = _SeqpackOpts(int(seq_len), int(pad_id), int(flags))
+        return self._from_ids_device(SeqpackResult, o, flags, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, (), stream)
 
     def encode_batch_device_seqpack(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, seq_len, add_bos=True, add_eos=True, pad_id=0, flags=0,
                                     checks=0, stream=0):
         """tk_encode_batch_device_seqpack: encode_batch_device + the packed pass on the same stream.
         Returns (d_ids_ptr, d_out_offs_ptr, n_ids, SeqpackResult), all context-owned."""
-        o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
-        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
-        self._call("tk_encode_batch_device_seqpack", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
-                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
-                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(p))
-        return d_ids.value, d_oo.value, int(n.value), SeqpackResult(p, int(flags))
+        o = _SeqpackOpts(int(seq_len), int(pad_id), int(flags))
+        return self._encode_device(SeqpackResult, o, flags, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream)
 
     def encode_batch_seqpack(self, data, offs, seq_len, add_bos=True, add_eos=True, validate_utf8=False, pad_id=0, flags=0):
         """tk_encode_batch_seqpack, host in / host out: a dict of numpy arrays (input_ids, position_ids, segment_ids [n_rows, seq_len]
         int32 or int64, cu_seqlens int32 [n_segments + 1]; an unselected one: None) and the counts n_rows, n_used, n_left,
         n_segments, max_seqlen."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        o, p = _SeqpackOpts(int(seq_len), int(pad_id), int(flags)), _Seqpack()
-        dbuf = data if len(data) else np.zeros(1, np.uint8)
-        self._call("tk_encode_batch_seqpack", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
-                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(p))
-        R, L = int(p.n_rows), int(p.row_len)
-        dt = np.int64 if flags & SEQPACK_I64 else np.int32
-
-        out = {"input_ids": _take(p.input_ids, R * L, dt).reshape(R, L),
-               "position_ids": _take(p.position_ids, R * L, dt).reshape(R, L) if p.position_ids else None,
-               "segment_ids": _take(p.segment_ids, R * L, dt).reshape(R, L) if p.segment_ids else None,
-               "cu_seqlens": _take(p.cu_seqlens, int(p.n_segments) + 1, np.int32) if p.cu_seqlens else None,
-               "max_seqlen": int(p.max_seqlen), "n_rows": R, "n_used": int(p.n_used), "n_left": int(p.n_left),
-               "n_segments": int(p.n_segments)}
-        lib().tk_free_seqpack(ctypes.byref(p))
-        return out
+        o = _SeqpackOpts(int(seq_len), int(pad_id), int(flags))
+        return self._encode_host(SeqpackResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
 
     def rowfit_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, seq_len, pad_id=0, keep_tail=0, flags=0, d_labels_ptr=0,
                                ignore_index=-100, stream=0):
         """tk_rowfit_from_ids_device: ragged ids resident in HBM -> whole documents placed next-fit into rows of seq_len, never cut
         (+ labels from d_labels_ptr, position_ids, segment_ids, cu_seqlens, doc_start as flags select); the definition is in
         include/tekken_hip.h.  Returns a RowfitResult (context-owned device buffers, apart from every other output)."""
-        o, p = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), int(ignore_index)), _Rowfit()
-        self._call("tk_rowfit_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
-                   ctypes.c_void_p(d_labels_ptr or None), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(p))
-        return RowfitResult(p, int(flags), n_docs)
+        o = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), int(ignore_index))
+        return self._from_ids_device(RowfitResult, o, flags, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, (d_labels_ptr,), stream)
 
     def encode_batch_device_rowfit(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, seq_len, add_bos=True, add_eos=True, pad_id=0, keep_tail=0,
                                    flags=0, checks=0, stream=0):
         """tk_encode_batch_device_rowfit: encode_batch_device + the rowfit pass on the same stream.
         Returns (d_ids_ptr, d_out_offs_ptr, n_ids, RowfitResult), all context-owned."""
-        o, p = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), -100), _Rowfit()
-        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
-        self._call("tk_encode_batch_device_rowfit", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
-                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
-                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(p))
-        return d_ids.value, d_oo.value, int(n.value), RowfitResult(p, int(flags), n_docs)
+        o = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), -100)
+        return self._encode_device(RowfitResult, o, flags, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream)
 
     def encode_batch_rowfit(self, data, offs, seq_len, add_bos=True, add_eos=True, validate_utf8=False, pad_id=0, keep_tail=0, flags=0):
         """tk_encode_batch_rowfit, host in / host out: a dict of numpy arrays (input_ids, position_ids, segment_ids [n_rows, seq_len]
         int32 or int64, cu_seqlens int32 [n_segments + 1], doc_start uint64 [n_docs]; an unselected one: None; labels: None, text
         has none) and the counts n_rows, n_segments, max_seqlen, n_truncated, n_pad."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        o, p = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), -100), _Rowfit()
-        dbuf = data if len(data) else np.zeros(1, np.uint8)
-        self._call("tk_encode_batch_rowfit", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
-                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(p))
-        R, L = int(p.n_rows), int(p.row_len)
-        dt = np.int64 if flags & ROWFIT_I64 else np.int32
-        out = {"input_ids": _take(p.input_ids, R * L, dt).reshape(R, L), "labels": None,
-               "position_ids": _take(p.position_ids, R * L, dt).reshape(R, L) if p.position_ids else None,
-               "segment_ids": _take(p.segment_ids, R * L, dt).reshape(R, L) if p.segment_ids else None,
-               "cu_seqlens": _take(p.cu_seqlens, int(p.n_segments) + 1, np.int32) if p.cu_seqlens else None,
-               "doc_start": _take(p.doc_start, len(offs) - 1, np.uint64) if p.doc_start else None,
-               "max_seqlen": int(p.max_seqlen), "n_rows": R, "n_segments": int(p.n_segments), "n_truncated": int(p.n_truncated),
-               "n_pad": int(p.n_pad)}
-        lib().tk_free_rowfit(ctypes.byref(p))
-        return out
+        o = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), -100)
+        return self._encode_host(RowfitResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
 
     def last_rowfit_ms(self):
         """tk_last_rowfit_ms: GPU time of the stages of the last rowfit pass on this context."""
@@ -979,44 +928,23 @@ class Engine:
         """tk_window_from_ids_device: ragged ids resident in HBM -> overlapping windows [n_windows, row_len] (+ mask with
         WINDOW_MASK, spans with WINDOW_SPANS from d_spans_ptr, lengths, window_doc, window_start, doc_windows); the definition is
         in include/tekken_hip.h.  Returns a WindowResult (context-owned device buffers, apart from every other output)."""
-        o, w = _window_opts(max_length, stride, multiple_of, pad_id, keep_head, keep_tail, flags), _Window()
-        self._call("tk_window_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
-                   ctypes.c_void_p(d_spans_ptr or None), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(w))
-        return WindowResult(w, int(flags))
+        o = _window_opts(max_length, stride, multiple_of, pad_id, keep_head, keep_tail, flags)
+        return self._from_ids_device(WindowResult, o, flags, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, (d_spans_ptr,), stream)
 
     def encode_batch_device_window(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, max_length, stride=0, add_bos=True, add_eos=True,
                                    multiple_of=0, pad_id=0, flags=0, checks=0, stream=0):
         """tk_encode_batch_device_window: encode_batch_device (+ the spans pass with WINDOW_SPANS) + the window pass on the same
         stream; every window repeats BOS / EOS.  Returns (d_ids_ptr, d_out_offs_ptr, n_ids, WindowResult), all context-owned."""
-        o, w = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags), _Window()
-        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
-        self._call("tk_encode_batch_device_window", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
-                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
-                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(w))
-        return d_ids.value, d_oo.value, int(n.value), WindowResult(w, int(flags))
+        o = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags)
+        return self._encode_device(WindowResult, o, flags, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream)
 
     def encode_batch_window(self, data, offs, max_length, stride=0, add_bos=True, add_eos=True, validate_utf8=False, multiple_of=0,
                             pad_id=0, flags=0):
         """tk_encode_batch_window, host in / host out: a dict of numpy arrays (input_ids int32 or int64 [n_windows, row_len], mask
         uint8 or None, lengths / window_doc / window_start uint32 [n_windows], doc_windows uint64 [n_docs + 1], spans uint32
         [n_windows, row_len, 2] or None) and the counts n_windows, n_split."""
-        data = np.ascontiguousarray(data, dtype=np.uint8)
-        offs = np.ascontiguousarray(offs, dtype=np.uint64)
-        o, w = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags), _Window()
-        dbuf = data if len(data) else np.zeros(1, np.uint8)
-        self._call("tk_encode_batch_window", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
-                   int(add_eos), int(validate_utf8), ctypes.byref(o), ctypes.byref(w))
-        W, L = int(w.n_windows), int(w.row_len)
-        dt = np.int64 if flags & WINDOW_I64 else np.int32
-
-        out = {"input_ids": _take(w.input_ids, W * L, dt).reshape(W, L),
-               "mask": _take(w.mask, W * L, np.uint8).reshape(W, L) if w.mask else None,
-               "lengths": _take(w.lengths, W, np.uint32), "window_doc": _take(w.window_doc, W, np.uint32),
-               "window_start": _take(w.window_start, W, np.uint32), "doc_windows": _take(w.doc_windows, int(w.n_docs) + 1, np.uint64),
-               "spans": _take(w.spans, W * L * 2, np.uint32).reshape(W, L, 2) if w.spans else None,
-               "n_windows": W, "n_split": int(w.n_split)}
-        lib().tk_free_window(ctypes.byref(w))
-        return out
+        o = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags)
+        return self._encode_host(WindowResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
 
     def join_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, d_part_ctrl_ptr, d_part_flags_ptr, d_conv_offs_ptr, n_convs,
                              ignore_index=-100, flags=0, checks=0, stream=0):
@@ -1061,14 +989,7 @@ class Engine:
         self._call("tk_encode_parts_join", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), n_parts, _p(cbuf, ctypes.c_uint32),
                    None if fbuf is None else _p(fbuf, ctypes.c_uint32), _p(conv, ctypes.c_uint64), len(conv) - 1,
                    int(validate_utf8), ctypes.byref(o), ctypes.byref(j))
-        N, C = int(j.n_ids), int(j.n_convs)
-
-        out = {"ids": _take(j.ids, N, np.uint32), "offsets": _take(j.offsets, C + 1, np.uint64),
-               "labels": _take(j.labels, N, np.int32) if j.labels else None,
-               "part_index": _take(j.part_index, N, np.uint32) if j.part_index else None,
-               "n_ids": N, "n_ctrl": int(j.n_ctrl), "n_labelled": int(j.n_labelled)}
-        lib().tk_free_join(ctypes.byref(j))
-        return out
+        return JoinResult.take(j)[1]
 
     def ragged_from_dense_device(self, d_dense_ptr, n_docs, row_len, flags=0, d_lengths_ptr=0, pad_id=0, stream=0):
         """tk_ragged_from_dense_device: dense rows in HBM (int32, or int64 with DENSE_I64; DENSE_PAD_LEFT) -> (d_ids_ptr,
@@ -1390,6 +1311,23 @@ class Tekkenizer:
             raise TokenizerError(TK_ERR_NO_DEVICE, "tokenizer was created without a device (host-only object)")
         return eng
 
+    def _batch_prelude(self, method, docs, add_bos, add_eos, pad_id, values_ok, values, ranges=None, upload=True):
+        """What the batch methods do behind _device_engine(), in the order their errors are raised in: values_ok, the method's check
+        of its keyword values (values: how its message names them); the BOS / EOS probe; the pad id (None: self.pad_id());
+        ranges, {name: number} that go into uint32 options; the documents packed and -- upload -- on the GPU.
+        -> (pad, data, offs, uint8 tensor, int64 tensor, stream), the last three None without upload."""
+        if not values_ok:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "%s: unknown %s value" % (method, values))
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        if not all(0 <= int(x) < 2 ** 32 for x in (ranges or {}).values()):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "%s: %s" % (method, ", ".join("%s %r" % kv for kv in ranges.items())))
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        return (pad, data, offs) + (_upload(data, offs) if upload else (None, None, None))
+
     def encode_batch_padded(self, docs, add_bos=False, add_eos=False, max_length=None, padding="longest", truncation_side="right",
                             padding_side="right", pad_to_multiple_of=None, pad_id=None, dtype="int64", return_mask=True,
                             return_tensors="pt", copy=True):
@@ -1400,30 +1338,20 @@ class Tekkenizer:
         pad_to_multiple_of.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on the tokenizer's GPU (the text goes
         up once; copy=False returns views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
         eng = self._device_engine()
-        if padding not in ("longest", "max_length") or truncation_side not in ("left", "right") or padding_side not in ("left", "right") \
-                or dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
-            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_padded: unknown padding / side / dtype / return_tensors value")
-        if add_bos:
-            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
-        if add_eos:
-            self.eos_id()
-        pad = self.pad_id() if pad_id is None else int(pad_id)
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_padded", docs, add_bos, add_eos, pad_id,
+            padding in ("longest", "max_length") and truncation_side in ("left", "right") and padding_side in ("left", "right")
+            and dtype in ("int64", "int32") and return_tensors in ("pt", "np"), "padding / side / dtype / return_tensors",
+            upload=return_tensors != "np")
         flags = (DENSE_FIXED if padding == "max_length" else 0) | (DENSE_TRUNC_LEFT if truncation_side == "left" else 0) \
             | (DENSE_PAD_LEFT if padding_side == "left" else 0) | (DENSE_I64 if dtype == "int64" else 0) | (DENSE_MASK if return_mask else 0)
-        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
         if return_tensors == "np":
             dense, mask, lengths = eng.encode_batch_dense(data, offs, add_bos, add_eos, False, max_length, pad_to_multiple_of, pad, flags)
             return {"input_ids": dense, "attention_mask": mask, "lengths": lengths.astype(np.int32), "n_truncated": eng.last_n_truncated}
-        import torch
-        d_bytes, d_offs, stream = _upload(data, offs)
         _, _, _, res = eng.encode_batch_device_dense(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos, add_eos,
                                                      max_length, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
-        D, L = res.n_docs, res.row_len
-        tdt = torch.int64 if dtype == "int64" else torch.int32
-        v_ids, v_mask, v_len = res.views()
-        return {"input_ids": _torch_wrap(v_ids, (D, L), tdt, copy),
-                "attention_mask": _torch_wrap(v_mask, (D, L), torch.uint8, copy) if return_mask else None,
-                "lengths": _torch_wrap(v_len, (D,), torch.int32, copy), "n_truncated": res.n_truncated}
+        t = res.tensors(copy)
+        return {"input_ids": t["ids"], "attention_mask": t["mask"], "lengths": t["lengths"], "n_truncated": t["n_truncated"]}
 
     def encode_batch_packed(self, docs, seq_len, add_bos=True, add_eos=True, drop_last=False, pad_id=None, dtype="int64",
                             return_position_ids=True, return_segment_ids=True, return_cu_seqlens=True, return_tensors="pt", copy=True):
@@ -1436,32 +1364,17 @@ class Tekkenizer:
         into the next batch).  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on the tokenizer's GPU (copy=False:
         views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
         eng = self._device_engine()
-        if dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
-            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed: unknown dtype / return_tensors value")
-        if add_bos:
-            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
-        if add_eos:
-            self.eos_id()
-        pad = self.pad_id() if pad_id is None else int(pad_id)
-        if not 0 <= int(seq_len) < 2 ** 32:
-            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed: seq_len %r" % (seq_len,))
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_packed", docs, add_bos, add_eos, pad_id, dtype in ("int64", "int32") and return_tensors in ("pt", "np"),
+            "dtype / return_tensors", {"seq_len": seq_len}, upload=return_tensors != "np")
         flags = (SEQPACK_I64 if dtype == "int64" else 0) | (SEQPACK_POSITIONS if return_position_ids else 0) \
             | (SEQPACK_SEGMENTS if return_segment_ids else 0) | (SEQPACK_CU_SEQLENS if return_cu_seqlens else 0) \
             | (SEQPACK_DROP_LAST if drop_last else 0)
-        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
         if return_tensors == "np":
             return eng.encode_batch_seqpack(data, offs, seq_len, add_bos, add_eos, False, pad, flags)
-        import torch
-        d_bytes, d_offs, stream = _upload(data, offs)
         _, _, _, res = eng.encode_batch_device_seqpack(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), seq_len, add_bos, add_eos,
                                                        pad, flags, CHECK_OFFSETS, stream)
-        tdt = torch.int64 if dtype == "int64" else torch.int32
-        v_ids, v_pos, v_seg, v_cu = res.views()
-        shape = (res.n_rows, res.row_len)
-        return {"input_ids": _torch_wrap(v_ids, shape, tdt, copy), "position_ids": _torch_wrap(v_pos, shape, tdt, copy),
-                "segment_ids": _torch_wrap(v_seg, shape, tdt, copy),
-                "cu_seqlens": _torch_wrap(v_cu, (res.n_segments + 1,), torch.int32, copy), "max_seqlen": res.max_seqlen, "n_rows": res.n_rows,
-                "n_used": res.n_used, "n_left": res.n_left, "n_segments": res.n_segments}
+        return res.tensors(copy)
 
     @staticmethod
     def _rowfit_flags(dtype, return_position_ids, return_segment_ids, return_cu_seqlens, return_doc_start):
@@ -1481,21 +1394,13 @@ class Tekkenizer:
         the documents by length before the call to pad less.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on
         the tokenizer's GPU (copy=False: views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
         eng = self._device_engine()
-        if dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
-            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed_whole: unknown dtype / return_tensors value")
-        if add_bos:
-            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
-        if add_eos:
-            self.eos_id()
-        pad = self.pad_id() if pad_id is None else int(pad_id)
-        if not 0 <= int(seq_len) < 2 ** 32:
-            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_packed_whole: seq_len %r" % (seq_len,))
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_packed_whole", docs, add_bos, add_eos, pad_id, dtype in ("int64", "int32") and return_tensors in ("pt", "np"),
+            "dtype / return_tensors", {"seq_len": seq_len}, upload=return_tensors != "np")
         flags = self._rowfit_flags(dtype, return_position_ids, return_segment_ids, return_cu_seqlens, return_doc_start)
         keep_tail = min(1, int(seq_len)) if add_eos else 0
-        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
         if return_tensors == "np":
             return eng.encode_batch_rowfit(data, offs, seq_len, add_bos, add_eos, False, pad, keep_tail, flags)
-        d_bytes, d_offs, stream = _upload(data, offs)
         _, _, _, res = eng.encode_batch_device_rowfit(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), seq_len, add_bos, add_eos,
                                                       pad, keep_tail, flags, CHECK_OFFSETS, stream)
         return res.tensors(copy)
@@ -1517,19 +1422,13 @@ class Tekkenizer:
         views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
         eng = self._device_engine()
         unit = self._unit(offsets_unit)
-        if padding not in ("longest", "max_length") or dtype not in ("int64", "int32") or return_tensors not in ("pt", "np"):
-            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_windows: unknown padding / dtype / return_tensors value")
-        if add_bos:
-            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
-        if add_eos:
-            self.eos_id()
-        pad = self.pad_id() if pad_id is None else int(pad_id)
-        if not (0 <= int(max_length) < 2 ** 32 and 0 <= int(stride) < 2 ** 32):
-            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_windows: max_length %r, stride %r" % (max_length, stride))
+        in_units = unit != UNIT_BYTE and return_offsets_mapping
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_windows", docs, add_bos, add_eos, pad_id,
+            padding in ("longest", "max_length") and dtype in ("int64", "int32") and return_tensors in ("pt", "np"),
+            "padding / dtype / return_tensors", {"max_length": max_length, "stride": stride}, upload=return_tensors != "np" or in_units)
         flags = (WINDOW_FIXED if padding == "max_length" else 0) | (WINDOW_I64 if dtype == "int64" else 0) \
             | (WINDOW_MASK if return_attention_mask else 0) | (WINDOW_SPANS if return_offsets_mapping else 0)
-        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
-        in_units = unit != UNIT_BYTE and return_offsets_mapping
         if return_tensors == "np" and not in_units:
             r = eng.encode_batch_window(data, offs, max_length, stride, add_bos, add_eos, False, pad_to_multiple_of, pad, flags)
             return {"input_ids": r["input_ids"], "attention_mask": r["mask"], "lengths": r["lengths"].astype(np.int32),
@@ -1538,7 +1437,6 @@ class Tekkenizer:
                     "offset_mapping": r["spans"].astype(np.int32) if r["spans"] is not None else None,
                     "n_windows": r["n_windows"], "n_split": r["n_split"]}
         import torch
-        d_bytes, d_offs, stream = _upload(data, offs)
         if in_units:
             # three calls on the stream: encode, the units pass, the window pass over the unit spans (every window repeats BOS / EOS)
             p_ids, p_oo, p_sp, n = eng.encode_batch_device_spans_units(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos,
@@ -1548,15 +1446,10 @@ class Tekkenizer:
         else:
             _, _, _, res = eng.encode_batch_device_window(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), max_length, stride,
                                                           add_bos, add_eos, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
-        W, L = res.n_windows, res.row_len
-        tdt = torch.int64 if dtype == "int64" else torch.int32
-        v_ids, v_mask, v_len, v_doc, v_start, v_dw, v_sp = res.views()
-        out = {"input_ids": _torch_wrap(v_ids, (W, L), tdt, copy), "attention_mask": _torch_wrap(v_mask, (W, L), torch.uint8, copy),
-               "lengths": _torch_wrap(v_len, (W,), torch.int32, copy),
-               "overflow_to_sample_mapping": _torch_wrap(v_doc, (W,), torch.int32, copy),
-               "window_start": _torch_wrap(v_start, (W,), torch.int32, copy),
-               "doc_windows": _torch_wrap(v_dw, (res.n_docs + 1,), torch.int64, copy),
-               "offset_mapping": _torch_wrap(v_sp, (W, L, 2), torch.int32, copy), "n_windows": W, "n_split": res.n_split}
+        t = res.tensors(copy)
+        out = {"input_ids": t["input_ids"], "attention_mask": t["mask"], "lengths": t["lengths"], "overflow_to_sample_mapping": t["window_doc"],
+               "window_start": t["window_start"], "doc_windows": t["doc_windows"], "offset_mapping": t["spans"],
+               "n_windows": t["n_windows"], "n_split": t["n_split"]}
         if return_tensors == "np":
             out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
         return out
@@ -1595,11 +1488,9 @@ class Tekkenizer:
         d_ann = torch.from_numpy(ann.view(np.int32) if A else np.zeros((1, 2), np.int32)).cuda()
         d_ann_doc = torch.from_numpy(ann_doc.view(np.int32) if A else np.zeros(1, np.int32)).cuda()
         p_rng = eng.spans_locate_device(p_sp, p_oo, len(docs), n, d_ann_doc.data_ptr(), d_ann.data_ptr(), A, stream)
-        out = {"ids": _torch_wrap(DeviceView(p_ids, n, "<i4"), (n,), torch.int32, True),
-               "id_offsets": _torch_wrap(DeviceView(p_oo, len(docs) + 1, "<i8"), (len(docs) + 1,), torch.int64, True),
-               "offset_mapping": _torch_wrap(DeviceView(p_sp, (n, 2), "<i4"), (n, 2), torch.int32, True),
-               "ann_offsets": torch.from_numpy(ann_offs).cuda(),
-               "token_ranges": _torch_wrap(DeviceView(p_rng, (A, 2), "<i4"), (A, 2), torch.int32, True)}
+        out = {"ids": _torch_wrap(DeviceView(p_ids, n, "<i4"), True), "id_offsets": _torch_wrap(DeviceView(p_oo, len(docs) + 1, "<i8"), True),
+               "offset_mapping": _torch_wrap(DeviceView(p_sp, (n, 2), "<i4"), True), "ann_offsets": torch.from_numpy(ann_offs).cuda(),
+               "token_ranges": _torch_wrap(DeviceView(p_rng, (A, 2), "<i4"), True)}
         if return_tensors == "np":
             out = {k: v.cpu().numpy() for k, v in out.items()}
         return out
@@ -1656,13 +1547,8 @@ class Tekkenizer:
             r = eng.encode_parts_join(*parts, ignore_index=ignore_index, flags=flags)
             return {"input_ids": r["ids"], "offsets": r["offsets"], "labels": r["labels"], "part_index": r["part_index"],
                     "n_labelled": r["n_labelled"]}
-        import torch
-        res, _ = self._join_device(eng, parts, ignore_index, flags)
-        v_ids, v_offs, v_lab, v_pi = res.views()
-        N = (res.n_ids,)
-        return {"input_ids": _torch_wrap(v_ids, N, torch.int32, copy), "offsets": _torch_wrap(v_offs, (res.n_convs + 1,), torch.int64, copy),
-                "labels": _torch_wrap(v_lab, N, torch.int32, copy), "part_index": _torch_wrap(v_pi, N, torch.int32, copy),
-                "n_labelled": res.n_labelled}
+        t = self._join_device(eng, parts, ignore_index, flags)[0].tensors(copy)
+        return {"input_ids": t["ids"], "offsets": t["offsets"], "labels": t["labels"], "part_index": t["part_index"], "n_labelled": t["n_labelled"]}
 
     def _chat_parts(self, conversations, roles, add_bos):
         table = dict(self.CHAT_ROLES)
@@ -1710,21 +1596,16 @@ class Tekkenizer:
         flags = (DENSE_FIXED if padding == "max_length" else 0) | (DENSE_TRUNC_LEFT if truncation_side == "left" else 0) \
             | (DENSE_PAD_LEFT if padding_side == "left" else 0)
 
-        def dense(ptr, pad_value, fl, tdtype, want_mask):
-            d = eng.dense_from_ids_device(ptr if N else 0, res.offsets_ptr, C, N, max_length, pad_to_multiple_of, pad_value, int(bool(add_bos)), 0,
-                                          fl, stream)
-            shape = (d.n_docs, d.row_len)
-            v_ids, v_mask, v_len = d.views()
-            return (d, _torch_wrap(v_ids, shape, tdtype, True), _torch_wrap(v_mask, shape, torch.uint8, True) if want_mask else None,
-                    _torch_wrap(v_len, (d.n_docs,), torch.int32, True))
+        def dense(ptr, pad_value, fl):
+            return eng.dense_from_ids_device(ptr if N else 0, res.offsets_ptr, C, N, max_length, pad_to_multiple_of, pad_value, int(bool(add_bos)), 0,
+                                             fl, stream).tensors(True)
 
         i64 = dtype == "int64"
-        d, ids, mask, lengths = dense(res.ids_ptr, pad, flags | (DENSE_I64 if i64 else 0) | (DENSE_MASK if return_mask else 0),
-                                      torch.int64 if i64 else torch.int32, return_mask)
+        d = dense(res.ids_ptr, pad, flags | (DENSE_I64 if i64 else 0) | (DENSE_MASK if return_mask else 0))
         # (the labels are int32 with negative values: int32 elements through the pass, widened here -- which sign-extends)
-        _, labels, _, _ = dense(res.labels_ptr, int(ignore_index) & 0xFFFFFFFF, flags, torch.int32, False)
-        return {"input_ids": ids, "attention_mask": mask, "labels": labels.to(torch.int64) if i64 else labels, "lengths": lengths,
-                "n_truncated": d.n_truncated, "n_labelled": res.n_labelled}
+        labels = dense(res.labels_ptr, int(ignore_index) & 0xFFFFFFFF, flags)["ids"]
+        return {"input_ids": d["ids"], "attention_mask": d["mask"], "labels": labels.to(torch.int64) if i64 else labels, "lengths": d["lengths"],
+                "n_truncated": d["n_truncated"], "n_labelled": res.n_labelled}
 
     def encode_chat_packed(self, conversations, seq_len, roles=None, add_bos=True, ignore_index=-100, pad_id=None, dtype="int64",
                            return_position_ids=True, return_segment_ids=True, return_cu_seqlens=True, return_doc_start=True,

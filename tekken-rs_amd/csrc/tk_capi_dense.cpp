@@ -1,6 +1,6 @@
 // tk_capi_dense.cpp -- model-ready dense batches (include/tekken_hip.h tk_dense_from_ids_device and the entries around it;
 // csrc/tk_dense.hip): truncation, padding, mask and lengths, and back to the ragged form.
-#include "tk_ctx.h"
+#include "tk_capi_layout.h"
 
 #define TK_DENSE_ALL_FLAGS (TK_DENSE_PAD_LEFT | TK_DENSE_TRUNC_LEFT | TK_DENSE_FIXED | TK_DENSE_I64 | TK_DENSE_MASK)
 
@@ -36,7 +36,7 @@ static int dense_too_large(tk_ctx* c, uint64_t n_docs, uint64_t row_len) {
     return TK_ERR_INVALID_ARG;
 }
 
-// The dense pass over ids on the device into the context's dn_* buffers; *out gets the device pointers.  Longest-row mode: one
+// The dense pass over ids on the device into the context's c->dense buffers; *out gets the device pointers.  Longest-row mode: one
 // reduction over the id offsets and one 8-byte read size the tensor; FIXED: no read before the launch.  One wait at the end
 // (the truncated count).  Nothing of an earlier result is touched before every argument has been accepted.  The caller holds c->mu.
 static int run_dense(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, const tk_dense_opts* o,
@@ -45,8 +45,8 @@ static int run_dense(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
     if (rc != TK_OK) return rc;
     if ((rc = check_n_docs(c, n_docs)) != TK_OK) return rc;
     const bool fixed = (o->flags & TK_DENSE_FIXED) != 0, i64 = (o->flags & TK_DENSE_I64) != 0, mask = (o->flags & TK_DENSE_MASK) != 0;
-    TK_HIP(c, c->dn_stat.reserve(64));
-    unsigned long long* d_stat = (unsigned long long*)c->dn_stat.p;
+    TK_HIP(c, c->dense.stat.reserve(64));
+    unsigned long long* d_stat = (unsigned long long*)c->dense.stat.p;
     TK_HIP(c, hipMemsetAsync(d_stat, 0, 16, s));
     uint64_t L = o->max_length;
     if (!fixed) {
@@ -59,9 +59,9 @@ static int run_dense(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
     if (o->multiple_of) L = (L + o->multiple_of - 1) / o->multiple_of * o->multiple_of;
     if (L > TK_LAYOUT_MAX_ROW || (n_docs && L > TK_LAYOUT_MAX_ELEMS / n_docs)) return dense_too_large(c, n_docs, L);
     const uint64_t elems = n_docs * L;
-    TK_HIP(c, c->dn_ids.reserve(elems * (i64 ? 8 : 4) + 16));
-    if (mask) TK_HIP(c, c->dn_mask.reserve(elems + 16));
-    TK_HIP(c, c->dn_len.reserve(n_docs * 4 + 16));
+    TK_HIP(c, c->dense.ids.reserve(elems * (i64 ? 8 : 4) + 16));
+    if (mask) TK_HIP(c, c->dense.mask.reserve(elems + 16));
+    TK_HIP(c, c->dense.len.reserve(n_docs * 4 + 16));
     TkDenseArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = d_ids;
@@ -74,76 +74,52 @@ static int run_dense(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
     a.pad_id = o->pad_id;
     a.trunc_left = (o->flags & TK_DENSE_TRUNC_LEFT) != 0;
     a.pad_left = (o->flags & TK_DENSE_PAD_LEFT) != 0;
-    a.out = c->dn_ids.p;
-    a.mask = mask ? (uint8_t*)c->dn_mask.p : nullptr;
-    a.lengths = (uint32_t*)c->dn_len.p;
+    a.out = c->dense.ids.p;
+    a.mask = mask ? (uint8_t*)c->dense.mask.p : nullptr;
+    a.lengths = (uint32_t*)c->dense.len.p;
     a.stat = d_stat;
     unsigned long long n_trunc = 0;
-    if (L == 0 && n_docs) TK_HIP(c, hipMemsetAsync(c->dn_len.p, 0, n_docs * 4, s));   // (no document has an id: nothing to launch)
+    if (L == 0 && n_docs) TK_HIP(c, hipMemsetAsync(c->dense.len.p, 0, n_docs * 4, s));   // (no document has an id: nothing to launch)
     TK_HIP(c, tk_launch_dense(a, i64, s));
     TK_HIP(c, hipMemcpyAsync(&n_trunc, d_stat + 1, 8, hipMemcpyDeviceToHost, s));
     TK_HIP(c, hipStreamSynchronize(s));
-    out->ids = c->dn_ids.p;
-    out->mask = mask ? (uint8_t*)c->dn_mask.p : nullptr;
-    out->lengths = (uint32_t*)c->dn_len.p;
+    out->ids = c->dense.ids.p;
+    out->mask = mask ? (uint8_t*)c->dense.mask.p : nullptr;
+    out->lengths = (uint32_t*)c->dense.len.p;
     out->n_docs = n_docs;
     out->row_len = L;
     out->n_truncated = n_trunc;
     return TK_OK;
 }
 
+namespace {
+struct DensePass : LayoutPass<DensePass> {
+    typedef tk_dense_opts Opts;
+    typedef tk_dense Result;
+    static constexpr const char* name = "dense";
+    static uint64_t esz(const Opts& o) { return (o.flags & TK_DENSE_I64) ? 8 : 4; }
+    static constexpr auto encode_opts = dense_encode_opts;
+    static int run(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t, const Opts* o, hipStream_t s, Result* out) {
+        return run_dense(c, d_ids, d_id_offs, n_docs, o, s, out);   // (the offsets say how many ids there are)
+    }
+};
+}  // namespace
+
 extern "C" int tk_dense_from_ids_device(tk_ctx* c, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
                                         const tk_dense_opts* opts, void* hip_stream, tk_dense* out) {
-    TK_ENTRY(c);
-    if (!d_id_offsets || (!d_ids && n_ids) || !opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    TK_HIP(c, hipSetDevice(c->device));
-    return run_dense(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_docs, opts, (hipStream_t)hip_stream, out);
+    return layout_from_ids_device<DensePass>(c, d_ids, d_id_offsets, n_docs, n_ids, opts, hip_stream, out);
 }
-
 extern "C" int tk_encode_batch_device_dense(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs,
                                             uint64_t n_bytes, int add_bos, int add_eos, int checks, const tk_dense_opts* opts,
                                             void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_dense* out) {
-    TK_ENTRY(c);
-    int rc = check_flags_and_args(c, checks, TK_CHECK_OFFSETS | TK_CHECK_UTF8, !opts || !out);
-    if (rc != TK_OK) return rc;
-    tk_dense_opts o;
-    if ((rc = dense_encode_opts(c, opts, add_bos, add_eos, &o)) != TK_OK) return rc;
-    rc = encode_device_checked(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, hip_stream, d_ids, d_out_offsets, n_ids);
-    if (rc != TK_OK) return rc;
-    return run_dense(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, &o, (hipStream_t)hip_stream, out);
+    return layout_encode_device<DensePass>(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, opts, hip_stream, d_ids,
+                                           d_out_offsets, n_ids, out);
 }
-
-extern "C" void tk_free_dense(tk_dense* r) {
-    if (!r) return;
-    tk_pinned_put(r->ids);
-    tk_pinned_put(r->mask);
-    tk_pinned_put(r->lengths);
-    memset(r, 0, sizeof(*r));
-}
-
 extern "C" int tk_encode_batch_dense(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
                                      int add_eos, int validate_utf8, const tk_dense_opts* opts, tk_dense* out) {
-    TK_ENTRY(c);
-    if (!opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    memset(out, 0, sizeof(*out));
-    tk_dense_opts o;
-    int rc = dense_encode_opts(c, opts, add_bos, add_eos, &o);
-    if (rc != TK_OK) return rc;
-    DevBatch dev;
-    uint64_t n_ids;
-    if ((rc = encode_batch_for_layout(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &dev, &n_ids)) != TK_OK) return rc;
-    tk_dense d;
-    rc = run_dense(c, dev.ids, dev.id_offs, n_docs, &o, c->stream, &d);
-    if (rc != TK_OK) return rc;
-    const uint64_t elems = d.n_docs * d.row_len, esz = (o.flags & TK_DENSE_I64) ? 8 : 4;
-    CopyOut h[3] = {{d.ids, elems * esz, nullptr}, {d.mask, elems, nullptr, d.mask != nullptr}, {d.lengths, n_docs * 4, nullptr}};
-    if ((rc = copy_out(c, h, 3, "dense")) != TK_OK) return rc;
-    *out = d;
-    out->ids = h[0].host;
-    out->mask = (uint8_t*)h[1].host;
-    out->lengths = (uint32_t*)h[2].host;
-    return TK_OK;
+    return layout_encode_host<DensePass>(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, opts, out);
 }
+extern "C" void tk_free_dense(tk_dense* r) { layout_free(r); }
 
 extern "C" int tk_ragged_from_dense_device(tk_ctx* c, const void* d_dense, uint64_t n_docs, uint64_t row_len, int flags,
                                            const void* d_lengths, uint32_t pad_id, void* hip_stream, void** d_ids,
@@ -156,9 +132,9 @@ extern "C" int tk_ragged_from_dense_device(tk_ctx* c, const void* d_dense, uint6
     hipStream_t s = (hipStream_t)hip_stream;
     const int i64 = (flags & TK_DENSE_I64) != 0;
     // (the ids are sized by the tensor, an upper bound of what the rows hold: no host read between the scan and the copy)
-    TK_HIP(c, c->dn_rids.reserve(n_docs * row_len * 4 + 16));
-    TK_HIP(c, c->dn_roffs.reserve((n_docs + 1) * 8));
-    TK_HIP(c, c->dn_rlens.reserve(n_docs * 4 + 16));
+    TK_HIP(c, c->dense.rids.reserve(n_docs * row_len * 4 + 16));
+    TK_HIP(c, c->dense.roffs.reserve((n_docs + 1) * 8));
+    TK_HIP(c, c->dense.rlens.reserve(n_docs * 4 + 16));
     TK_HIP(c, c->block_sums.reserve(scan_workspace_bytes(n_docs)));
     TkRaggedArgs a;
     memset(&a, 0, sizeof(a));
@@ -168,23 +144,23 @@ extern "C" int tk_ragged_from_dense_device(tk_ctx* c, const void* d_dense, uint6
     a.pad_id = pad_id;
     a.pad_left = (flags & TK_DENSE_PAD_LEFT) != 0;
     a.given = (const uint32_t*)d_lengths;
-    a.lens = (uint32_t*)c->dn_rlens.p;
-    a.offs = (const uint64_t*)c->dn_roffs.p;
-    a.out_ids = (uint32_t*)c->dn_rids.p;
+    a.lens = (uint32_t*)c->dense.rlens.p;
+    a.offs = (const uint64_t*)c->dense.roffs.p;
+    a.out_ids = (uint32_t*)c->dense.rids.p;
     uint64_t total = 0;
     if (n_docs == 0) {
-        TK_HIP(c, hipMemsetAsync(c->dn_roffs.p, 0, 8, s));
+        TK_HIP(c, hipMemsetAsync(c->dense.roffs.p, 0, 8, s));
     } else {
-        if (row_len == 0) TK_HIP(c, hipMemsetAsync(c->dn_rlens.p, 0, n_docs * 4, s));
+        if (row_len == 0) TK_HIP(c, hipMemsetAsync(c->dense.rlens.p, 0, n_docs * 4, s));
         else TK_HIP(c, tk_launch_ragged_rowlen(a, i64, s));
-        int rc = scan_u32(c, c->block_sums, a.lens, n_docs, (uint64_t*)c->dn_roffs.p, s);
+        int rc = scan_u32(c, c->block_sums, a.lens, n_docs, (uint64_t*)c->dense.roffs.p, s);
         if (rc != TK_OK) return rc;
         TK_HIP(c, tk_launch_ragged_copy(a, i64, s));
-        TK_HIP(c, hipMemcpyAsync(&total, (const uint64_t*)c->dn_roffs.p + n_docs, 8, hipMemcpyDeviceToHost, s));
+        TK_HIP(c, hipMemcpyAsync(&total, (const uint64_t*)c->dense.roffs.p + n_docs, 8, hipMemcpyDeviceToHost, s));
     }
     TK_HIP(c, hipStreamSynchronize(s));
-    *d_ids = c->dn_rids.p;
-    *d_id_offsets = c->dn_roffs.p;
+    *d_ids = c->dense.rids.p;
+    *d_id_offsets = c->dense.roffs.p;
     *n_ids = total;
     return TK_OK;
 }

@@ -1,7 +1,7 @@
 // tk_capi_join.cpp -- chat batches (include/tekken_hip.h tk_join_from_ids_device and the entries around it; csrc/tk_join.hip):
 // the ids of text parts, encoded one by one, joined with control ids into one stream per conversation, with labels and the part
 // index of every element.
-#include "tk_ctx.h"
+#include "tk_capi_layout.h"
 
 #define TK_JOIN_ALL_FLAGS (TK_JOIN_LABELS | TK_JOIN_PART_INDEX)
 
@@ -38,11 +38,11 @@ static int check_parts_host(tk_ctx* c, const uint32_t* ctrl, const uint64_t* con
 
 // TK_CHECK_PARTS on the device: one small kernel and one wait, before any buffer of an earlier result is given up
 static int check_parts_device(tk_ctx* c, const uint32_t* d_ctrl, const uint64_t* d_conv, uint64_t P, uint64_t C, hipStream_t s) {
-    TK_HIP(c, c->jn_stat.reserve(64));
+    TK_HIP(c, c->join.stat.reserve(64));
     TkJoinArgs a;
     memset(&a, 0, sizeof(a));
     a.n_parts = P; a.n_convs = C; a.ctrl = d_ctrl; a.conv_offs = d_conv; a.num_special = c->host.num_special;
-    a.stat = (unsigned long long*)c->jn_stat.p;
+    a.stat = (unsigned long long*)c->join.stat.p;
     unsigned long long bad[2] = {0, 0};
     TK_HIP(c, hipMemsetAsync(a.stat + 1, 0xFF, 16, s));
     TK_HIP(c, tk_launch_join_check(a, s));
@@ -57,7 +57,7 @@ static int check_parts_device(tk_ctx* c, const uint32_t* d_ctrl, const uint64_t*
     return TK_OK;
 }
 
-// The join over ids on the device into the context's jn_* buffers; *out gets the device pointers.  The outputs are sized for
+// The join over ids on the device into the context's c->join buffers; *out gets the device pointers.  The outputs are sized for
 // n_ids + n_parts elements, so nothing is read before the launches; ONE wait at the end (N, n_ctrl, n_labelled).  Nothing of an
 // earlier result is touched before every argument has been accepted.  The caller holds c->mu.
 static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t P, uint64_t n_ids, const uint32_t* d_ctrl,
@@ -69,20 +69,20 @@ static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs,
     if (check_parts && (rc = check_parts_device(c, d_ctrl, d_conv, P, C, s)) != TK_OK) return rc;
     const bool want_lab = (o->flags & TK_JOIN_LABELS) != 0, want_pi = (o->flags & TK_JOIN_PART_INDEX) != 0;
     const uint64_t cap = n_ids + P;
-    TK_HIP(c, c->jn_stat.reserve(64));
-    TK_HIP(c, c->jn_ids.reserve(cap * 4 + 16));
-    TK_HIP(c, c->jn_offs.reserve((C + 1) * 8));
-    if (want_lab) TK_HIP(c, c->jn_labels.reserve(cap * 4 + 16));
-    if (want_pi) TK_HIP(c, c->jn_pidx.reserve(cap * 4 + 16));
+    TK_HIP(c, c->join.stat.reserve(64));
+    TK_HIP(c, c->join.ids.reserve(cap * 4 + 16));
+    TK_HIP(c, c->join.offs.reserve((C + 1) * 8));
+    if (want_lab) TK_HIP(c, c->join.labels.reserve(cap * 4 + 16));
+    if (want_pi) TK_HIP(c, c->join.pidx.reserve(cap * 4 + 16));
     unsigned long long got[3] = {0, 0, 0};      // N, n_ctrl, n_labelled
     if (P == 0) {                               // (no part: offsets = [0] * (C + 1), nothing to launch)
-        TK_HIP(c, hipMemsetAsync(c->jn_offs.p, 0, (C + 1) * 8, s));
+        TK_HIP(c, hipMemsetAsync(c->join.offs.p, 0, (C + 1) * 8, s));
     } else {
-        TK_HIP(c, c->jn_has.reserve(P * 4 + 16));
-        TK_HIP(c, c->jn_cb.reserve((P + 1) * 8));
-        TK_HIP(c, c->jn_start.reserve((P + 1) * 8));
-        if (want_pi) TK_HIP(c, c->jn_plocal.reserve(P * 4 + 16));
-        TK_HIP(c, c->jn_bsum.reserve(scan_workspace_bytes(P)));
+        TK_HIP(c, c->join.has.reserve(P * 4 + 16));
+        TK_HIP(c, c->join.cb.reserve((P + 1) * 8));
+        TK_HIP(c, c->join.start.reserve((P + 1) * 8));
+        if (want_pi) TK_HIP(c, c->join.plocal.reserve(P * 4 + 16));
+        TK_HIP(c, c->join.bsum.reserve(scan_workspace_bytes(P)));
         TkJoinArgs a;
         memset(&a, 0, sizeof(a));
         a.ids = d_ids;
@@ -95,18 +95,18 @@ static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs,
         a.cap = cap;
         a.num_special = c->host.num_special;
         a.ignore = o->ignore_index;
-        a.has = (uint32_t*)c->jn_has.p;
-        a.cb = (const uint64_t*)c->jn_cb.p;
-        a.start = (uint64_t*)c->jn_start.p;
-        a.plocal = (uint32_t*)c->jn_plocal.p;
-        a.out_ids = (uint32_t*)c->jn_ids.p;
-        a.out_offs = (uint64_t*)c->jn_offs.p;
-        a.labels = want_lab ? (int32_t*)c->jn_labels.p : nullptr;
-        a.part_index = want_pi ? (uint32_t*)c->jn_pidx.p : nullptr;
-        a.stat = (unsigned long long*)c->jn_stat.p;
+        a.has = (uint32_t*)c->join.has.p;
+        a.cb = (const uint64_t*)c->join.cb.p;
+        a.start = (uint64_t*)c->join.start.p;
+        a.plocal = (uint32_t*)c->join.plocal.p;
+        a.out_ids = (uint32_t*)c->join.ids.p;
+        a.out_offs = (uint64_t*)c->join.offs.p;
+        a.labels = want_lab ? (int32_t*)c->join.labels.p : nullptr;
+        a.part_index = want_pi ? (uint32_t*)c->join.pidx.p : nullptr;
+        a.stat = (unsigned long long*)c->join.stat.p;
         TK_HIP(c, hipMemsetAsync(a.stat, 0, 8, s));
         TK_HIP(c, tk_launch_join_has(a, s));
-        if ((rc = scan_u32(c, c->jn_bsum, a.has, P, (uint64_t*)c->jn_cb.p, s)) != TK_OK) return rc;
+        if ((rc = scan_u32(c, c->join.bsum, a.has, P, (uint64_t*)c->join.cb.p, s)) != TK_OK) return rc;
         TK_HIP(c, tk_launch_join_parts(a, s));
         TK_HIP(c, tk_launch_join(a, s));
         TK_HIP(c, hipMemcpyAsync(got, a.start + P, 8, hipMemcpyDeviceToHost, s));
@@ -118,10 +118,10 @@ static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs,
         c->err = "join: id_offsets end at " + std::to_string(got[0] - got[1]) + ", beyond n_ids = " + std::to_string(n_ids);
         return TK_ERR_INVALID_ARG;
     }
-    out->ids = (uint32_t*)c->jn_ids.p;
-    out->offsets = (uint64_t*)c->jn_offs.p;
-    out->labels = want_lab ? (int32_t*)c->jn_labels.p : nullptr;
-    out->part_index = want_pi ? (uint32_t*)c->jn_pidx.p : nullptr;
+    out->ids = (uint32_t*)c->join.ids.p;
+    out->offsets = (uint64_t*)c->join.offs.p;
+    out->labels = want_lab ? (int32_t*)c->join.labels.p : nullptr;
+    out->part_index = want_pi ? (uint32_t*)c->join.pidx.p : nullptr;
     out->n_convs = C;
     out->n_parts = P;
     out->n_ids = got[0];
@@ -169,14 +169,7 @@ extern "C" int tk_encode_parts_device_join(tk_ctx* c, const void* d_bytes, const
                                     opts, hip_stream, out);
 }
 
-extern "C" void tk_free_join(tk_join* r) {
-    if (!r) return;
-    tk_pinned_put(r->ids);
-    tk_pinned_put(r->offsets);
-    tk_pinned_put(r->labels);
-    tk_pinned_put(r->part_index);
-    memset(r, 0, sizeof(*r));
-}
+extern "C" void tk_free_join(tk_join* r) { layout_free(r); }
 
 extern "C" int tk_encode_parts_join(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_parts, const uint32_t* part_ctrl,
                                     const uint32_t* part_flags, const uint64_t* conv_offsets, uint64_t n_convs, int validate_utf8,
@@ -190,25 +183,15 @@ extern "C" int tk_encode_parts_join(tk_ctx* c, const uint8_t* bytes, const uint6
     DevBatch dev;
     uint64_t n_ids;
     if ((rc = encode_batch_for_layout(c, bytes, doc_offsets, n_parts, 0, 0, validate_utf8, &dev, &n_ids)) != TK_OK) return rc;
-    TK_HIP(c, c->jn_in_ctrl.reserve(n_parts * 4 + 16));
-    TK_HIP(c, c->jn_in_flags.reserve(n_parts * 4 + 16));
-    TK_HIP(c, c->jn_in_conv.reserve((n_convs + 1) * 8));
-    if (n_parts) TK_HIP(c, hipMemcpyAsync(c->jn_in_ctrl.p, part_ctrl, n_parts * 4, hipMemcpyHostToDevice, c->stream));
-    if (n_parts && part_flags) TK_HIP(c, hipMemcpyAsync(c->jn_in_flags.p, part_flags, n_parts * 4, hipMemcpyHostToDevice, c->stream));
-    TK_HIP(c, hipMemcpyAsync(c->jn_in_conv.p, conv_offsets, (n_convs + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    TK_HIP(c, c->join.in_ctrl.reserve(n_parts * 4 + 16));
+    TK_HIP(c, c->join.in_flags.reserve(n_parts * 4 + 16));
+    TK_HIP(c, c->join.in_conv.reserve((n_convs + 1) * 8));
+    if (n_parts) TK_HIP(c, hipMemcpyAsync(c->join.in_ctrl.p, part_ctrl, n_parts * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_parts && part_flags) TK_HIP(c, hipMemcpyAsync(c->join.in_flags.p, part_flags, n_parts * 4, hipMemcpyHostToDevice, c->stream));
+    TK_HIP(c, hipMemcpyAsync(c->join.in_conv.p, conv_offsets, (n_convs + 1) * 8, hipMemcpyHostToDevice, c->stream));
     tk_join j;
-    rc = run_join(c, dev.ids, dev.id_offs, n_parts, n_ids, (const uint32_t*)c->jn_in_ctrl.p, part_flags ? (const uint32_t*)c->jn_in_flags.p : nullptr,
-                  (const uint64_t*)c->jn_in_conv.p, n_convs, false, opts, c->stream, &j);
+    rc = run_join(c, dev.ids, dev.id_offs, n_parts, n_ids, (const uint32_t*)c->join.in_ctrl.p, part_flags ? (const uint32_t*)c->join.in_flags.p : nullptr,
+                  (const uint64_t*)c->join.in_conv.p, n_convs, false, opts, c->stream, &j);
     if (rc != TK_OK) return rc;
-    const uint64_t n4 = (j.n_ids ? j.n_ids : 1) * 4;     // (no id: no device source, the block alone)
-    CopyOut h[4] = {{j.n_ids ? j.ids : nullptr, n4, nullptr}, {j.offsets, (n_convs + 1) * 8, nullptr},
-                    {j.n_ids ? j.labels : nullptr, n4, nullptr, j.labels != nullptr},
-                    {j.n_ids ? j.part_index : nullptr, n4, nullptr, j.part_index != nullptr}};
-    if ((rc = copy_out(c, h, 4, "join")) != TK_OK) return rc;
-    *out = j;
-    out->ids = (uint32_t*)h[0].host;
-    out->offsets = (uint64_t*)h[1].host;
-    out->labels = (int32_t*)h[2].host;
-    out->part_index = (uint32_t*)h[3].host;
-    return TK_OK;
+    return layout_copy_out(c, j, 4, n_convs, "join", out);
 }

@@ -1,6 +1,6 @@
 // tk_capi_seqpack.cpp -- packed fixed-length training rows (include/tekken_hip.h tk_seqpack_from_ids_device and the entries
 // around it; csrc/tk_seqpack.hip): the stream of all ids cut into rows of seq_len, with position_ids, segment_ids and cu_seqlens.
-#include "tk_ctx.h"
+#include "tk_capi_layout.h"
 
 #define TK_SEQPACK_ALL_FLAGS (TK_SEQPACK_I64 | TK_SEQPACK_POSITIONS | TK_SEQPACK_SEGMENTS | TK_SEQPACK_CU_SEQLENS | TK_SEQPACK_DROP_LAST)
 
@@ -13,7 +13,7 @@ static int seqpack_check_opts(tk_ctx* c, const tk_seqpack_opts* o) {
     return TK_OK;
 }
 
-// The packed pass over ids on the device into the context's sp_* buffers; *out gets the device pointers.  n_rows, n_used and
+// The packed pass over ids on the device into the context's c->seqpack buffers; *out gets the device pointers.  n_rows, n_used and
 // n_left follow from n_ids on the host, so nothing is read before the launches; ONE wait at the end (n_segments, max_seqlen).
 // Nothing of an earlier result is touched before every argument has been accepted.  The caller holds c->mu.
 static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids,
@@ -36,22 +36,22 @@ static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_of
         return TK_ERR_INVALID_ARG;
     }
     const uint64_t elems = n_rows * L, esz = i64 ? 8 : 4;
-    TK_HIP(c, c->sp_stat.reserve(64));
-    TK_HIP(c, c->sp_ids.reserve(elems * esz + 16));
-    if (want_pos) TK_HIP(c, c->sp_pos.reserve(elems * esz + 16));
-    if (want_seg) TK_HIP(c, c->sp_seg.reserve(elems * esz + 16));
-    if (want_cu) TK_HIP(c, c->sp_cu.reserve((n_docs + n_rows + 2) * 4));
+    TK_HIP(c, c->seqpack.stat.reserve(64));
+    TK_HIP(c, c->seqpack.ids.reserve(elems * esz + 16));
+    if (want_pos) TK_HIP(c, c->seqpack.pos.reserve(elems * esz + 16));
+    if (want_seg) TK_HIP(c, c->seqpack.seg.reserve(elems * esz + 16));
+    if (want_cu) TK_HIP(c, c->seqpack.cu.reserve((n_docs + n_rows + 2) * 4));
     unsigned long long stat[2] = {0, 0};
     if (n_used == 0) {                          // (no row: cu_seqlens = [0], nothing to launch)
-        if (want_cu) TK_HIP(c, hipMemsetAsync(c->sp_cu.p, 0, 4, s));
+        if (want_cu) TK_HIP(c, hipMemsetAsync(c->seqpack.cu.p, 0, 4, s));
     } else {
-        TK_HIP(c, c->sp_flags.reserve(n_docs * 4 + 16));
-        TK_HIP(c, c->sp_aflags.reserve(n_docs * 4 + 16));
-        TK_HIP(c, c->sp_fpos.reserve((n_docs + 1) * 8));
-        TK_HIP(c, c->sp_apos.reserve((n_docs + 1) * 8));
-        TK_HIP(c, c->sp_starts.reserve((n_docs + 1) * 8));
-        TK_HIP(c, c->sp_aligned.reserve((n_docs + 1) * 8));
-        TK_HIP(c, c->sp_bsum.reserve(scan_workspace_bytes(n_docs)));
+        TK_HIP(c, c->seqpack.flags.reserve(n_docs * 4 + 16));
+        TK_HIP(c, c->seqpack.aflags.reserve(n_docs * 4 + 16));
+        TK_HIP(c, c->seqpack.fpos.reserve((n_docs + 1) * 8));
+        TK_HIP(c, c->seqpack.apos.reserve((n_docs + 1) * 8));
+        TK_HIP(c, c->seqpack.starts.reserve((n_docs + 1) * 8));
+        TK_HIP(c, c->seqpack.aligned.reserve((n_docs + 1) * 8));
+        TK_HIP(c, c->seqpack.bsum.reserve(scan_workspace_bytes(n_docs)));
         TkSeqpackArgs a;
         memset(&a, 0, sizeof(a));
         a.ids = d_ids;
@@ -61,31 +61,31 @@ static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_of
         a.pad_id = o->pad_id;
         a.n_rows = n_rows;
         a.n_used = n_used;
-        a.flags = (uint32_t*)c->sp_flags.p;
-        a.aflags = (uint32_t*)c->sp_aflags.p;
-        a.fpos = (const uint64_t*)c->sp_fpos.p;
-        a.apos = (const uint64_t*)c->sp_apos.p;
-        a.starts = (uint64_t*)c->sp_starts.p;
-        a.n_aligned = (uint64_t*)c->sp_aligned.p;
-        a.out_ids = c->sp_ids.p;
-        a.out_pos = want_pos ? c->sp_pos.p : nullptr;
-        a.out_seg = want_seg ? c->sp_seg.p : nullptr;
-        a.cu = want_cu ? (int32_t*)c->sp_cu.p : nullptr;
-        a.stat = (unsigned long long*)c->sp_stat.p;
+        a.flags = (uint32_t*)c->seqpack.flags.p;
+        a.aflags = (uint32_t*)c->seqpack.aflags.p;
+        a.fpos = (const uint64_t*)c->seqpack.fpos.p;
+        a.apos = (const uint64_t*)c->seqpack.apos.p;
+        a.starts = (uint64_t*)c->seqpack.starts.p;
+        a.n_aligned = (uint64_t*)c->seqpack.aligned.p;
+        a.out_ids = c->seqpack.ids.p;
+        a.out_pos = want_pos ? c->seqpack.pos.p : nullptr;
+        a.out_seg = want_seg ? c->seqpack.seg.p : nullptr;
+        a.cu = want_cu ? (int32_t*)c->seqpack.cu.p : nullptr;
+        a.stat = (unsigned long long*)c->seqpack.stat.p;
         TK_HIP(c, hipMemsetAsync(a.stat, 0, 16, s));
         TK_HIP(c, tk_launch_seqpack_flags(a, s));
-        if ((rc = scan_u32(c, c->sp_bsum, a.flags, n_docs, (uint64_t*)c->sp_fpos.p, s)) != TK_OK) return rc;
-        if ((rc = scan_u32(c, c->sp_bsum, a.aflags, n_docs, (uint64_t*)c->sp_apos.p, s)) != TK_OK) return rc;
+        if ((rc = scan_u32(c, c->seqpack.bsum, a.flags, n_docs, (uint64_t*)c->seqpack.fpos.p, s)) != TK_OK) return rc;
+        if ((rc = scan_u32(c, c->seqpack.bsum, a.aflags, n_docs, (uint64_t*)c->seqpack.apos.p, s)) != TK_OK) return rc;
         TK_HIP(c, tk_launch_seqpack_starts(a, s));
         TK_HIP(c, tk_launch_seqpack(a, i64, s));
         TK_HIP(c, tk_launch_seqpack_cu(a, s));
         TK_HIP(c, hipMemcpyAsync(stat, a.stat, 16, hipMemcpyDeviceToHost, s));
     }
     TK_HIP(c, hipStreamSynchronize(s));
-    out->input_ids = c->sp_ids.p;
-    out->position_ids = want_pos ? c->sp_pos.p : nullptr;
-    out->segment_ids = want_seg ? c->sp_seg.p : nullptr;
-    out->cu_seqlens = want_cu ? (int32_t*)c->sp_cu.p : nullptr;
+    out->input_ids = c->seqpack.ids.p;
+    out->position_ids = want_pos ? c->seqpack.pos.p : nullptr;
+    out->segment_ids = want_seg ? c->seqpack.seg.p : nullptr;
+    out->cu_seqlens = want_cu ? (int32_t*)c->seqpack.cu.p : nullptr;
     out->n_rows = n_rows;
     out->row_len = L;
     out->n_used = n_used;
@@ -95,56 +95,30 @@ static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_of
     return TK_OK;
 }
 
+namespace {
+struct SeqpackPass : LayoutPass<SeqpackPass> {
+    typedef tk_seqpack_opts Opts;
+    typedef tk_seqpack Result;
+    static constexpr const char* name = "seqpack";
+    static uint64_t esz(const Opts& o) { return (o.flags & TK_SEQPACK_I64) ? 8 : 4; }
+    // the options of an entry that encodes first are the caller's
+    static int encode_opts(tk_ctx* c, const Opts* opts, int, int, Opts* o) { *o = *opts; return seqpack_check_opts(c, o); }
+    static constexpr auto run = run_seqpack;
+};
+}  // namespace
+
 extern "C" int tk_seqpack_from_ids_device(tk_ctx* c, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
                                           const tk_seqpack_opts* opts, void* hip_stream, tk_seqpack* out) {
-    TK_ENTRY(c);
-    if (!d_id_offsets || (!d_ids && n_ids) || !opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    TK_HIP(c, hipSetDevice(c->device));
-    return run_seqpack(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_docs, n_ids, opts, (hipStream_t)hip_stream, out);
+    return layout_from_ids_device<SeqpackPass>(c, d_ids, d_id_offsets, n_docs, n_ids, opts, hip_stream, out);
 }
-
 extern "C" int tk_encode_batch_device_seqpack(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs,
                                               uint64_t n_bytes, int add_bos, int add_eos, int checks, const tk_seqpack_opts* opts,
                                               void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_seqpack* out) {
-    TK_ENTRY(c);
-    int rc = check_flags_and_args(c, checks, TK_CHECK_OFFSETS | TK_CHECK_UTF8, !opts || !out);
-    if (rc != TK_OK || (rc = seqpack_check_opts(c, opts)) != TK_OK) return rc;
-    rc = encode_device_checked(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, hip_stream, d_ids, d_out_offsets, n_ids);
-    if (rc != TK_OK) return rc;
-    return run_seqpack(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, *n_ids, opts, (hipStream_t)hip_stream, out);
+    return layout_encode_device<SeqpackPass>(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, opts, hip_stream, d_ids,
+                                             d_out_offsets, n_ids, out);
 }
-
-extern "C" void tk_free_seqpack(tk_seqpack* r) {
-    if (!r) return;
-    tk_pinned_put(r->input_ids);
-    tk_pinned_put(r->position_ids);
-    tk_pinned_put(r->segment_ids);
-    tk_pinned_put(r->cu_seqlens);
-    memset(r, 0, sizeof(*r));
-}
-
 extern "C" int tk_encode_batch_seqpack(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
                                        int add_eos, int validate_utf8, const tk_seqpack_opts* opts, tk_seqpack* out) {
-    TK_ENTRY(c);
-    if (!opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    memset(out, 0, sizeof(*out));
-    int rc = seqpack_check_opts(c, opts);
-    if (rc != TK_OK) return rc;
-    DevBatch dev;
-    uint64_t n_ids;
-    if ((rc = encode_batch_for_layout(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &dev, &n_ids)) != TK_OK) return rc;
-    tk_seqpack p;
-    rc = run_seqpack(c, dev.ids, dev.id_offs, n_docs, n_ids, opts, c->stream, &p);
-    if (rc != TK_OK) return rc;
-    const uint64_t bytes_t = p.n_rows * p.row_len * ((opts->flags & TK_SEQPACK_I64) ? 8 : 4);
-    CopyOut h[4] = {{p.input_ids, bytes_t, nullptr}, {p.position_ids, bytes_t, nullptr, p.position_ids != nullptr},
-                    {p.segment_ids, bytes_t, nullptr, p.segment_ids != nullptr},
-                    {p.cu_seqlens, (p.n_segments + 1) * 4, nullptr, p.cu_seqlens != nullptr}};
-    if ((rc = copy_out(c, h, 4, "seqpack")) != TK_OK) return rc;
-    *out = p;
-    out->input_ids = h[0].host;
-    out->position_ids = h[1].host;
-    out->segment_ids = h[2].host;
-    out->cu_seqlens = (int32_t*)h[3].host;
-    return TK_OK;
+    return layout_encode_host<SeqpackPass>(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, opts, out);
 }
+extern "C" void tk_free_seqpack(tk_seqpack* r) { layout_free(r); }

@@ -15,12 +15,12 @@ int doc_of_id(tk_ctx* c, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t id
     return TK_OK;
 }
 
-// The spans pass over ids on the device: (start, end) of every id into c->sp_spans, the checks of `checks` (TK_SPANS_CHECK_*
+// The spans pass over ids on the device: (start, end) of every id into c->spans.spans, the checks of `checks` (TK_SPANS_CHECK_*
 // only) in the same pass, one host wait for the error words.  The caller holds c->mu.  (Also the window entries' spans pass, and
 // -- into its own buffer -- the units pass in bytes.)
 int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids,
               const uint64_t* d_doc_offs, const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc, DevBuf* into) {
-    DevBuf& spans = into ? *into : c->sp_spans;
+    DevBuf& spans = into ? *into : c->spans.spans;
     if (checks & TK_SPANS_CHECK_BYTES) checks |= TK_SPANS_CHECK_COVER;
     if (((checks & TK_SPANS_CHECK_COVER) && !d_doc_offs) || ((checks & TK_SPANS_CHECK_BYTES) && !d_bytes)) {
         c->err = "the spans checks need the document offsets (COVER) and the text (BYTES)";
@@ -29,7 +29,7 @@ int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint6
     int rc = token_tables(c);
     if (rc != TK_OK) return rc;
     TK_HIP(c, spans.reserve(n_ids * 8 + 16));
-    TK_HIP(c, c->sp_err.reserve(64));
+    TK_HIP(c, c->spans.err.reserve(64));
     TkSpansArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = d_ids;
@@ -38,12 +38,12 @@ int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint6
     a.doc_offs = d_doc_offs;
     a.bytes = d_bytes;
     a.spans = (uint32_t*)spans.p;
-    a.err = (unsigned long long*)c->sp_err.p;
+    a.err = (unsigned long long*)c->spans.err.p;
     token_args(c, a);
     unsigned long long err[4] = {~0ull, ~0ull, ~0ull, ~0ull};
-    TK_HIP(c, hipMemsetAsync(c->sp_err.p, 0xFF, 32, s));
+    TK_HIP(c, hipMemsetAsync(c->spans.err.p, 0xFF, 32, s));
     TK_HIP(c, tk_launch_spans(a, checks, s));
-    TK_HIP(c, hipMemcpyAsync(err, c->sp_err.p, 32, hipMemcpyDeviceToHost, s));
+    TK_HIP(c, hipMemcpyAsync(err, c->spans.err.p, 32, hipMemcpyDeviceToHost, s));
     TK_HIP(c, hipStreamSynchronize(s));
     if (err[0] == ~0ull && err[1] == ~0ull && err[2] == ~0ull && err[3] == ~0ull) return TK_OK;
     // error path: name the first document that fails and say why
@@ -95,7 +95,7 @@ extern "C" int tk_token_spans_device(tk_ctx* c, const void* d_ids, const void* d
     int rc = run_spans(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_docs, n_ids, (const uint64_t*)d_doc_offsets,
                        (const uint8_t*)d_bytes, checks, s, bad_doc);
     if (rc != TK_OK) return rc;
-    *d_spans = c->sp_spans.p;
+    *d_spans = c->spans.spans.p;
     return TK_OK;
 }
 
@@ -112,7 +112,7 @@ extern "C" int tk_encode_batch_device_spans(tk_ctx* c, const void* d_bytes, cons
     rc = run_spans(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, *n_ids, (const uint64_t*)d_doc_offsets,
                    (const uint8_t*)d_bytes, checks & sp, (hipStream_t)hip_stream, bad_doc);
     if (rc != TK_OK) return rc;
-    *d_spans = c->sp_spans.p;
+    *d_spans = c->spans.spans.p;
     return TK_OK;
 }
 
@@ -127,7 +127,7 @@ extern "C" int tk_encode_batch_spans(tk_ctx* c, const uint8_t* bytes, const uint
     if (rc != TK_OK) return rc;
     // (the small path's ids, offsets and text are mapped pinned memory: the spans kernel reads them there)
     rc = run_spans(c, dev.ids, dev.id_offs, n_docs, out->n_ids, dev.doc_offs, dev.bytes, checks, c->stream, bad_doc);
-    CopyOut h = {c->sp_spans.p, out->n_ids * 8, nullptr};
+    CopyOut h = {c->spans.spans.p, out->n_ids * 8, nullptr};
     if (rc != TK_OK || (rc = copy_out(c, &h, 1, "spans")) != TK_OK) {
         tk_free_result(out);
         return rc;

@@ -5,12 +5,12 @@
 
 // the per-rank entries of the units kernel, built at the first units call on the context
 static int units_table(tk_ctx* c) {
-    if (c->t_units.p) return TK_OK;
+    if (c->units.table.p) return TK_OK;
     const TkHostTables& h = c->host;
     std::vector<uint16_t> tab((size_t)h.n_ranks + 8, 0);
     tk_units_table_build(h.blob.data(), h.offs.data(), h.n_ranks, tab.data());
-    const int rc = upload(c, c->t_units, tab.data(), tab.size() * 2);
-    if (rc != TK_OK) c->t_units.release();             // (the pointer is the "built" flag: a failed copy must not leave it set)
+    const int rc = upload(c, c->units.table, tab.data(), tab.size() * 2);
+    if (rc != TK_OK) c->units.table.release();             // (the pointer is the "built" flag: a failed copy must not leave it set)
     return rc;
 }
 
@@ -20,31 +20,31 @@ static int check_unit(tk_ctx* c, int unit) {
     return TK_ERR_INVALID_ARG;
 }
 
-// The units pass over ids on the device: (start, end) of every id in `unit` into c->su_spans, one host wait for the error words.
+// The units pass over ids on the device: (start, end) of every id in `unit` into c->units.spans, one host wait for the error words.
 // TK_UNIT_BYTE is the byte kernel into the same buffer.  The caller holds c->mu.
 static int run_spans_units(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, int unit,
                            hipStream_t s) {
-    if (unit == TK_UNIT_BYTE) return run_spans(c, d_ids, d_id_offs, n_docs, n_ids, nullptr, nullptr, 0, s, nullptr, &c->su_spans);
+    if (unit == TK_UNIT_BYTE) return run_spans(c, d_ids, d_id_offs, n_docs, n_ids, nullptr, nullptr, 0, s, nullptr, &c->units.spans);
     int rc = units_table(c);
     if (rc != TK_OK) return rc;
-    TK_HIP(c, c->su_spans.reserve(n_ids * 8 + 16));
-    TK_HIP(c, c->su_err.reserve(64));
+    TK_HIP(c, c->units.spans.reserve(n_ids * 8 + 16));
+    TK_HIP(c, c->units.err.reserve(64));
     TkSpansUnitsArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = d_ids;
     a.id_offs = d_id_offs;
     a.n_docs = n_docs;
-    a.spans = (uint32_t*)c->su_spans.p;
-    a.err = (unsigned long long*)c->su_err.p;
+    a.spans = (uint32_t*)c->units.spans.p;
+    a.err = (unsigned long long*)c->units.err.p;
     a.tok_blob = (const uint8_t*)c->t_blob.p;
     a.tok_offs = (const uint32_t*)c->t_offs.p;
-    a.tok_units = (const uint16_t*)c->t_units.p;
+    a.tok_units = (const uint16_t*)c->units.table.p;
     a.n_ranks = c->host.n_ranks;
     a.num_special = c->host.num_special;
     unsigned long long err[4] = {~0ull, ~0ull, ~0ull, ~0ull};
-    TK_HIP(c, hipMemsetAsync(c->su_err.p, 0xFF, 32, s));
+    TK_HIP(c, hipMemsetAsync(c->units.err.p, 0xFF, 32, s));
     TK_HIP(c, tk_launch_spans_units(a, unit, s));
-    TK_HIP(c, hipMemcpyAsync(err, c->su_err.p, 32, hipMemcpyDeviceToHost, s));
+    TK_HIP(c, hipMemcpyAsync(err, c->units.err.p, 32, hipMemcpyDeviceToHost, s));
     TK_HIP(c, hipStreamSynchronize(s));
     for (int k = 2; k < 4; ++k) {
         if (err[k] == ~0ull) continue;
@@ -71,7 +71,7 @@ extern "C" int tk_token_spans_units_device(tk_ctx* c, const void* d_ids, const v
     TK_HIP(c, hipSetDevice(c->device));
     rc = run_spans_units(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_docs, n_ids, unit, (hipStream_t)hip_stream);
     if (rc != TK_OK) return rc;
-    *d_spans = c->su_spans.p;
+    *d_spans = c->units.spans.p;
     return TK_OK;
 }
 
@@ -86,7 +86,7 @@ extern "C" int tk_encode_batch_device_spans_units(tk_ctx* c, const void* d_bytes
     if (rc != TK_OK) return rc;
     rc = run_spans_units(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, *n_ids, unit, (hipStream_t)hip_stream);
     if (rc != TK_OK) return rc;
-    *d_spans = c->su_spans.p;
+    *d_spans = c->units.spans.p;
     return TK_OK;
 }
 
@@ -101,7 +101,7 @@ extern "C" int tk_encode_batch_spans_units(tk_ctx* c, const uint8_t* bytes, cons
     if ((rc = encode_batch(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, out, &dev)) != TK_OK) return rc;
     // (the small path's ids and offsets are mapped pinned memory: the units kernel reads them there)
     rc = run_spans_units(c, dev.ids, dev.id_offs, n_docs, out->n_ids, unit, c->stream);
-    CopyOut h = {c->su_spans.p, out->n_ids * 8, nullptr};
+    CopyOut h = {c->units.spans.p, out->n_ids * 8, nullptr};
     if (rc != TK_OK || (rc = copy_out(c, &h, 1, "spans")) != TK_OK) {
         tk_free_result(out);
         return rc;
@@ -119,8 +119,8 @@ extern "C" int tk_spans_locate_device(tk_ctx* c, const void* d_spans, const void
     TK_HIP(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
     // the ranges go to the work buffer; it becomes the result (a swap of the two) only once every annotation is accepted
-    TK_HIP(c, c->lc_next.reserve(n_ann * 8 + 16));
-    TK_HIP(c, c->lc_err.reserve(64));
+    TK_HIP(c, c->units.next.reserve(n_ann * 8 + 16));
+    TK_HIP(c, c->units.range_err.reserve(64));
     TkLocateArgs a;
     memset(&a, 0, sizeof(a));
     a.spans = (const uint32_t*)d_spans;
@@ -130,19 +130,19 @@ extern "C" int tk_spans_locate_device(tk_ctx* c, const void* d_spans, const void
     a.ann_doc = (const uint32_t*)d_ann_doc;
     a.ann = (const uint32_t*)d_ann;
     a.n_ann = n_ann;
-    a.out = (uint32_t*)c->lc_next.p;
-    a.err = (unsigned long long*)c->lc_err.p;
+    a.out = (uint32_t*)c->units.next.p;
+    a.err = (unsigned long long*)c->units.range_err.p;
     unsigned long long err = ~0ull;
-    TK_HIP(c, hipMemsetAsync(c->lc_err.p, 0xFF, 8, s));
+    TK_HIP(c, hipMemsetAsync(c->units.range_err.p, 0xFF, 8, s));
     TK_HIP(c, tk_launch_spans_locate(a, s));
-    TK_HIP(c, hipMemcpyAsync(&err, c->lc_err.p, 8, hipMemcpyDeviceToHost, s));
+    TK_HIP(c, hipMemcpyAsync(&err, c->units.range_err.p, 8, hipMemcpyDeviceToHost, s));
     TK_HIP(c, hipStreamSynchronize(s));
     if (err != ~0ull) {
         if (bad_ann) *bad_ann = err;
         c->err = "locate: annotation " + std::to_string(err) + " names a document beyond n_docs or starts behind its end";
         return TK_ERR_INVALID_ARG;
     }
-    std::swap(c->lc_range, c->lc_next);
-    *d_tok_range = c->lc_range.p;
+    std::swap(c->units.range, c->units.next);
+    *d_tok_range = c->units.range.p;
     return TK_OK;
 }

@@ -1,7 +1,7 @@
 // tk_capi_window.cpp -- overlapping windows for long documents (include/tekken_hip.h tk_window_from_ids_device and the entries
 // around it; csrc/tk_window.hip): every document longer than max_length split into windows that overlap by stride ids, with the
 // mapping back to the documents.
-#include "tk_ctx.h"
+#include "tk_capi_layout.h"
 
 #define TK_WINDOW_ALL_FLAGS (TK_WINDOW_FIXED | TK_WINDOW_I64 | TK_WINDOW_MASK | TK_WINDOW_SPANS)
 
@@ -31,7 +31,7 @@ static int window_encode_opts(tk_ctx* c, const tk_window_opts* opts, int add_bos
 }
 static uint64_t round_up(uint64_t L, uint64_t m) { return m ? (L + m - 1) / m * m : L; }
 
-// The window pass over ids on the device into the context's wn_* buffers; *out gets the device pointers.  The per-document counts
+// The window pass over ids on the device into the context's c->window buffers; *out gets the device pointers.  The per-document counts
 // and their scan go to work buffers; ONE read (W, the longest document, n_split) sizes the tensor, and only once the sizes are
 // accepted is anything of an earlier result touched (the scan becomes doc_windows by a swap of the two buffers).  One wait ends
 // the call.  The caller holds c->mu.
@@ -48,10 +48,10 @@ static int run_window(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
         c->err = "windows: max_length rounded up to a multiple of " + std::to_string(o->multiple_of) + " is beyond 2^31 - 1";
         return TK_ERR_INVALID_ARG;
     }
-    TK_HIP(c, c->wn_stat.reserve(64));
-    TK_HIP(c, c->wn_cnt.reserve(n_docs * 4 + 16));
-    TK_HIP(c, c->wn_dw_next.reserve((n_docs + 1) * 8));
-    TK_HIP(c, c->wn_bsum.reserve(scan_workspace_bytes(n_docs)));
+    TK_HIP(c, c->window.stat.reserve(64));
+    TK_HIP(c, c->window.cnt.reserve(n_docs * 4 + 16));
+    TK_HIP(c, c->window.dw_next.reserve((n_docs + 1) * 8));
+    TK_HIP(c, c->window.bsum.reserve(scan_workspace_bytes(n_docs)));
     TkWindowArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = d_ids;
@@ -63,17 +63,17 @@ static int run_window(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
     a.keep_head = o->keep_head;
     a.keep_tail = o->keep_tail;
     a.pad_id = o->pad_id;
-    a.counts = (uint32_t*)c->wn_cnt.p;
-    a.stat = (unsigned long long*)c->wn_stat.p;
+    a.counts = (uint32_t*)c->window.cnt.p;
+    a.stat = (unsigned long long*)c->window.stat.p;
     unsigned long long stat[2] = {0, 0};            // the longest document | the split ones
     uint64_t W = 0;
     if (n_docs == 0) {
-        TK_HIP(c, hipMemsetAsync(c->wn_dw_next.p, 0, 8, s));
+        TK_HIP(c, hipMemsetAsync(c->window.dw_next.p, 0, 8, s));
     } else {
         TK_HIP(c, hipMemsetAsync(a.stat, 0, 16, s));
         TK_HIP(c, tk_launch_window_counts(a, s));
-        if ((rc = scan_u32(c, c->wn_bsum, a.counts, n_docs, (uint64_t*)c->wn_dw_next.p, s)) != TK_OK) return rc;
-        TK_HIP(c, hipMemcpyAsync(&W, (const uint64_t*)c->wn_dw_next.p + n_docs, 8, hipMemcpyDeviceToHost, s));
+        if ((rc = scan_u32(c, c->window.bsum, a.counts, n_docs, (uint64_t*)c->window.dw_next.p, s)) != TK_OK) return rc;
+        TK_HIP(c, hipMemcpyAsync(&W, (const uint64_t*)c->window.dw_next.p + n_docs, 8, hipMemcpyDeviceToHost, s));
         TK_HIP(c, hipMemcpyAsync(stat, a.stat, 16, hipMemcpyDeviceToHost, s));
     }
     TK_HIP(c, hipStreamSynchronize(s));
@@ -84,30 +84,30 @@ static int run_window(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
         return TK_ERR_INVALID_ARG;
     }
     const uint64_t elems = W * L;
-    TK_HIP(c, c->wn_ids.reserve(elems * (i64 ? 8 : 4) + 16));
-    if (mask) TK_HIP(c, c->wn_mask.reserve(elems + 16));
-    if (spans) TK_HIP(c, c->wn_spans.reserve(elems * 8 + 16));
-    TK_HIP(c, c->wn_len.reserve(W * 4 + 16));
-    TK_HIP(c, c->wn_doc.reserve(W * 4 + 16));
-    TK_HIP(c, c->wn_start.reserve(W * 4 + 16));
-    std::swap(c->wn_dw, c->wn_dw_next);
+    TK_HIP(c, c->window.ids.reserve(elems * (i64 ? 8 : 4) + 16));
+    if (mask) TK_HIP(c, c->window.mask.reserve(elems + 16));
+    if (spans) TK_HIP(c, c->window.spans.reserve(elems * 8 + 16));
+    TK_HIP(c, c->window.len.reserve(W * 4 + 16));
+    TK_HIP(c, c->window.doc.reserve(W * 4 + 16));
+    TK_HIP(c, c->window.start.reserve(W * 4 + 16));
+    std::swap(c->window.dw, c->window.dw_next);
     a.row_len = (uint32_t)L;
     a.n_rows = W;
-    a.doc_windows = (const uint64_t*)c->wn_dw.p;
-    a.out = c->wn_ids.p;
-    a.mask = mask ? (uint8_t*)c->wn_mask.p : nullptr;
-    a.out_spans = spans ? (uint32_t*)c->wn_spans.p : nullptr;
-    a.lengths = (uint32_t*)c->wn_len.p;
-    a.window_doc = (uint32_t*)c->wn_doc.p;
-    a.window_start = (uint32_t*)c->wn_start.p;
+    a.doc_windows = (const uint64_t*)c->window.dw.p;
+    a.out = c->window.ids.p;
+    a.mask = mask ? (uint8_t*)c->window.mask.p : nullptr;
+    a.out_spans = spans ? (uint32_t*)c->window.spans.p : nullptr;
+    a.lengths = (uint32_t*)c->window.len.p;
+    a.window_doc = (uint32_t*)c->window.doc.p;
+    a.window_start = (uint32_t*)c->window.start.p;
     TK_HIP(c, tk_launch_window(a, i64, s));
     TK_HIP(c, hipStreamSynchronize(s));
-    out->input_ids = c->wn_ids.p;
+    out->input_ids = c->window.ids.p;
     out->mask = a.mask;
     out->lengths = a.lengths;
     out->window_doc = a.window_doc;
     out->window_start = a.window_start;
-    out->doc_windows = (uint64_t*)c->wn_dw.p;
+    out->doc_windows = (uint64_t*)c->window.dw.p;
     out->spans = a.out_spans;
     out->n_docs = n_docs;
     out->n_windows = W;
@@ -116,73 +116,38 @@ static int run_window(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
     return TK_OK;
 }
 
+namespace {
+struct WindowPass : LayoutPass<WindowPass> {
+    typedef tk_window_opts Opts;
+    typedef tk_window Result;
+    static constexpr const char* name = "window";
+    static uint64_t esz(const Opts& o) { return (o.flags & TK_WINDOW_I64) ? 8 : 4; }
+    static constexpr auto encode_opts = window_encode_opts;
+    static constexpr auto run = run_window;
+    // behind an encode the spans are the spans pass's own, which runs in front where they are asked for
+    static int run_encoded(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const Opts* o, hipStream_t s,
+                           Result* out) {
+        if (o->flags & TK_WINDOW_SPANS) {
+            int rc = run_spans(c, d_ids, d_id_offs, n_docs, n_ids, nullptr, nullptr, 0, s, nullptr);
+            if (rc != TK_OK) return rc;
+        }
+        return run_window(c, d_ids, d_id_offs, n_docs, n_ids, (const uint32_t*)c->spans.spans.p, o, s, out);
+    }
+};
+}  // namespace
+
 extern "C" int tk_window_from_ids_device(tk_ctx* c, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
                                          const void* d_spans, const tk_window_opts* opts, void* hip_stream, tk_window* out) {
-    TK_ENTRY(c);
-    if (!d_id_offsets || (!d_ids && n_ids) || !opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    TK_HIP(c, hipSetDevice(c->device));
-    return run_window(c, (const uint32_t*)d_ids, (const uint64_t*)d_id_offsets, n_docs, n_ids, (const uint32_t*)d_spans, opts,
-                      (hipStream_t)hip_stream, out);
+    return layout_from_ids_device<WindowPass>(c, d_ids, d_id_offsets, n_docs, n_ids, opts, hip_stream, out, (const uint32_t*)d_spans);
 }
-
 extern "C" int tk_encode_batch_device_window(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs,
                                              uint64_t n_bytes, int add_bos, int add_eos, int checks, const tk_window_opts* opts,
                                              void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_window* out) {
-    TK_ENTRY(c);
-    int rc = check_flags_and_args(c, checks, TK_CHECK_OFFSETS | TK_CHECK_UTF8, !opts || !out);
-    if (rc != TK_OK) return rc;
-    tk_window_opts o;
-    if ((rc = window_encode_opts(c, opts, add_bos, add_eos, &o)) != TK_OK) return rc;
-    rc = encode_device_checked(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, hip_stream, d_ids, d_out_offsets, n_ids);
-    if (rc != TK_OK) return rc;
-    if (o.flags & TK_WINDOW_SPANS) {
-        rc = run_spans(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, *n_ids, nullptr, nullptr, 0, (hipStream_t)hip_stream, nullptr);
-        if (rc != TK_OK) return rc;
-    }
-    return run_window(c, (const uint32_t*)*d_ids, (const uint64_t*)*d_out_offsets, n_docs, *n_ids, (const uint32_t*)c->sp_spans.p, &o,
-                      (hipStream_t)hip_stream, out);
+    return layout_encode_device<WindowPass>(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, checks, opts, hip_stream, d_ids,
+                                            d_out_offsets, n_ids, out);
 }
-
-extern "C" void tk_free_window(tk_window* r) {
-    if (!r) return;
-    tk_pinned_put(r->input_ids);
-    tk_pinned_put(r->mask);
-    tk_pinned_put(r->lengths);
-    tk_pinned_put(r->window_doc);
-    tk_pinned_put(r->window_start);
-    tk_pinned_put(r->doc_windows);
-    tk_pinned_put(r->spans);
-    memset(r, 0, sizeof(*r));
-}
-
 extern "C" int tk_encode_batch_window(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos,
                                       int add_eos, int validate_utf8, const tk_window_opts* opts, tk_window* out) {
-    TK_ENTRY(c);
-    if (!opts || !out) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    memset(out, 0, sizeof(*out));
-    tk_window_opts o;
-    int rc = window_encode_opts(c, opts, add_bos, add_eos, &o);
-    if (rc != TK_OK) return rc;
-    DevBatch dev;
-    uint64_t n_ids;
-    if ((rc = encode_batch_for_layout(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, &dev, &n_ids)) != TK_OK) return rc;
-    // (the small path's ids and offsets are mapped pinned memory: the spans and window kernels read them there)
-    if ((o.flags & TK_WINDOW_SPANS) && (rc = run_spans(c, dev.ids, dev.id_offs, n_docs, n_ids, nullptr, nullptr, 0, c->stream, nullptr)) != TK_OK) return rc;
-    tk_window w;
-    rc = run_window(c, dev.ids, dev.id_offs, n_docs, n_ids, (const uint32_t*)c->sp_spans.p, &o, c->stream, &w);
-    if (rc != TK_OK) return rc;
-    const uint64_t elems = w.n_windows * w.row_len, esz = (o.flags & TK_WINDOW_I64) ? 8 : 4;
-    CopyOut h[7] = {{w.input_ids, elems * esz, nullptr}, {w.mask, elems, nullptr, w.mask != nullptr}, {w.lengths, w.n_windows * 4, nullptr},
-                    {w.window_doc, w.n_windows * 4, nullptr}, {w.window_start, w.n_windows * 4, nullptr},
-                    {w.doc_windows, (n_docs + 1) * 8, nullptr}, {w.spans, elems * 8, nullptr, w.spans != nullptr}};
-    if ((rc = copy_out(c, h, 7, "window")) != TK_OK) return rc;
-    *out = w;
-    out->input_ids = h[0].host;
-    out->mask = (uint8_t*)h[1].host;
-    out->lengths = (uint32_t*)h[2].host;
-    out->window_doc = (uint32_t*)h[3].host;
-    out->window_start = (uint32_t*)h[4].host;
-    out->doc_windows = (uint64_t*)h[5].host;
-    out->spans = (uint32_t*)h[6].host;
-    return TK_OK;
+    return layout_encode_host<WindowPass>(c, bytes, doc_offsets, n_docs, add_bos, add_eos, validate_utf8, opts, out);
 }
+extern "C" void tk_free_window(tk_window* r) { layout_free(r); }

@@ -84,6 +84,37 @@ struct TkCallKnobs {
     int ablate = 0;                // TK_DEBUG_ABLATE (`make ablate` builds only)
 };
 
+// ---- the buffers of the passes behind encode, one struct per pass and one member of tk_ctx each.  The buffers of a pass are apart
+// from those of every other pass and from every encode / decode buffer (a result stays valid through the calls of the other
+// passes), only grow, and are allocated at the first call of the pass.
+struct SpansBufs { DevBuf spans, err; };   // tk_token_spans_device: (start, end) per id, the error words
+// the units pass and the annotation look-up (tk_spans_units.hip): the per-rank entries of tk_units_table.h (built at the first
+// units call), the spans in the unit and their error words; the token ranges (next: written first, swapped in once the call is
+// accepted) and their error words
+struct UnitsBufs { DevBuf table, spans, err, range, next, range_err; };
+// the dense layout (tk_dense.hip): the tensor, its mask, lengths and the two statistics words; the ragged ids / offsets / row
+// lengths of the inverse
+struct DenseBufs { DevBuf ids, mask, len, stat, rids, roffs, rlens; };
+// the packed training rows (tk_seqpack.hip): the three tensors, cu_seqlens and the two statistics words; the work arrays
+// (flags and their scans, the compacted starts, the scan workspace)
+struct SeqpackBufs { DevBuf ids, pos, seg, cu, stat, flags, aflags, fpos, apos, starts, aligned, bsum; };
+// the chat batches (tk_join.hip): the joined ids, their per-conversation offsets, labels, part indices and the statistics
+// words; the work arrays (has-a-control-id and its scan, the parts' output starts and local indices, the scan workspace); the
+// host entry's copies of part_ctrl / part_flags / conv_offsets
+struct JoinBufs { DevBuf ids, offs, labels, pidx, stat, has, cb, start, plocal, bsum, in_ctrl, in_flags, in_conv; };
+// the overlapping windows (tk_window.hip): the tensor, its mask and spans, the per-window arrays, doc_windows; the work arrays
+// (dw_next: the scan that becomes doc_windows once the call is accepted, the counts, the scan workspace, the statistics words)
+struct WindowBufs { DevBuf ids, mask, spans, len, doc, start, dw, dw_next, cnt, bsum, stat; };
+// the whole-document rows (tk_rowfit.hip): the four tensors, cu_seqlens, doc_start and the statistics words; the work arrays
+// (lengths and their scans, the jump tables, the row marks, the row openers, the per-document segment numbers, the per-row
+// pad flags and their scan, the scan workspace)
+struct RowfitBufs {
+    DevBuf ids, lab, pos, seg, cu, dstart, stat, e, nz, E, nzp, ja, jb, row, open, segno, padf, padp, bsum;
+    Event ev[5];                   // the stages of the last rowfit call (tk_last_rowfit_ms), created at the first one
+    float ms[3] = {0.f, 0.f, 0.f};   // placement | fill kernel | cu_seqlens kernel
+    float ms_chain = 0.f;          // the placement's part in front of the host read
+};
+
 struct tk_ctx {
     int device = 0;
     std::mutex mu;
@@ -105,33 +136,14 @@ struct tk_ctx {
     bool have_specials = false;
     DevBuf dec_lens, dec_bytes, dec_offs, dec_bits, dec_err, dec_in_ids, dec_in_offs, dec_hi, dec_glens, dec_goffs;
     DevBuf t_inline, t_len8;   // decode: 16-byte inline entries and one-byte lengths by rank (built at the first decode / spans call)
-    DevBuf sp_spans, sp_err;   // tk_token_spans_device: (start, end) per id, the error words (apart from every encode / decode buffer)
-    // the units pass and the annotation look-up (tk_spans_units.hip): the per-rank entries of tk_units_table.h (built at the first
-    // units call), the spans in the unit, the token ranges (lc_next: written first, swapped in once the call is accepted) and the
-    // error words.  Apart from every other buffer
-    DevBuf t_units, su_spans, su_err, lc_range, lc_next, lc_err;
-    // the dense layout (tk_dense.hip): the tensor, its mask, lengths and the two statistics words; the ragged ids / offsets / row
-    // lengths of the inverse.  Apart from every encode / spans / decode buffer, allocated at the first dense call
-    DevBuf dn_ids, dn_mask, dn_len, dn_stat, dn_rids, dn_roffs, dn_rlens;
-    // the packed training rows (tk_seqpack.hip): the three tensors, cu_seqlens and the two statistics words; the work arrays
-    // (flags and their scans, the compacted starts, the scan workspace).  Apart from every other buffer, allocated at the first packed call
-    DevBuf sp_ids, sp_pos, sp_seg, sp_cu, sp_stat, sp_flags, sp_aflags, sp_fpos, sp_apos, sp_starts, sp_aligned, sp_bsum;
-    // the chat batches (tk_join.hip): the joined ids, their per-conversation offsets, labels, part indices and the statistics
-    // words; the work arrays (has-a-control-id and its scan, the parts' output starts and local indices, the scan workspace); the
-    // host entry's copies of part_ctrl / part_flags / conv_offsets.  Apart from every other buffer, allocated at the first join call
-    DevBuf jn_ids, jn_offs, jn_labels, jn_pidx, jn_stat, jn_has, jn_cb, jn_start, jn_plocal, jn_bsum, jn_in_ctrl, jn_in_flags, jn_in_conv;
-    // the overlapping windows (tk_window.hip): the tensor, its mask and spans, the per-window arrays, doc_windows; the work arrays
-    // (w_d, the scan that becomes doc_windows once the call is accepted, the scan workspace, the statistics words).  Apart from
-    // every other buffer, allocated at the first window call
-    DevBuf wn_ids, wn_mask, wn_spans, wn_len, wn_doc, wn_start, wn_dw, wn_dw_next, wn_cnt, wn_bsum, wn_stat;
-    // the whole-document rows (tk_rowfit.hip): the four tensors, cu_seqlens, doc_start and the statistics words; the work arrays
-    // (lengths and their scans, the jump tables, the row marks, the row openers, the per-document segment numbers, the per-row
-    // pad flags and their scan, the scan workspace).  Apart from every other buffer, allocated at the first rowfit call
-    DevBuf rf_ids, rf_lab, rf_pos, rf_seg, rf_cu, rf_dstart, rf_stat, rf_e, rf_nz, rf_E, rf_nzp, rf_ja, rf_jb, rf_row, rf_open, rf_segno,
-           rf_padf, rf_padp, rf_bsum;
-    Event rf_ev[5];                // the stages of the last rowfit call (tk_last_rowfit_ms), created at the first one
-    float rf_ms[3] = {0.f, 0.f, 0.f};   // placement | fill kernel | cu_seqlens kernel
-    float rf_ms_chain = 0.f;       // the placement's part in front of the host read
+    // the passes behind encode, one member each (the structs above tk_ctx)
+    SpansBufs spans;
+    UnitsBufs units;
+    DenseBufs dense;
+    SeqpackBufs seqpack;
+    JoinBufs join;
+    WindowBufs window;
+    RowfitBufs rowfit;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -207,7 +219,7 @@ int enter_device(tk_ctx* c, uint64_t n_docs);
 struct CopyOut { const void* dev; size_t bytes; void* host; bool selected = true; };
 int pinned_blocks(tk_ctx* c, CopyOut* a, int n);
 int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what);
-// ---- what the layout passes share (tk_capi_dense / _seqpack / _join / _window.cpp) ----
+// ---- what the layout passes share (tk_capi_dense / _seqpack / _join / _window / _rowfit.cpp; tk_capi_layout.h is theirs alone) ----
 #define TK_LAYOUT_MAX_ROW 0x7FFFFFFFull         /* a row of a tensor stays below 2^31 elements */
 #define TK_LAYOUT_MAX_ELEMS (1ull << 36)        /* rows * row length: 256 GiB of int32, more than the part holds */
 // how an entry with check flags opens: an unknown flag is refused first, then a null argument
@@ -248,7 +260,7 @@ template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // .
     a.tok_inline = (const uint8_t*)c->t_inline.p; a.tok_len8 = (const uint8_t*)c->t_len8.p;
     a.n_ranks = c->host.n_ranks; a.num_special = c->host.num_special;
 }
-// tk_capi_spans.cpp: the spans pass over ids on the device into c->sp_spans, with the TK_SPANS_CHECK_* of `checks`
+// tk_capi_spans.cpp: the spans pass over ids on the device into c->spans.spans, with the TK_SPANS_CHECK_* of `checks`
 // (into: the buffer the spans go to instead -- the units pass with TK_UNIT_BYTE)
 int run_spans(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const uint64_t* d_doc_offs,
               const uint8_t* d_bytes, int checks, hipStream_t s, uint64_t* bad_doc, DevBuf* into = nullptr);
