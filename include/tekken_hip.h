@@ -520,7 +520,8 @@ void tk_free_join(tk_join* out);
  *      any output buffer is touched (offsets that do not end at n_ids are refused at the same point).  A failed allocation is
  *      TK_ERR_RUNTIME.  D == 0 or N == 0 is valid and gives n_rows == 0.
  * Next-fit trades padding for order and parallelism: best-fit-decreasing packs tighter, but it reorders the samples and is
- * sequential.  A caller who wants less padding sorts or buckets the documents before the call; n_pad makes the cost visible.
+ * sequential.  A caller who wants less padding puts the documents into length order first, on the device:
+ * tk_regroup_from_ids_device below, whose ids / offsets this entry takes as they are; n_pad makes the cost visible.
  * The layout is a separate pass behind the unchanged encode pipeline (csrc/tk_rowfit.hip).  The placement is not sequential
  * either: with E the exclusive prefix sum of e, the row opened at document i ends in front of nxt(i), the largest j with
  * E[j] <= E[i] + L; pointer doubling over the chain 0, nxt(0), nxt(nxt(0)), ... marks the row openers and numbers the rows in
@@ -565,6 +566,87 @@ void tk_free_rowfit(tk_rowfit* out);
  * doubling rounds, doc_start; the host read between them is not counted), the fill kernel, the cu_seqlens kernel.  All 0 when
  * the pass launched nothing (n_ids == 0) or was refused.  A NULL pointer is skipped. */
 void tk_last_rowfit_ms(const tk_ctx* ctx, float* placement_ms, float* fill_ms, float* cu_ms);
+
+/* ---- encoded documents selected, reordered and cut into batches on the device (no reference equivalent) ----
+ * What a data pipeline does between "encode" and "batch": drop documents, put the rest into another order (shuffled, by length, by
+ * length within shuffled groups), cut that order into batches under a padded-token budget.  Ragged in, ragged out: the result's
+ * ids / offsets feed tk_dense_from_ids_device, tk_rowfit_from_ids_device, tk_seqpack_from_ids_device and the spans entries as
+ * they are.  Input: the ragged ids R_d = ids[oo[d] : oo[d+1]] with n_d ids each, d < D; N = oo[D]; optionally lab, int32[N], with
+ * the SAME offsets (a join's labels); optionally keep, uint8[D]; the options and flags below.
+ *   1. Selection.  Document d is kept iff (keep is NULL or keep[d] != 0) and n_d >= min_length and (max_length == 0 or
+ *      n_d <= max_length).  A dropped document is counted once, under the first test it fails: n_masked, then n_short, then
+ *      n_long.  K = n_docs is the number kept; c_0 < ... < c_{K-1} are the kept indices.
+ *   2. Order.  perm[k] is the source document of output document k.
+ *      TK_REGROUP_ORDER_KEEP: perm = c.
+ *      TK_REGROUP_ORDER_LENGTH: ascending n_d, stable (equal lengths stay in ascending d); with TK_REGROUP_DESC descending n_d,
+ *      still stable in d.
+ *      TK_REGROUP_ORDER_SHUFFLE: ascending h(seed, d), all arithmetic mod 2^32:
+ *          x = d * 0x9E3779B1 + seed;  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16
+ *      h is a bijection of the 32-bit d: no ties, and the order of two documents does not depend on what else was dropped.
+ *      TK_REGROUP_ORDER_GROUPED (needs window = w > 0): the SHUFFLE order cut into consecutive groups of w (the last may be
+ *      shorter), each group sorted by length (ascending; descending with TK_REGROUP_DESC), stable with respect to the shuffled
+ *      order.  TK_REGROUP_DESC means nothing to KEEP and SHUFFLE.
+ *   3. Ragged outputs.  offsets (uint64, K + 1) is the exclusive prefix sum of n_perm[k]; ids[offsets[k] : offsets[k+1]] =
+ *      R_perm[k]; n_ids = offsets[K].  labels (TK_REGROUP_LABELS, needs lab): lab moved the same way.  perm (TK_REGROUP_PERM):
+ *      uint32 [K].
+ *   4. Batches (TK_REGROUP_BATCHES, needs max_tokens = T > 0; max_docs == 0: no limit).  With m_k = n_perm[k]:
+ *          bo = [0]; start = 0; mx = 0
+ *          for k in 0 .. K-1:
+ *              m = max(mx, m_k); cnt = k - start + 1
+ *              if cnt > 1 and (cnt * m > T or (max_docs and cnt > max_docs)): bo.append(k); start = k; m = m_k
+ *              mx = m
+ *          if K > 0: bo.append(K)
+ *      batch_offsets = bo (TK_REGROUP_BATCH_OFFSETS, uint64 [n_batches + 1]; [0] and n_batches = 0 when K = 0).  batch_rowlen[b]
+ *      (TK_REGROUP_BATCH_ROWLEN, uint32 [n_batches]) is the longest document of batch b: the L of a dense call over the batch.
+ *      n_oversize = the batches with cnt * rowlen > T (such a batch is one document on its own; max_length <= T rules it out).
+ *      n_batch_pad = sum_b cnt_b * rowlen_b - n_ids.  The three counts are filled whether or not the arrays are selected, as
+ *      long as TK_REGROUP_BATCHES is set; without it the two array flags select nothing and the counts are 0.
+ *   5. TK_ERR_INVALID_ARG, nothing written, an earlier regroup result stays readable: an unknown order or flag; D >= 2^32;
+ *      TK_REGROUP_ORDER_GROUPED with window == 0; TK_REGROUP_BATCHES with max_tokens == 0; TK_REGROUP_LABELS without lab when
+ *      N > 0; min_length > max_length > 0; n_docs == 0 with n_ids > 0; and, known behind the selection and before any output
+ *      buffer is touched: offsets that do not end at n_ids, a document of 2^32 ids or more (which is also what offsets that
+ *      decrease look like).  A failed allocation is TK_ERR_RUNTIME.  D = 0, N = 0 and "everything dropped" are valid: K = 0.
+ * A separate pass behind the unchanged encode pipeline (csrc/tk_regroup.hip): the selection and its scan, one host
+ * read (K, n_ids, the drop counts, the longest kept document), a stable least-significant-digit radix sort of (key, document)
+ * pairs, 8 bits a pass, which skips the digits above the largest key, the gather of every id in 16-byte stores, and the batch
+ * boundaries by one search per document and the pointer doubling that the rowfit pass has.  One more wait ends the call. */
+#define TK_REGROUP_ORDER_KEEP 0
+#define TK_REGROUP_ORDER_LENGTH 1
+#define TK_REGROUP_ORDER_SHUFFLE 2
+#define TK_REGROUP_ORDER_GROUPED 3
+#define TK_REGROUP_DESC 1
+#define TK_REGROUP_LABELS 2
+#define TK_REGROUP_PERM 4
+#define TK_REGROUP_BATCHES 8
+#define TK_REGROUP_BATCH_OFFSETS 16
+#define TK_REGROUP_BATCH_ROWLEN 32
+typedef struct tk_regroup_opts { uint64_t max_tokens; uint32_t min_length, max_length, order, seed, window, max_docs, flags; } tk_regroup_opts;
+typedef struct tk_regroup { uint32_t* ids; uint64_t* offsets; int32_t* labels; uint32_t* perm; uint64_t* batch_offsets; uint32_t* batch_rowlen;
+                            uint64_t n_docs, n_ids, n_masked, n_short, n_long, n_batches, n_oversize, n_batch_pad; } tk_regroup;
+/* ids already on the device (encode's own outputs, a join's ids / offsets / labels, or the caller's; d_id_offsets: n_docs + 1
+ * uint64) -> the regrouped documents.  d_labels: NULL or int32[n_ids]; d_keep: NULL or uint8[n_docs].  out's buffers are device
+ * buffers owned by the context, valid until the next regroup call on it, and SEPARATE from the encode, spans, dense, packed, join,
+ * window, rowfit and decode outputs: out->ids / out->offsets (and out->offsets + first_doc for one batch: the passes index
+ * ids[offsets[d] + j]) are meant to go into those passes next.  The work is enqueued on hip_stream and the call returns after
+ * the stream has drained. */
+int tk_regroup_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                               const void* d_labels, const void* d_keep, const tk_regroup_opts* opts, void* hip_stream, tk_regroup* out);
+/* tk_encode_batch_device_ex + the regroup pass on the same stream.  Text has neither a labels stream nor a keep mask:
+ * TK_REGROUP_LABELS is refused before anything is encoded, here and in tk_encode_batch_regroup.  The ragged outputs of encode
+ * (*d_ids / *d_out_offsets / *n_ids as tk_encode_batch_device) are returned as well. */
+int tk_encode_batch_device_regroup(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                   int add_bos, int add_eos, int checks, const tk_regroup_opts* opts, void* hip_stream,
+                                   void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_regroup* out);
+/* Host in / host out: tk_encode_batch + the regroup pass.  out's buffers are pinned host memory, released with tk_free_regroup (an
+ * unselected output is NULL). */
+int tk_encode_batch_regroup(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                            int validate_utf8, const tk_regroup_opts* opts, tk_regroup* out);
+void tk_free_regroup(tk_regroup* out);
+/* As tk_last_rowfit_ms, for tools/regroup_time.py: GPU time of the stages of the context's last regroup pass, from events on its
+ * stream: ms[0] the selection and its compaction (the host read behind it is not counted), ms[1] the sort (keys, radix passes,
+ * the new offsets), ms[2] the gather kernel, ms[3] the batches.  All 0 where the pass was refused; a stage that launched nothing
+ * is 0 or the cost of two event records. */
+void tk_last_regroup_ms(const tk_ctx* ctx, float ms[4]);
 
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token

@@ -177,6 +177,45 @@ pub struct TkRowfit {
     pub n_truncated: u64,
     pub n_pad: u64,
 }
+// documents selected, reordered and cut into batches (tk_regroup_opts.order / .flags; include/tekken_hip.h has the definition)
+pub const TK_REGROUP_ORDER_KEEP: u32 = 0;
+pub const TK_REGROUP_ORDER_LENGTH: u32 = 1;
+pub const TK_REGROUP_ORDER_SHUFFLE: u32 = 2;
+pub const TK_REGROUP_ORDER_GROUPED: u32 = 3;
+pub const TK_REGROUP_DESC: u32 = 1;
+pub const TK_REGROUP_LABELS: u32 = 2;
+pub const TK_REGROUP_PERM: u32 = 4;
+pub const TK_REGROUP_BATCHES: u32 = 8;
+pub const TK_REGROUP_BATCH_OFFSETS: u32 = 16;
+pub const TK_REGROUP_BATCH_ROWLEN: u32 = 32;
+#[repr(C)]
+pub struct TkRegroupOpts {
+    pub max_tokens: u64,
+    pub min_length: u32,
+    pub max_length: u32,
+    pub order: u32,
+    pub seed: u32,
+    pub window: u32,
+    pub max_docs: u32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkRegroup {
+    pub ids: *mut u32,
+    pub offsets: *mut u64,
+    pub labels: *mut i32,
+    pub perm: *mut u32,
+    pub batch_offsets: *mut u64,
+    pub batch_rowlen: *mut u32,
+    pub n_docs: u64,
+    pub n_ids: u64,
+    pub n_masked: u64,
+    pub n_short: u64,
+    pub n_long: u64,
+    pub n_batches: u64,
+    pub n_oversize: u64,
+    pub n_batch_pad: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -280,6 +319,16 @@ extern "C" {
                                   validate_utf8: c_int, opts: *const TkRowfitOpts, out: *mut TkRowfit) -> c_int;
     pub fn tk_free_rowfit(out: *mut TkRowfit);
     pub fn tk_last_rowfit_ms(ctx: *const TkCtx, placement_ms: *mut f32, fill_ms: *mut f32, cu_ms: *mut f32);
+    pub fn tk_regroup_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                      d_labels: *const c_void, d_keep: *const c_void, opts: *const TkRegroupOpts, hip_stream: *mut c_void,
+                                      out: *mut TkRegroup) -> c_int;
+    pub fn tk_encode_batch_device_regroup(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                          add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkRegroupOpts, hip_stream: *mut c_void,
+                                          d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkRegroup) -> c_int;
+    pub fn tk_encode_batch_regroup(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                   validate_utf8: c_int, opts: *const TkRegroupOpts, out: *mut TkRegroup) -> c_int;
+    pub fn tk_free_regroup(out: *mut TkRegroup);
+    pub fn tk_last_regroup_ms(ctx: *const TkCtx, ms: *mut f32);
     // memo of merged pieces (round 4): a device table {unknown piece of 2..16 bytes -> its <= 4 ids}; never changes an id
     pub fn tk_ctx_set_memo(ctx: *mut TkCtx, log2_entries: c_int, policy: c_int) -> c_int;
     pub fn tk_ctx_memo_clear(ctx: *mut TkCtx) -> c_int;

@@ -39,6 +39,9 @@ JOIN_NONE = 0xFFFFFFFF   # part_ctrl: the part has no control id
 PART_LABEL_CTRL, PART_LABEL_TEXT = 1, 2   # part_flags
 JOIN_LABELS, JOIN_PART_INDEX = 1, 2   # tk_join_opts.flags (the join entries)
 ROWFIT_I64, ROWFIT_POSITIONS, ROWFIT_SEGMENTS, ROWFIT_CU_SEQLENS, ROWFIT_LABELS, ROWFIT_DOC_START = 1, 2, 4, 8, 16, 32   # tk_rowfit_opts.flags (the rowfit entries)
+REGROUP_ORDER_KEEP, REGROUP_ORDER_LENGTH, REGROUP_ORDER_SHUFFLE, REGROUP_ORDER_GROUPED = 0, 1, 2, 3   # tk_regroup_opts.order
+REGROUP_DESC, REGROUP_LABELS, REGROUP_PERM, REGROUP_BATCHES, REGROUP_BATCH_OFFSETS, REGROUP_BATCH_ROWLEN = 1, 2, 4, 8, 16, 32   # tk_regroup_opts.flags (the regroup entries)
+_ORDERS = {"keep": REGROUP_ORDER_KEEP, "length": REGROUP_ORDER_LENGTH, "shuffle": REGROUP_ORDER_SHUFFLE, "grouped": REGROUP_ORDER_GROUPED}   # the order keyword of encode_batch_regrouped
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
 TK_ERR_INVALID_UTF8 = -3
@@ -131,6 +134,18 @@ class _Rowfit(ctypes.Structure):
     _fields_ = [("input_ids", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("position_ids", ctypes.c_void_p), ("segment_ids", ctypes.c_void_p),
                 ("cu_seqlens", ctypes.c_void_p), ("doc_start", ctypes.c_void_p), ("n_rows", ctypes.c_uint64), ("row_len", ctypes.c_uint64),
                 ("n_segments", ctypes.c_uint64), ("max_seqlen", ctypes.c_uint64), ("n_truncated", ctypes.c_uint64), ("n_pad", ctypes.c_uint64)]
+
+
+class _RegroupOpts(ctypes.Structure):
+    _fields_ = [("max_tokens", ctypes.c_uint64), ("min_length", ctypes.c_uint32), ("max_length", ctypes.c_uint32), ("order", ctypes.c_uint32),
+                ("seed", ctypes.c_uint32), ("window", ctypes.c_uint32), ("max_docs", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class _Regroup(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("perm", ctypes.c_void_p),
+                ("batch_offsets", ctypes.c_void_p), ("batch_rowlen", ctypes.c_void_p), ("n_docs", ctypes.c_uint64), ("n_ids", ctypes.c_uint64),
+                ("n_masked", ctypes.c_uint64), ("n_short", ctypes.c_uint64), ("n_long", ctypes.c_uint64), ("n_batches", ctypes.c_uint64),
+                ("n_oversize", ctypes.c_uint64), ("n_batch_pad", ctypes.c_uint64)]
 
 
 _LIB = None
@@ -327,7 +342,7 @@ def lib():
     # library built before a pass still loads through TK_HIP_LIB
     u64, ci, vpp = ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(vp)
     for R, opts, extra in ((DenseResult, _DenseOpts, []), (SeqpackResult, _SeqpackOpts, []), (WindowResult, _WindowOpts, [vp]),
-                           (RowfitResult, _RowfitOpts, [vp])):
+                           (RowfitResult, _RowfitOpts, [vp]), (RegroupResult, _RegroupOpts, [vp, vp])):
         if not hasattr(L, "tk_%s_from_ids_device" % R.PASS):
             continue
         op, rp = ctypes.POINTER(opts), ctypes.POINTER(R.STRUCT)
@@ -355,6 +370,9 @@ def lib():
                                                     ctypes.POINTER(_Rowfit)]
         L.tk_last_rowfit_ms.restype = None
         L.tk_last_rowfit_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    if hasattr(L, "tk_last_regroup_ms"):
+        L.tk_last_regroup_ms.restype = None
+        L.tk_last_regroup_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 4)]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -434,7 +452,7 @@ def _dense_opts(max_length=0, multiple_of=0, pad_id=0, keep_head=0, keep_tail=0,
 
 
 class _LayoutResult:
-    """What the five layout results share.  A result class declares its outputs ONCE, in the order of the C struct's pointer
+    """What the six layout results share.  A result class declares its outputs ONCE, in the order of the C struct's pointer
     fields (tests/test_layout_binding_cpu.py holds them against include/tekken_hip.h), and everything that walks them is here:
     the *_ptr attributes, views(), tensors() and the host copy.
     OUTPUTS: (name, typestr of views() -- None: the tensors' dtype, self.typestr --, shape(self), numpy dtype of the host entry's
@@ -569,6 +587,36 @@ class RowfitResult(_LayoutResult):
 
     def counts(self):
         return self._counts()
+
+
+def _regroup_opts(order=REGROUP_ORDER_KEEP, min_length=0, max_length=0, seed=0, window=0, max_tokens=0, max_docs=0, flags=0):
+    return _RegroupOpts(int(max_tokens or 0), int(min_length or 0), int(max_length or 0), int(order), int(seed), int(window or 0),
+                        int(max_docs or 0), int(flags))
+
+
+class RegroupResult(_LayoutResult):
+    """What the device regroup entries return (tk_regroup): raw device pointers of context-owned buffers, valid until the next
+    regroup call on the context.  ids_ptr: uint32 [n_ids]; offsets_ptr: uint64 [n_docs + 1] (n_docs: the KEPT documents);
+    labels_ptr: int32 [n_ids]; perm_ptr: uint32 [n_docs]; batch_offsets_ptr: uint64 [n_batches + 1]; batch_rowlen_ptr: uint32
+    [n_batches] (an unselected one: None).
+    views(): (ids as int32 [n_ids], offsets as int64 [n_docs + 1], labels or None, perm as int32 or None, batch_offsets as int64
+    or None, batch_rowlen as int32 or None)."""
+    STRUCT, PASS = _Regroup, "regroup"
+    OUTPUTS = (("ids", "<i4", lambda r: (r.n_ids,), np.uint32, False), ("offsets", "<i8", lambda r: (r.n_docs + 1,), np.uint64, False),
+               ("labels", "<i4", lambda r: (r.n_ids,), np.int32, True), ("perm", "<i4", lambda r: (r.n_docs,), np.uint32, True),
+               ("batch_offsets", "<i8", lambda r: (r.n_batches + 1,), np.uint64, True),
+               ("batch_rowlen", "<i4", lambda r: (r.n_batches,), np.uint32, True))
+    COUNTS = ("n_docs", "n_ids", "n_masked", "n_short", "n_long", "n_batches", "n_oversize", "n_batch_pad")
+    DICT_COUNTS = COUNTS
+
+    def batches(self):
+        """(first_doc, end_doc, rowlen) of every batch, from one host copy of batch_offsets and batch_rowlen (both selected)."""
+        if self.batch_offsets_ptr is None or self.batch_rowlen_ptr is None:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "batches(): REGROUP_BATCHES | REGROUP_BATCH_OFFSETS | REGROUP_BATCH_ROWLEN were not selected")
+        v = self.views()
+        bo, rl = (_torch_wrap(x, False).cpu().tolist() for x in (v[4], v[5]))
+        for b in range(self.n_batches):
+            yield bo[b], bo[b + 1], rl[b]
 
 
 class Engine:
@@ -905,6 +953,44 @@ class Engine:
         has none) and the counts n_rows, n_segments, max_seqlen, n_truncated, n_pad."""
         o = _RowfitOpts(int(seq_len), int(pad_id), int(keep_tail), int(flags), -100)
         return self._encode_host(RowfitResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
+
+    def regroup_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, order=REGROUP_ORDER_KEEP, min_length=0, max_length=0, seed=0,
+                                window=0, max_tokens=0, max_docs=0, flags=0, d_labels_ptr=0, d_keep_ptr=0, stream=0):
+        """tk_regroup_from_ids_device: ragged ids resident in HBM -> the kept documents in another order, ragged again (ids, offsets,
+        labels with REGROUP_LABELS and d_labels_ptr, perm) and the batches a padded-token budget cuts them into; the definition is in
+        include/tekken_hip.h.  d_keep_ptr: uint8 [n_docs] or 0.  Returns a RegroupResult (context-owned device buffers, apart from
+        every other output: its ids_ptr / offsets_ptr go into the other passes as they are)."""
+        o = _regroup_opts(order, min_length, max_length, seed, window, max_tokens, max_docs, flags)
+        return self._from_ids_device(RegroupResult, o, flags, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, (d_labels_ptr, d_keep_ptr), stream)
+
+    def encode_batch_device_regroup(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, order=REGROUP_ORDER_KEEP,
+                                    min_length=0, max_length=0, seed=0, window=0, max_tokens=0, max_docs=0, flags=0, checks=0, stream=0):
+        """tk_encode_batch_device_regroup: encode_batch_device + the regroup pass on the same stream (no labels, no keep mask).
+        Returns (d_ids_ptr, d_out_offs_ptr, n_ids, RegroupResult), all context-owned."""
+        o = _regroup_opts(order, min_length, max_length, seed, window, max_tokens, max_docs, flags)
+        return self._encode_device(RegroupResult, o, flags, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream)
+
+    def encode_batch_regroup(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, order=REGROUP_ORDER_KEEP, min_length=0,
+                             max_length=0, seed=0, window=0, max_tokens=0, max_docs=0, flags=0):
+        """tk_encode_batch_regroup, host in / host out: a dict of numpy arrays (ids uint32, offsets uint64, perm uint32,
+        batch_offsets uint64, batch_rowlen uint32; an unselected one None) and the counts."""
+        o = _regroup_opts(order, min_length, max_length, seed, window, max_tokens, max_docs, flags)
+        return self._encode_host(RegroupResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
+
+    def dense_from_regroup_batch(self, res, first_doc, end_doc, pad_id=0, flags=0, max_length=0, multiple_of=0, stream=0):
+        """The dense pass over documents first_doc .. end_doc of a RegroupResult (one of its batches()): the same ids pointer and
+        offsets + first_doc -- the dense kernel indexes ids[offsets[d] + j], so nothing is rebased or copied.  Returns a DenseResult
+        [end_doc - first_doc, the longest document of the range]."""
+        if not 0 <= first_doc <= end_doc <= res.n_docs:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "dense_from_regroup_batch: documents %d .. %d of %d" % (first_doc, end_doc, res.n_docs))
+        return self.dense_from_ids_device(res.ids_ptr, res.offsets_ptr + 8 * first_doc, end_doc - first_doc, res.n_ids, max_length, multiple_of,
+                                          pad_id, 0, 0, flags, stream)
+
+    def last_regroup_ms(self):
+        """tk_last_regroup_ms: GPU time of the stages of the last regroup pass on this context: (select, sort, gather, batches)."""
+        ms = (ctypes.c_float * 4)()
+        _need("tk_last_regroup_ms")(self._h, ctypes.byref(ms))
+        return tuple(ms)
 
     def last_rowfit_ms(self):
         """tk_last_rowfit_ms: GPU time of the stages of the last rowfit pass on this context."""
@@ -1390,8 +1476,8 @@ class Tekkenizer:
         {"input_ids", "position_ids", "segment_ids": [n_rows, seq_len] of `dtype` ("int64" | "int32"), "cu_seqlens": int32
         [n_segments + 1] (offsets into the flattened tensor that tile it, every pad run a segment of its own), "doc_start": [D]
         where every document went (row * seq_len + column), "labels": None, "max_seqlen", "n_rows", "n_segments", "n_truncated",
-        "n_pad": int}; an unselected tensor is None.  Next-fit keeps the order and pays for it in padding (n_pad): sort or bucket
-        the documents by length before the call to pad less.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on
+        "n_pad": int}; an unselected tensor is None.  Next-fit keeps the order and pays for it in padding (n_pad): the regroup pass
+        (encode_batch_regrouped, Engine.regroup_from_ids_device) puts the documents into length order on the device first.  pad_id None: self.pad_id().  return_tensors "pt": torch tensors on
         the tokenizer's GPU (copy=False: views of context-owned buffers, valid until the next call on this tokenizer); "np": numpy."""
         eng = self._device_engine()
         pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
@@ -1403,6 +1489,43 @@ class Tekkenizer:
             return eng.encode_batch_rowfit(data, offs, seq_len, add_bos, add_eos, False, pad, keep_tail, flags)
         _, _, _, res = eng.encode_batch_device_rowfit(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), seq_len, add_bos, add_eos,
                                                       pad, keep_tail, flags, CHECK_OFFSETS, stream)
+        return res.tensors(copy)
+
+    def encode_batch_regrouped(self, docs, order="keep", add_bos=False, add_eos=False, min_length=0, max_length=0, seed=0, window=0,
+                               max_tokens=0, max_docs=0, descending=False, keep=None, return_perm=True, return_tensors="pt", copy=True):
+        """The documents encoded, selected, reordered and cut into batches on the device (tk_encode_batch_device_regroup /
+        tk_regroup_from_ids_device / tk_encode_batch_regroup; the definition is in include/tekken_hip.h).  order: "keep" |
+        "length" (stable; descending=True: longest first) | "shuffle" (by a hash of seed and the document index) | "grouped"
+        (shuffled, then sorted by length inside consecutive groups of `window`).  Documents of fewer than min_length or more than
+        max_length (0: no limit) ids are dropped, as are those where keep (a sequence of D truth values) is false.  max_tokens >
+        0: the order is cut into batches whose padded size, documents * longest document, stays within max_tokens (and max_docs).
+        {"ids": int32 [n_ids], "offsets": int64 [n_docs + 1] (n_docs: the kept documents), "perm": int32 [n_docs], the source
+        document of every output document, "batch_offsets": int64 [n_batches + 1], "batch_rowlen": int32 [n_batches], "labels":
+        None, and the counts n_docs, n_ids, n_masked, n_short, n_long, n_batches, n_oversize, n_batch_pad}; an unselected array is
+        None.  return_tensors "pt": torch tensors on the tokenizer's GPU (copy=False: views of context-owned buffers, valid until
+        the next call on this tokenizer); "np": numpy (no keep mask: the host entry has none)."""
+        eng = self._device_engine()
+        _, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_regrouped", docs, add_bos, add_eos, 0, order in _ORDERS and return_tensors in ("pt", "np")
+            and not (keep is not None and return_tensors == "np"), "order / return_tensors / keep",
+            {"min_length": min_length, "max_length": max_length, "seed": seed, "window": window, "max_docs": max_docs},
+            upload=return_tensors != "np")
+        flags = (REGROUP_DESC if descending else 0) | (REGROUP_PERM if return_perm else 0) \
+            | (REGROUP_BATCHES | REGROUP_BATCH_OFFSETS | REGROUP_BATCH_ROWLEN if max_tokens else 0)
+        opts = (_ORDERS[order], min_length, max_length, seed, window, max_tokens, max_docs, flags)
+        if return_tensors == "np":
+            return eng.encode_batch_regroup(data, offs, add_bos, add_eos, False, *opts)
+        if keep is None:
+            _, _, _, res = eng.encode_batch_device_regroup(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos, add_eos, *opts,
+                                                           CHECK_OFFSETS, stream)
+        else:
+            import torch
+            if len(keep) != len(docs):
+                raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_regrouped: keep has %d entries for %d documents" % (len(keep), len(docs)))
+            d_keep = torch.as_tensor(np.asarray(keep, bool).astype(np.uint8)).cuda() if len(docs) else None
+            d_ids, d_oo, n_ids = eng.encode_batch_device(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos, add_eos, stream,
+                                                         CHECK_OFFSETS)[:3]
+            res = eng.regroup_from_ids_device(d_ids, d_oo, len(docs), n_ids, *opts, 0, d_keep.data_ptr() if d_keep is not None else 0, stream)
         return res.tensors(copy)
 
     def encode_batch_windows(self, docs, max_length, stride=0, add_bos=False, add_eos=False, padding="max_length", pad_to_multiple_of=None,

@@ -1,4 +1,4 @@
-// tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _rowfit.cpp) share, and
+// tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _rowfit / _regroup.cpp) share, and
 // only they include: ONE description of the outputs of each result struct, from which tk_free_<pass> and the copy-out of the host
 // entries are made, and the three entries around a pass (ids on the device | text on the device | text on the host) written once.
 #ifndef TK_CAPI_LAYOUT_H
@@ -50,6 +50,15 @@ template <class F> static inline void layout_outputs(tk_rowfit& r, uint64_t esz,
     f(r.cu_seqlens, (r.n_segments + 1) * 4, r.cu_seqlens != nullptr);
     f(r.doc_start, n_docs * 8, r.doc_start != nullptr);
 }
+template <class F> static inline void layout_outputs(tk_regroup& r, uint64_t, uint64_t, F&& f) {
+    const uint64_t n4 = r.n_ids * 4;            // (r.n_docs: the kept documents)
+    f(r.ids, n4, true);
+    f(r.offsets, (r.n_docs + 1) * 8, true);
+    f(r.labels, n4, r.labels != nullptr);
+    f(r.perm, r.n_docs * 4, r.perm != nullptr);
+    f(r.batch_offsets, (r.n_batches + 1) * 8, r.batch_offsets != nullptr);
+    f(r.batch_rowlen, r.n_batches * 4, r.batch_rowlen != nullptr);
+}
 
 // tk_free_<pass>: every block back to the pinned pool, the struct zeroed
 template <class R> static inline void layout_free(R* r) {
@@ -72,15 +81,15 @@ template <class R> static inline int layout_copy_out(tk_ctx* c, const R& dev, ui
     return TK_OK;
 }
 
-// ---- the three entries around a pass, for the passes whose entries take the same arguments (dense, seqpack, window, rowfit; join
-// has its own).  A pass is a struct P with
+// ---- the three entries around a pass, for the passes whose entries take the same arguments (dense, seqpack, window, rowfit, regroup;
+// join has its own).  A pass is a struct P with
 //   Opts, Result    the option and result structs of the C ABI
 //   name            what a failed copy-out is called in the message
 //   esz(o)          the bytes of an element of the tensors
 //   encode_opts(c, opts, add_bos, add_eos, &o)   the options of an entry that encodes first, checked: what can be refused is refused
 //                   before anything is encoded
 //   run(c, d_ids, d_id_offs, n_docs, n_ids, [d_extra,] o, s, out)   the pass (it checks its options itself); d_extra: the second
-//                   input of the passes that have one (window: the spans, rowfit: the labels)
+//                   input of the passes that have one (window: the spans, rowfit: the labels, regroup: the labels and the keep mask)
 //   run_encoded(c, d_ids, d_id_offs, n_docs, n_ids, o, s, out)      the pass behind an encode on s; LayoutPass<P> has it for a pass
 //                   without a second input, the others say what stands in for theirs
 // What a bad call reports first is behaviour (check_n_docs, tk_ctx.h): an unknown check flag, a null argument, the options of the

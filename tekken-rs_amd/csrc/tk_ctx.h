@@ -114,6 +114,15 @@ struct RowfitBufs {
     float ms[3] = {0.f, 0.f, 0.f};   // placement | fill kernel | cu_seqlens kernel
     float ms_chain = 0.f;          // the placement's part in front of the host read
 };
+// the regrouped documents (tk_regroup.hip): the ragged outputs, perm, the batch arrays and the statistics words; the work arrays
+// (the kept flags, their scan and the kept documents, two key and three document buffers of the radix sort, its digit counts and
+// their scan, the documents' lengths and source starts, the maximum pyramid, the jump tables, the batch marks, openers and row
+// lengths, the scan workspace)
+struct RegroupBufs {
+    DevBuf ids, offs, lab, perm, bo, brl, stat, flag, fpos, kept, key[2], val[3], hist, hpos, len, src, pyr, ja, jb, row, open, bmax, bsum;
+    Event ev[6];                   // the stages of the last regroup call (tk_last_regroup_ms), created at the first one
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};   // selection | sort | gather kernel | batches
+};
 
 struct tk_ctx {
     int device = 0;
@@ -144,6 +153,7 @@ struct tk_ctx {
     JoinBufs join;
     WindowBufs window;
     RowfitBufs rowfit;
+    RegroupBufs regroup;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -219,7 +229,7 @@ int enter_device(tk_ctx* c, uint64_t n_docs);
 struct CopyOut { const void* dev; size_t bytes; void* host; bool selected = true; };
 int pinned_blocks(tk_ctx* c, CopyOut* a, int n);
 int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what);
-// ---- what the layout passes share (tk_capi_dense / _seqpack / _join / _window / _rowfit.cpp; tk_capi_layout.h is theirs alone) ----
+// ---- what the layout passes share (tk_capi_dense / _seqpack / _join / _window / _rowfit / _regroup.cpp; tk_capi_layout.h is theirs alone) ----
 #define TK_LAYOUT_MAX_ROW 0x7FFFFFFFull         /* a row of a tensor stays below 2^31 elements */
 #define TK_LAYOUT_MAX_ELEMS (1ull << 36)        /* rows * row length: 256 GiB of int32, more than the part holds */
 // how an entry with check flags opens: an unknown flag is refused first, then a null argument

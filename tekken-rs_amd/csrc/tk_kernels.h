@@ -277,9 +277,67 @@ struct TkRowfitArgs {
 };
 hipError_t tk_launch_rowfit_len(const TkRowfitArgs& a, hipStream_t s);     // e, nz, n_truncated (n_docs > 0)
 hipError_t tk_launch_rowfit_chain(const TkRowfitArgs& a, uint32_t rounds, hipStream_t s);   // jump, row, open (behind the scan of e)
+// the doubling rounds and the openers alone, over a chain whose first links the caller has written (jump_a[v] = nxt(v) | 1 << 32,
+// jump_a[n_docs] = n_docs, row[v] = v ? 0xFFFFFFFF : 0): what tk_launch_rowfit_chain runs behind its own nxt kernel, and the
+// regroup pass behind its.  Reads E[n_docs] and id_offs[n_docs] into stat[4], stat[5] and writes stat[3] = the links of the chain
+hipError_t tk_launch_chain_rounds(const TkRowfitArgs& a, uint32_t rounds, hipStream_t s);
 hipError_t tk_launch_rowfit_place(const TkRowfitArgs& a, hipStream_t s);   // dstart, segno, padf (n_rows known)
 hipError_t tk_launch_rowfit(const TkRowfitArgs& a, int i64, hipStream_t s);   // the tensors; n_rows == 0: nothing is launched
 hipError_t tk_launch_rowfit_cu(const TkRowfitArgs& a, hipStream_t s);      // cu_seqlens (a.cu != NULL), n_segments, max_seqlen (behind the scan of padf)
+
+// ---- documents selected, reordered and cut into batches (tk_regroup.hip) ----
+#define TKG_CHUNK 2048u        /* (key, document) pairs of a block of a radix pass */
+#define TKG_FAN 64u            /* entries of a level of the maximum pyramid under one entry of the next */
+#define TKG_MAX_LEVELS 6       /* 64^6 > 2^32 */
+struct TkRegroupArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const int32_t* lab;        // [n_ids] a second stream with the same offsets, or NULL
+    const uint64_t* id_offs;   // [n_docs + 1]
+    const uint8_t* keep;       // [n_docs] or NULL
+    uint64_t n_docs;           // D (< 2^32)
+    uint64_t n_kept;           // K: known behind the host read
+    uint64_t n_out;            // ids of the kept documents: known behind the host read
+    uint64_t max_tokens;
+    uint32_t min_len, max_len, order, seed, window, max_docs, desc;
+    uint32_t longest;          // the longest kept document: known behind the host read
+    uint32_t* flag;            // [n_docs] the document is kept
+    const uint64_t* fpos;      // [n_docs + 1] exclusive scan of flag
+    uint32_t* kept;            // [K] c: the kept documents, increasing
+    const uint32_t *key_in, *val_in;   // [K] the pairs of a radix pass ...
+    uint32_t *key_out, *val_out;       // ... and where it puts them
+    uint32_t* hist;            // [256 * blocks] digit-major counts of a radix pass
+    const uint64_t* hpos;      // [256 * blocks + 1] exclusive scan of hist
+    const uint32_t* shuf;      // [K] GROUPED: the documents in shuffled order (val is the rank in it)
+    uint32_t* perm;            // [K]
+    uint32_t* len;             // [K] m_k = n_perm[k]
+    uint64_t* src;             // [K] id_offs[perm[k]]
+    uint64_t* out_offs;        // [K + 1] exclusive scan of len
+    uint32_t* out_ids;         // [n_out]
+    int32_t* out_lab;          // [n_out] or NULL
+    uint32_t* pyr;             // the maximum pyramid over len: level l (from 1) at pyr + pyr_at[l], ceil(K / 64^l) entries
+    uint64_t pyr_at[TKG_MAX_LEVELS + 1];
+    uint32_t n_levels;         // levels above len
+    uint64_t* jump;            // [K + 1] the chain's first links (TkRowfitArgs.jump_a)
+    uint32_t* row;             // [K + 1] the batch a document opens, 0xFFFFFFFF = none; [K] = n_batches
+    uint32_t* bmax;            // [K] the longest document of the batch that would open at k
+    const uint64_t* open;      // [n_batches + 1] the documents that open a batch; [n_batches] = K
+    uint64_t* batch_offs;      // [n_batches + 1] or NULL
+    uint32_t* batch_rowlen;    // [n_batches] or NULL
+    unsigned long long* stat;  // [0..2] += n_masked, n_short, n_long; [3] += ids of the kept documents; [4] = K; [5] = id_offs[D];
+                               // [6] = the longest kept document (atomicMax); [7] += documents of 2^32 ids or more: zeroed by the
+                               // caller.  [8] += n_oversize; [9] += sum cnt * rowlen; [10] = n_batches.  [12..15]: the chain's own
+};
+hipError_t tk_launch_regroup_select(const TkRegroupArgs& a, hipStream_t s);    // flag, stat[0..3], [6], [7] (n_docs > 0)
+hipError_t tk_launch_regroup_compact(const TkRegroupArgs& a, hipStream_t s);   // kept, stat[4], stat[5] (behind the scan of flag)
+hipError_t tk_launch_regroup_keys(const TkRegroupArgs& a, int what, hipStream_t s);   // key_out / val_out of K pairs: what = 0 the order's key of kept[k] | 1 GROUPED's length key of rank k | 2 GROUPED's group of val_in[k]
+uint32_t tk_regroup_sort_blocks(uint64_t n_kept);
+hipError_t tk_launch_regroup_hist(const TkRegroupArgs& a, uint32_t shift, hipStream_t s);      // hist of digit (key_in >> shift) & 255
+hipError_t tk_launch_regroup_scatter(const TkRegroupArgs& a, uint32_t shift, hipStream_t s);   // key_out, val_out (behind the scan of hist)
+hipError_t tk_launch_regroup_perm(const TkRegroupArgs& a, hipStream_t s);      // perm (GROUPED: shuf[val_in]; else a copy of val_in where they differ), len, src
+hipError_t tk_launch_regroup_gather(const TkRegroupArgs& a, hipStream_t s);    // out_ids, out_lab; n_out == 0: nothing is launched
+hipError_t tk_launch_regroup_pyramid(const TkRegroupArgs& a, hipStream_t s);   // pyr
+hipError_t tk_launch_regroup_nxt(const TkRegroupArgs& a, hipStream_t s);       // jump, row, bmax
+hipError_t tk_launch_regroup_batches(const TkRegroupArgs& a, hipStream_t s);   // batch_offs, batch_rowlen, stat[8..10] (behind tk_launch_chain_rounds)
 
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,

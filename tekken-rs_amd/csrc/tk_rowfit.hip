@@ -235,6 +235,11 @@ hipError_t tk_launch_rowfit_len(const TkRowfitArgs& a, hipStream_t s) {
 hipError_t tk_launch_rowfit_chain(const TkRowfitArgs& a, uint32_t rounds, hipStream_t s) {
     const dim3 grid(tky_blocks(a.n_docs + 1u, 1u << 16));
     hipLaunchKernelGGL(tk_rowfit_nxt_kernel, grid, dim3(TKY_BLOCK), 0, s, a);
+    return tk_launch_chain_rounds(a, rounds, s);
+}
+
+hipError_t tk_launch_chain_rounds(const TkRowfitArgs& a, uint32_t rounds, hipStream_t s) {
+    const dim3 grid(tky_blocks(a.n_docs + 1u, 1u << 16));
     for (uint32_t k = 0; k < rounds; ++k) hipLaunchKernelGGL(tk_rowfit_round_kernel, grid, dim3(TKY_BLOCK), 0, s, a, (int)(k & 1u));
     hipLaunchKernelGGL(tk_rowfit_open_kernel, grid, dim3(TKY_BLOCK), 0, s, a);
     return hipGetLastError();
