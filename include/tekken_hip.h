@@ -648,6 +648,67 @@ void tk_free_regroup(tk_regroup* out);
  * is 0 or the cost of two event records. */
 void tk_last_regroup_ms(const tk_ctx* ctx, float ms[4]);
 
+/* ---- word ids: the pre-tokenization piece every id came from (HF tokenizers' word_ids(), word_to_tokens(), token_to_word();
+ * no reference equivalent: the reference splits inside CoreBPE::encode, src/tekkenizer.rs:384-386, and keeps no trace of it) ----
+ * Inputs, all for the same documents: the text (bytes, doc_offsets) and the ids (ids, id_offsets: encode's own output or the
+ * caller's).  Per document d:
+ *   - F_d is the set of document-relative piece starts of the document's text under the pattern the context is set to: the
+ *     hard-coded pattern, or the JSON pattern after tk_tokenizer_set_honour_pattern / tk_ctx_set_pattern(ctx, 1).  The
+ *     document is split alone.  0 is in F_d iff the document is not empty.
+ *   - (s_i, e_i) is the byte span of id i, as tk_token_spans_device defines it.  A special id has s == e.
+ *   - begins(i) holds iff all three of these hold: s_i < e_i, s_i < doc_len(d), and s_i is in F_d.
+ *   - word_ids[i] (uint32) is TK_WORD_NONE (HF's None) if s_i == e_i.  Otherwise it is #{ j <= i in document d : begins(j) } - 1.
+ *     An id in front of the document's first begins wraps to TK_WORD_NONE.
+ *   - n_words(d) = #{ i in d : begins(i) }.
+ *   - doc_words (uint64, n_docs + 1) is the exclusive prefix sum of n_words.
+ *   - word_first[doc_words[d] + w] (uint32, only with TK_WORDS_FIRST) is i - id_offsets[d] for the id with begins(i) and
+ *     word_ids[i] == w.  The ids of word w are the non-special ids from there up to word_first of the document's next word.
+ *     For the last word, they run up to the document's last id.
+ * For encode's own output every piece is a run of whole tokens.  Then word_ids[i] is the index of the piece that holds token i
+ * (what HF returns), and n_words(d) = |F_d|.
+ * The definition is total.  It holds for any ids.  No read leaves the buffers (s_i < doc_len(d) is tested before the flag is
+ * read).  Every word_first index lies in [doc_words[d], doc_words[d + 1]) by construction.
+ * A document of 2^32 bytes or more is TK_ERR_INVALID_ARG.  An id outside the vocabulary is TK_ERR_RUNTIME.  Both are as in the
+ * spans pass.
+ * One check flag sits above the existing check bits, so one word can carry it with TK_CHECK_OFFSETS / TK_CHECK_UTF8:
+ *   TK_WORDS_CHECK_ALIGNED  per document, the ids' text is exactly as long as the document; and no piece start lies strictly
+ *                           inside a token's span (the invariant of encode that no token crosses a pre-token boundary)
+ * A failed check returns TK_ERR_RUNTIME; the message names the document (and the document-relative id index of a token that
+ * crosses a piece start), and *bad (optional) receives the first failing document.
+ * A separate pass behind the unchanged encode pipeline (csrc/tk_words.hip): the piece-start flags of the text by
+ * the split-only launch of the per-document encode kernel, which overwrites encode's temporaries and none of its outputs (a
+ * document with malformed UTF-8 is split again piece by piece: every byte outside a well-formed sequence is a character of its
+ * own there; the JSON pattern: a per-document kernel over the sequential matcher); the words kernel; the scan of the per-document
+ * counts and one 8-byte read (n_words); with TK_WORDS_FIRST the same walk once more. */
+#define TK_WORD_NONE 0xFFFFFFFFu
+#define TK_WORDS_FIRST 1u                 /* opts.flags: also the document-relative first id of every word */
+#define TK_WORDS_CHECK_ALIGNED 32
+typedef struct tk_words_opts { uint32_t flags; } tk_words_opts;
+typedef struct tk_words { uint32_t* word_ids; uint64_t* doc_words; uint32_t* word_first;
+                          uint64_t n_docs, n_ids, n_words; } tk_words;
+/* ids and text already on the device.  checks: 0 or TK_WORDS_CHECK_ALIGNED.  out's buffers are device buffers owned by the
+ * context, valid until the next words call on it, and SEPARATE from the encode, spans, units and layout outputs: what earlier
+ * calls on the context returned stays valid through this call.  d_doc_offsets must be well-formed (n_docs + 1 uint64 that end
+ * at n_bytes).  The work is enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_words_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                             const void* d_bytes, const void* d_doc_offsets, uint64_t n_bytes, int checks, const tk_words_opts* opts,
+                             void* hip_stream, tk_words* out, uint64_t* bad);
+/* tk_encode_batch_device_ex + the words pass on the same stream.  checks may combine TK_CHECK_OFFSETS / TK_CHECK_UTF8 with
+ * TK_WORDS_CHECK_ALIGNED.  *d_ids / *d_out_offsets / *n_ids as tk_encode_batch_device. */
+int tk_encode_batch_device_words(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 int add_bos, int add_eos, int checks, const tk_words_opts* opts, void* hip_stream, void** d_ids,
+                                 void** d_out_offsets, uint64_t* n_ids, tk_words* out, uint64_t* bad);
+/* Host in / host out: tk_encode_batch + the words pass (batches of the one-launch small path included).  checks: 0 or
+ * TK_WORDS_CHECK_ALIGNED.  ids_out as tk_encode_batch (tk_free_result); out's buffers are pinned host memory, released with
+ * tk_free_words (word_first is NULL without TK_WORDS_FIRST). */
+int tk_encode_batch_words(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                          int validate_utf8, int checks, const tk_words_opts* opts, tk_result* ids_out, tk_words* out, uint64_t* bad);
+void tk_free_words(tk_words* out);
+/* As tk_last_regroup_ms, for tools/words_time.py: GPU time of the stages of the context's last words pass, from events on its
+ * stream: ms[0] the split launch (with the memset of the flags), ms[1] the words kernel, ms[2] the scan of the counts (the
+ * 8-byte read behind it is not counted), ms[3] the word_first kernel.  All 0 where the pass was refused. */
+void tk_last_words_ms(const tk_ctx* ctx, float ms[4]);
+
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token
  * at POSITION i of the reference's all_special_tokens vector (src/tekkenizer.rs:108-116, 536-540);

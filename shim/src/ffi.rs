@@ -216,6 +216,23 @@ pub struct TkRegroup {
     pub n_oversize: u64,
     pub n_batch_pad: u64,
 }
+// word ids: the pre-tokenization piece of every id (tk_words_opts.flags, the check bit; include/tekken_hip.h has the definition)
+pub const TK_WORD_NONE: u32 = 0xFFFF_FFFF;
+pub const TK_WORDS_FIRST: u32 = 1;
+pub const TK_WORDS_CHECK_ALIGNED: c_int = 32;
+#[repr(C)]
+pub struct TkWordsOpts {
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkWords {
+    pub word_ids: *mut u32,
+    pub doc_words: *mut u64,
+    pub word_first: *mut u32,
+    pub n_docs: u64,
+    pub n_ids: u64,
+    pub n_words: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -329,6 +346,18 @@ extern "C" {
                                    validate_utf8: c_int, opts: *const TkRegroupOpts, out: *mut TkRegroup) -> c_int;
     pub fn tk_free_regroup(out: *mut TkRegroup);
     pub fn tk_last_regroup_ms(ctx: *const TkCtx, ms: *mut f32);
+    pub fn tk_words_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                    d_bytes: *const c_void, d_doc_offsets: *const c_void, n_bytes: u64, checks: c_int,
+                                    opts: *const TkWordsOpts, hip_stream: *mut c_void, out: *mut TkWords, bad: *mut u64) -> c_int;
+    pub fn tk_encode_batch_device_words(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                        add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkWordsOpts, hip_stream: *mut c_void,
+                                        d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkWords,
+                                        bad: *mut u64) -> c_int;
+    pub fn tk_encode_batch_words(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                 validate_utf8: c_int, checks: c_int, opts: *const TkWordsOpts, ids_out: *mut TkResult, out: *mut TkWords,
+                                 bad: *mut u64) -> c_int;
+    pub fn tk_free_words(out: *mut TkWords);
+    pub fn tk_last_words_ms(ctx: *const TkCtx, ms: *mut f32);
     // memo of merged pieces (round 4): a device table {unknown piece of 2..16 bytes -> its <= 4 ids}; never changes an id
     pub fn tk_ctx_set_memo(ctx: *mut TkCtx, log2_entries: c_int, policy: c_int) -> c_int;
     pub fn tk_ctx_memo_clear(ctx: *mut TkCtx) -> c_int;

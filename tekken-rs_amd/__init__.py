@@ -41,6 +41,9 @@ JOIN_LABELS, JOIN_PART_INDEX = 1, 2   # tk_join_opts.flags (the join entries)
 ROWFIT_I64, ROWFIT_POSITIONS, ROWFIT_SEGMENTS, ROWFIT_CU_SEQLENS, ROWFIT_LABELS, ROWFIT_DOC_START = 1, 2, 4, 8, 16, 32   # tk_rowfit_opts.flags (the rowfit entries)
 REGROUP_ORDER_KEEP, REGROUP_ORDER_LENGTH, REGROUP_ORDER_SHUFFLE, REGROUP_ORDER_GROUPED = 0, 1, 2, 3   # tk_regroup_opts.order
 REGROUP_DESC, REGROUP_LABELS, REGROUP_PERM, REGROUP_BATCHES, REGROUP_BATCH_OFFSETS, REGROUP_BATCH_ROWLEN = 1, 2, 4, 8, 16, 32   # tk_regroup_opts.flags (the regroup entries)
+WORD_NONE = 0xFFFFFFFF   # word_ids: a special id (HF's None)
+WORDS_FIRST = 1   # tk_words_opts.flags (the words entries)
+WORDS_CHECK_ALIGNED = 32   # the words entries' check (beside CHECK_OFFSETS / CHECK_UTF8 in one word)
 _ORDERS = {"keep": REGROUP_ORDER_KEEP, "length": REGROUP_ORDER_LENGTH, "shuffle": REGROUP_ORDER_SHUFFLE, "grouped": REGROUP_ORDER_GROUPED}   # the order keyword of encode_batch_regrouped
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
@@ -146,6 +149,15 @@ class _Regroup(ctypes.Structure):
                 ("batch_offsets", ctypes.c_void_p), ("batch_rowlen", ctypes.c_void_p), ("n_docs", ctypes.c_uint64), ("n_ids", ctypes.c_uint64),
                 ("n_masked", ctypes.c_uint64), ("n_short", ctypes.c_uint64), ("n_long", ctypes.c_uint64), ("n_batches", ctypes.c_uint64),
                 ("n_oversize", ctypes.c_uint64), ("n_batch_pad", ctypes.c_uint64)]
+
+
+class _WordsOpts(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32)]
+
+
+class _Words(ctypes.Structure):
+    _fields_ = [("word_ids", ctypes.c_void_p), ("doc_words", ctypes.c_void_p), ("word_first", ctypes.c_void_p),
+                ("n_docs", ctypes.c_uint64), ("n_ids", ctypes.c_uint64), ("n_words", ctypes.c_uint64)]
 
 
 _LIB = None
@@ -373,6 +385,18 @@ def lib():
     if hasattr(L, "tk_last_regroup_ms"):
         L.tk_last_regroup_ms.restype = None
         L.tk_last_regroup_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 4)]
+    if hasattr(L, "tk_words_from_ids_device"):   # (word ids: libraries built before them still load through TK_HIP_LIB)
+        wop, wp = ctypes.POINTER(_WordsOpts), ctypes.POINTER(_Words)
+        L.tk_words_from_ids_device.restype = ci
+        L.tk_words_from_ids_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u64, ci, wop, vp, wp, u64p]
+        L.tk_encode_batch_device_words.restype = ci
+        L.tk_encode_batch_device_words.argtypes = [vp, vp, vp, u64, u64, ci, ci, ci, wop, vp, vpp, vpp, u64p, wp, u64p]
+        L.tk_encode_batch_words.restype = ci
+        L.tk_encode_batch_words.argtypes = [vp, u8p, u64p, u64, ci, ci, ci, ci, wop, ctypes.POINTER(_Result), wp, u64p]
+        L.tk_free_words.restype = None
+        L.tk_free_words.argtypes = [wp]
+        L.tk_last_words_ms.restype = None
+        L.tk_last_words_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 4)]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -617,6 +641,18 @@ class RegroupResult(_LayoutResult):
         bo, rl = (_torch_wrap(x, False).cpu().tolist() for x in (v[4], v[5]))
         for b in range(self.n_batches):
             yield bo[b], bo[b + 1], rl[b]
+
+
+class WordsResult(_LayoutResult):
+    """What the device words entries return (tk_words): raw device pointers of context-owned buffers, valid until the next words
+    call on the context.  word_ids_ptr: uint32 [n_ids] (WORD_NONE for a special id; views() shows it as int32: -1);
+    doc_words_ptr: uint64 [n_docs + 1]; word_first_ptr: uint32 [n_words] or None (WORDS_FIRST).
+    views(): (word_ids as int32 [n_ids], doc_words as int64 [n_docs + 1], word_first as int32 [n_words] or None)."""
+    STRUCT, PASS = _Words, "words"
+    OUTPUTS = (("word_ids", "<i4", lambda r: (r.n_ids,), np.uint32, False), ("doc_words", "<i8", lambda r: (r.n_docs + 1,), np.uint64, False),
+               ("word_first", "<i4", lambda r: (r.n_words,), np.uint32, True))
+    COUNTS = ("n_docs", "n_ids", "n_words")
+    DICT_COUNTS = ("n_words",)
 
 
 class Engine:
@@ -985,6 +1021,58 @@ class Engine:
             raise TokenizerError(TK_ERR_INVALID_ARG, "dense_from_regroup_batch: documents %d .. %d of %d" % (first_doc, end_doc, res.n_docs))
         return self.dense_from_ids_device(res.ids_ptr, res.offsets_ptr + 8 * first_doc, end_doc - first_doc, res.n_ids, max_length, multiple_of,
                                           pad_id, 0, 0, flags, stream)
+
+    # ---- word ids (tk_words): the three entries take the text, so they are the pass's own
+    def _words_raise(self, rc, bad):
+        e = self._err(rc)
+        e.bad_doc = int(bad.value)
+        raise e
+
+    def words_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_bytes_ptr, d_doc_offs_ptr, n_bytes, flags=0, checks=0, stream=0):
+        """tk_words_from_ids_device: ids and their text resident in HBM -> the word of every id (HF's word_ids(); the definition is
+        in include/tekken_hip.h).  flags: WORDS_FIRST; checks: WORDS_CHECK_ALIGNED (a failed check raises with .bad_doc set).
+        Returns a WordsResult (context-owned device buffers, apart from every other output)."""
+        st, bad, o = _Words(), ctypes.c_uint64(0), _WordsOpts(int(flags))
+        rc = _need("tk_words_from_ids_device")(self._h, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                                               ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_doc_offs_ptr), n_bytes, int(checks),
+                                               ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(st), ctypes.byref(bad))
+        if rc != TK_OK:
+            self._words_raise(rc, bad)
+        return WordsResult(st)
+
+    def encode_batch_device_words(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, flags=0, checks=0, stream=0):
+        """tk_encode_batch_device_words: encode_batch_device + the words pass on the same stream.  checks may mix CHECK_OFFSETS /
+        CHECK_UTF8 with WORDS_CHECK_ALIGNED.  Returns (d_ids_ptr, d_out_offs_ptr, n_ids, WordsResult), all context-owned."""
+        st, bad, o = _Words(), ctypes.c_uint64(0), _WordsOpts(int(flags))
+        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        rc = _need("tk_encode_batch_device_words")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_docs, n_bytes,
+                                                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream),
+                                                   ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(st), ctypes.byref(bad))
+        if rc != TK_OK:
+            self._words_raise(rc, bad)
+        return d_ids.value, d_oo.value, int(n.value), WordsResult(st)
+
+    def encode_batch_words(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, flags=0, checks=0):
+        """tk_encode_batch_words, host in / host out: (ids uint32[T], out_offsets uint64[D+1], {"word_ids": uint32[T] (WORD_NONE
+        for a special id), "doc_words": uint64[D+1], "word_first": uint32[n_words] or None, "n_words"})."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        res, st, bad, o = _Result(), _Words(), ctypes.c_uint64(0), _WordsOpts(int(flags))
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        rc = _need("tk_encode_batch_words")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos),
+                                            int(add_eos), int(validate_utf8), int(checks), ctypes.byref(o), ctypes.byref(res), ctypes.byref(st),
+                                            ctypes.byref(bad))
+        if rc != TK_OK:
+            self._words_raise(rc, bad)
+        _, out = WordsResult.take(st)
+        ids, oo = _take_result(res)
+        return ids, oo, out
+
+    def last_words_ms(self):
+        """tk_last_words_ms: GPU milliseconds of the last words pass -- (split launch, words kernel, scan, word_first)."""
+        ms = (ctypes.c_float * 4)()
+        _need("tk_last_words_ms")(self._h, ctypes.byref(ms))
+        return tuple(float(x) for x in ms)
 
     def last_regroup_ms(self):
         """tk_last_regroup_ms: GPU time of the stages of the last regroup pass on this context: (select, sort, gather, batches)."""
@@ -1438,6 +1526,65 @@ class Tekkenizer:
                                                      max_length, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
         t = res.tensors(copy)
         return {"input_ids": t["ids"], "attention_mask": t["mask"], "lengths": t["lengths"], "n_truncated": t["n_truncated"]}
+
+    def encode_with_words(self, text, add_bos=False, add_eos=False):
+        """Tekkenizer::encode + the word of every id, HF's word_ids(): (ids, word_ids) with None for a special id.  A word is a
+        piece of the pre-tokenization split (the definition is in include/tekken_hip.h); a batch of one document."""
+        got = self.encode_batch_with_words([text], add_bos, add_eos, return_word_first=False)
+        return got["ids"].tolist(), [None if w < 0 else w for w in got["word_ids"].tolist()]
+
+    def encode_batch_with_words(self, docs, add_bos=False, add_eos=False, return_word_first=True, checks=0, return_tensors="np", copy=True):
+        """Batch form on the tokenizer's engine context (tk_encode_batch_words / tk_encode_batch_device_words): {"ids", "id_offsets"
+        (int64 [D + 1]), "word_ids" (int32, -1 for a special id), "doc_words" (int64 [D + 1]), "word_first" (the
+        document-relative first id of every word, None without return_word_first), "n_words"}.  checks: WORDS_CHECK_ALIGNED.
+        return_tensors "np": numpy; "pt": torch tensors on the tokenizer's GPU (copy=False: views of context-owned buffers, valid
+        until the next call on this tokenizer)."""
+        eng = self._device_engine()
+        _, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_with_words", docs, add_bos, add_eos, 0, return_tensors in ("pt", "np"), "return_tensors", upload=return_tensors != "np")
+        flags = WORDS_FIRST if return_word_first else 0
+        if return_tensors == "np":
+            ids, oo, w = eng.encode_batch_words(data, offs, add_bos, add_eos, False, flags, checks)
+            return {"ids": ids, "id_offsets": oo.astype(np.int64), "word_ids": w["word_ids"].view(np.int32), "doc_words": w["doc_words"].astype(np.int64),
+                    "word_first": w["word_first"], "n_words": w["n_words"]}
+        d_ids, d_oo, n, res = eng.encode_batch_device_words(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), add_bos, add_eos, flags,
+                                                           CHECK_OFFSETS | checks, stream)
+        out = res.tensors(copy)
+        out["ids"] = _torch_wrap(DeviceView(d_ids, n, "<i4"), copy)
+        out["id_offsets"] = _torch_wrap(DeviceView(d_oo, len(docs) + 1, "<i8"), copy)
+        return out
+
+    def encode_batch_padded_words(self, docs, add_bos=False, add_eos=False, max_length=None, padding="longest", truncation_side="right",
+                                  padding_side="right", pad_to_multiple_of=None, pad_id=None, dtype="int64", return_mask=True,
+                                  return_tensors="pt", copy=True):
+        """encode_batch_padded plus "word_ids" [B, L] of `dtype`: the word of every kept id, -1 for a special id and under the
+        padding.  One encode and one words pass; then the dense pass over the ids and over word_ids, one after the other with the
+        same options (word_ids as int32 elements padded with WORD_NONE, widened here -- which sign-extends; BOS / EOS survive
+        truncation in both).  return_tensors "pt": torch tensors on the tokenizer's GPU; "np": numpy copies of them."""
+        eng = self._device_engine()
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_padded_words", docs, add_bos, add_eos, pad_id,
+            padding in ("longest", "max_length") and truncation_side in ("left", "right") and padding_side in ("left", "right")
+            and dtype in ("int64", "int32") and return_tensors in ("pt", "np"), "padding / side / dtype / return_tensors")
+        import torch
+        flags = (DENSE_FIXED if padding == "max_length" else 0) | (DENSE_TRUNC_LEFT if truncation_side == "left" else 0) \
+            | (DENSE_PAD_LEFT if padding_side == "left" else 0)
+        i64 = dtype == "int64"
+        D = len(docs)
+        d_ids, d_oo, N, w = eng.encode_batch_device_words(d_bytes.data_ptr(), d_offs.data_ptr(), D, len(data), add_bos, add_eos, 0, CHECK_OFFSETS, stream)
+
+        def dense(ptr, pad_value, fl):
+            return eng.dense_from_ids_device(ptr if N else 0, d_oo, D, N, max_length, pad_to_multiple_of, pad_value, int(bool(add_bos)),
+                                             int(bool(add_eos)), fl, stream).tensors(True)
+
+        # (the first dense result is copied before the second call: both live in the dense pass's buffers)
+        d = dense(d_ids, pad, flags | (DENSE_I64 if i64 else 0) | (DENSE_MASK if return_mask else 0))
+        words = dense(w.word_ids_ptr, WORD_NONE, flags)["ids"]
+        out = {"input_ids": d["ids"], "attention_mask": d["mask"], "lengths": d["lengths"], "n_truncated": d["n_truncated"],
+               "word_ids": words.to(torch.int64) if i64 else words}
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
+        return out
 
     def encode_batch_packed(self, docs, seq_len, add_bos=True, add_eos=True, drop_last=False, pad_id=None, dtype="int64",
                             return_position_ids=True, return_segment_ids=True, return_cu_seqlens=True, return_tensors="pt", copy=True):

@@ -123,6 +123,13 @@ struct RegroupBufs {
     Event ev[6];                   // the stages of the last regroup call (tk_last_regroup_ms), created at the first one
     float ms[4] = {0.f, 0.f, 0.f, 0.f};   // selection | sort | gather kernel | batches
 };
+// the word ids (tk_words.hip): word_ids, doc_words, word_first; the work arrays (the piece-start flags of the text, the
+// per-document counts, the scan workspace, the error words; the text and offsets of a batch the one-launch small path encoded)
+struct WordsBufs {
+    DevBuf ids, dw, first, flags, cnt, bsum, err, text, toffs;
+    Event ev[6];                   // the stages of the last words call (tk_last_words_ms), created at the first one
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};   // split launch | words kernel | scan | word_first
+};
 
 struct tk_ctx {
     int device = 0;
@@ -154,6 +161,7 @@ struct tk_ctx {
     WindowBufs window;
     RowfitBufs rowfit;
     RegroupBufs regroup;
+    WordsBufs words;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy

@@ -116,6 +116,34 @@ struct TkSpansArgs {
 };
 hipError_t tk_launch_spans(const TkSpansArgs& a, int checks, hipStream_t s);
 
+// ---- word ids: the pre-tokenization piece of every id (tk_words.hip) ----
+struct TkWordsArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const uint64_t* id_offs;   // [n_docs + 1]
+    uint64_t n_docs;
+    const uint64_t* doc_offs;  // [n_docs + 1] text offsets
+    const uint8_t* flags;      // one byte per text byte: a piece starts here (the pass's own buffer, 64 zeroed bytes behind the text)
+    uint32_t* word_ids;        // [n_ids] the word of every id, TK_WORD_NONE for a special id
+    uint32_t* n_words;         // [n_docs] ids that begin a word
+    const uint64_t* doc_words; // [n_docs + 1] exclusive scan of n_words (tk_launch_words_first)
+    uint32_t* word_first;      // [n_words] the document-relative first id of every word (tk_launch_words_first)
+    unsigned long long* err;   // [5] see tk_words.hip
+    const uint8_t* tok_blob;   // token bytes by rank
+    const uint32_t* tok_offs;  // [n_ranks + 1]
+    const uint8_t* tok_inline; // [n_ranks] 16-byte entries (TkDecodeArgs::tok_inline; not read)
+    const uint8_t* tok_len8;   // [n_ranks] one-byte lengths (TkDecodeArgs::tok_len8)
+    uint32_t n_ranks, num_special;
+};
+hipError_t tk_launch_words(const TkWordsArgs& a, int check_aligned, hipStream_t s);   // word_ids, n_words, err
+hipError_t tk_launch_words_first(const TkWordsArgs& a, hipStream_t s);                // word_first (behind the scan of n_words)
+// behind the split-only launch of the encode kernel (hard-coded pattern): a document that holds a malformed UTF-8 byte is split
+// again with the sequential matcher, which takes such a byte as a character of its own (as the oracle does)
+hipError_t tk_launch_words_resplit(const TkTablesView& t, const uint8_t* bytes, const uint64_t* doc_offs, uint64_t n_docs, uint8_t* flags,
+                                   hipStream_t s);
+// flags[p] = 1 where a piece starts under the JSON pattern, every document split alone (flags zeroed by the caller)
+hipError_t tk_launch_words_split_json(const TkTablesView& t, const uint8_t* bytes, const uint64_t* doc_offs, uint64_t n_docs, uint8_t* flags,
+                                      hipStream_t s);
+
 // ---- per-token spans in code points / UTF-16 units, annotation -> token range (tk_spans_units.hip) ----
 struct TkSpansUnitsArgs {
     const uint32_t* ids;       // [n_ids] packed token ids of all documents
