@@ -709,6 +709,85 @@ void tk_free_words(tk_words* out);
  * 8-byte read behind it is not counted), ms[3] the word_first kernel.  All 0 where the pass was refused. */
 void tk_last_words_ms(const tk_ctx* ctx, float ms[4]);
 
+/* ---- sentence-pair rows: templates, truncation strategies, overflow (no reference equivalent: the reference encodes one text,
+ * src/tekkenizer.rs:378; this is the text_pair half of HF tokenizers' call: truncation = longest_first / only_first / only_second,
+ * stride, return_overflowing_tokens, token_type_ids, sequence_ids) ----
+ * Input: P pairs as 2P parts, encoded without BOS / EOS as for the join pass.  Part 2p is the first text A_p (a ids), part 2p + 1
+ * the second text B_p (b ids); d_ids and d_id_offsets[2P + 1] are as in tk_join_from_ids_device.  Options (tk_pair_opts):
+ * max_length T, strategy (TK_PAIR_LONGEST_FIRST / TK_PAIR_ONLY_FIRST / TK_PAIR_ONLY_SECOND), stride s, max_fixed F, multiple_of m
+ * (0 = none), pad_id, three fixed id lists head / sep / tail of n_head / n_sep / n_tail = 0..4 ids each ([BOS], [] or [EOS, BOS],
+ * [EOS]) and the flags below.
+ *   1. x = n_head + n_sep + n_tail ids of every row are fixed; c = T - x is left for the two texts.  c >= 2 is required.
+ *   2. TK_PAIR_LONGEST_FIRST: one row per pair, both sides cut on the right: A' = A[:a'], B' = B[:b'].  a + b <= c: nothing is
+ *      cut.  Otherwise, a <= b: a' = min(a, c / 2), b' = min(b, c - a'); a > b: b' = min(b, c / 2), a' = min(a, c - b') (c / 2
+ *      rounded down): the shorter side keeps up to half of c, the longer one what is left.  Modelled after HF's longest_first
+ *      (which removes one id at a time from the longer side); on ties with an odd c the two can differ by which side keeps
+ *      the odd id.
+ *   3. TK_PAIR_ONLY_SECOND: the fixed side is X = A, the windowed side V = B; TK_PAIR_ONLY_FIRST: X = B, V = A.  F == 0 reads as
+ *      c - 1, otherwise 1 <= F <= c - 1 is required.  f = min(|X|, F) and X' = X[:f]; cw = c - f, v = |V|.  v <= cw: one row, V
+ *      whole.  v > cw without TK_PAIR_OVERFLOW: one row with V[:cw].  v > cw with TK_PAIR_OVERFLOW: step = cw - s, the pair has
+ *      w = 1 + ceil((v - cw) / step) windows and window k holds V[k * step : min(k * step + cw, v)]; the last window may be
+ *      shorter (it is not right-aligned, as in the window pass).  s < c - F is required, so step >= 1 whatever the pair.
+ *   4. Every row is head + A-part + sep + B-part + tail; the fixed ids and X' are repeated in every window of a pair.
+ *   5. Rows are numbered pair by pair: pair_windows (uint64, P + 1 entries) is the exclusive prefix sum of w_p (w_p = 1 but for
+ *      3.), strictly increasing, and W = pair_windows[P].
+ *   6. Row length: L = T with TK_PAIR_FIXED, else L = min(the longest row, T) (x where every pair is empty, 0 for P == 0); then,
+ *      if m > 0, L is rounded up to a multiple of m.
+ *   7. Outputs, elements int32 or int64 with TK_PAIR_I64: input_ids[W, L] is the row followed by pad_id; mask[W, L] (uint8,
+ *      TK_PAIR_MASK) is 1 under the row; type_ids[W, L] (uint8, TK_PAIR_TYPE_IDS) is 0 from the head through the sep, 1 from the
+ *      first B id through the tail, 0 under a pad; sequence_ids[W, L] (uint8, TK_PAIR_SEQUENCE_IDS) is 0 under an id of A, 1
+ *      under an id of B and TK_PAIR_SEQ_NONE under a fixed id or a pad; lengths[W] (uint32); window_pair[W] (uint32) the pair of
+ *      every row (overflow_to_sample_mapping); window_start[W] (uint32) the index in V of the row's first id of V (k * step), 0
+ *      where nothing is windowed; second_start[W] (uint32) the column of the row's first B id = n_head + the row's A ids + n_sep;
+ *      spans[W, L, 2] (uint32, TK_PAIR_SPANS) the part-relative (start, end) of the id under every element, from a buffer with
+ *      the layout of tk_token_spans_device's output over the 2P parts, (0, 0) under a fixed id or a pad; pair_windows as in 5.
+ *      An unselected output is NULL.  Counts, filled always: n_pairs = P; n_windows = W; row_len = L; n_truncated = the pairs
+ *      with a row that lacks an id of A or of B (a + b > c in 2.; |X| > F or v > cw in 3., split pairs included); n_split = the
+ *      pairs with w_p > 1; n_fixed_cut = the pairs with |X| > F.
+ *   8. TK_ERR_INVALID_ARG, nothing written, an earlier pair result stays readable: c < 2 (T == 0 included: T == 0 is invalid with
+ *      and without TK_PAIR_FIXED); an unknown strategy or flag; a list count above 4; TK_PAIR_OVERFLOW or s > 0 with
+ *      TK_PAIR_LONGEST_FIRST; F > c - 1; s >= c - F; an odd number of parts; TK_PAIR_SPANS without a spans buffer in the from-ids
+ *      entry; T or the rounded L beyond 2^31 - 1; W >= 2^32; W * L > 2^36; a part of 2^32 - 1 ids or more; no part with
+ *      n_ids > 0.  A failed allocation is TK_ERR_RUNTIME.  P == 0 is valid and gives W == 0.
+ * The layout is a separate pass behind the unchanged encode pipeline (csrc/tk_pair.hip): every element of every
+ * selected output is written once, pad included, in 16-byte stores where L is a multiple of 4 (element stores otherwise).  W is not
+ * known before the per-pair counts have been summed: one small read (W, the longest row, the counts) sizes the tensors, and one
+ * wait ends the call. */
+#define TK_PAIR_LONGEST_FIRST 0
+#define TK_PAIR_ONLY_FIRST 1
+#define TK_PAIR_ONLY_SECOND 2
+#define TK_PAIR_FIXED 1
+#define TK_PAIR_I64 2
+#define TK_PAIR_MASK 4
+#define TK_PAIR_SPANS 8
+#define TK_PAIR_TYPE_IDS 16
+#define TK_PAIR_SEQUENCE_IDS 32
+#define TK_PAIR_OVERFLOW 64
+#define TK_PAIR_SEQ_NONE 255
+typedef struct tk_pair_opts { uint32_t max_length, strategy, stride, max_fixed, multiple_of, pad_id, n_head, n_sep, n_tail;
+                              uint32_t head[4], sep[4], tail[4]; uint32_t flags; } tk_pair_opts;
+typedef struct tk_pair { void* input_ids; uint8_t *mask, *type_ids, *sequence_ids; uint32_t *lengths, *window_pair, *window_start,
+                         *second_start, *spans; uint64_t* pair_windows;
+                         uint64_t n_pairs, n_windows, row_len, n_truncated, n_split, n_fixed_cut; } tk_pair;
+/* ids already on the device (encode's own outputs for add_bos = add_eos = 0, or the caller's; d_id_offsets: n_parts + 1 uint64,
+ * [0] = 0, non-decreasing, [n_parts] = n_ids -- NOT checked, as in tk_window_from_ids_device: anything else is out-of-bounds
+ * indexing on the device) -> rows.  n_parts = 2P.  d_spans: 2 * n_ids uint32 as tk_token_spans_device returns them, NULL without
+ * TK_PAIR_SPANS.  out's buffers are device buffers owned by the context, valid until the next pair call on it, and SEPARATE from
+ * the outputs of every other pass.  The work is enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_pair_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_parts, uint64_t n_ids,
+                            const void* d_spans, const tk_pair_opts* opts, void* hip_stream, tk_pair* out);
+/* tk_encode_batch_device_ex(add_bos = 0, add_eos = 0) over the 2P part texts + (with TK_PAIR_SPANS) the spans pass + the pair pass
+ * on the same stream.  checks: TK_CHECK_OFFSETS / TK_CHECK_UTF8; the ragged outputs (*d_ids / *d_out_offsets / *n_ids as
+ * tk_encode_batch_device) are returned as well. */
+int tk_encode_pairs_device(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes, int checks,
+                           const tk_pair_opts* opts, void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids,
+                           tk_pair* out);
+/* Host in / host out: tk_encode_batch over the part texts + the pair pass (batches of the one-launch small path included).  out's
+ * buffers are pinned host memory, released with tk_free_pair (an unselected output is NULL). */
+int tk_encode_pairs(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_parts, int validate_utf8,
+                    const tk_pair_opts* opts, tk_pair* out);
+void tk_free_pair(tk_pair* out);
+
 /* ---- decode: batch form of Tekkenizer::decode (src/tekkenizer.rs:436-560) ----
  * The engine needs the special-token strings for TK_POLICY_KEEP: entry i is the string of the special token
  * at POSITION i of the reference's all_special_tokens vector (src/tekkenizer.rs:108-116, 536-540);

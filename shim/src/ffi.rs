@@ -94,6 +94,53 @@ pub struct TkSeqpack {
     pub n_segments: u64,
     pub max_seqlen: u64,
 }
+// sentence-pair rows (tk_pair_opts.strategy / .flags; include/tekken_hip.h has the definition)
+pub const TK_PAIR_LONGEST_FIRST: u32 = 0;
+pub const TK_PAIR_ONLY_FIRST: u32 = 1;
+pub const TK_PAIR_ONLY_SECOND: u32 = 2;
+pub const TK_PAIR_FIXED: u32 = 1;
+pub const TK_PAIR_I64: u32 = 2;
+pub const TK_PAIR_MASK: u32 = 4;
+pub const TK_PAIR_SPANS: u32 = 8;
+pub const TK_PAIR_TYPE_IDS: u32 = 16;
+pub const TK_PAIR_SEQUENCE_IDS: u32 = 32;
+pub const TK_PAIR_OVERFLOW: u32 = 64;
+pub const TK_PAIR_SEQ_NONE: u8 = 255;
+#[repr(C)]
+pub struct TkPairOpts {
+    pub max_length: u32,
+    pub strategy: u32,
+    pub stride: u32,
+    pub max_fixed: u32,
+    pub multiple_of: u32,
+    pub pad_id: u32,
+    pub n_head: u32,
+    pub n_sep: u32,
+    pub n_tail: u32,
+    pub head: [u32; 4],
+    pub sep: [u32; 4],
+    pub tail: [u32; 4],
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkPair {
+    pub input_ids: *mut c_void,
+    pub mask: *mut u8,
+    pub type_ids: *mut u8,
+    pub sequence_ids: *mut u8,
+    pub lengths: *mut u32,
+    pub window_pair: *mut u32,
+    pub window_start: *mut u32,
+    pub second_start: *mut u32,
+    pub spans: *mut u32,
+    pub pair_windows: *mut u64,
+    pub n_pairs: u64,
+    pub n_windows: u64,
+    pub row_len: u64,
+    pub n_truncated: u64,
+    pub n_split: u64,
+    pub n_fixed_cut: u64,
+}
 // overlapping windows for long documents (tk_window_opts.flags; include/tekken_hip.h has the definition)
 pub const TK_WINDOW_FIXED: u32 = 1;
 pub const TK_WINDOW_I64: u32 = 2;
@@ -311,6 +358,16 @@ extern "C" {
     pub fn tk_encode_batch_window(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
                                   validate_utf8: c_int, opts: *const TkWindowOpts, out: *mut TkWindow) -> c_int;
     pub fn tk_free_window(out: *mut TkWindow);
+    // sentence-pair rows: the ids of 2P parts (first text, second text) as rows head + A + sep + B + tail, cut or split into
+    // overlapping windows (+ mask, type ids, sequence ids, spans, the mapping back to the pairs), fused with encode, host form
+    pub fn tk_pair_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_parts: u64, n_ids: u64,
+                                   d_spans: *const c_void, opts: *const TkPairOpts, hip_stream: *mut c_void, out: *mut TkPair) -> c_int;
+    pub fn tk_encode_pairs_device(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_parts: u64, n_bytes: u64,
+                                  checks: c_int, opts: *const TkPairOpts, hip_stream: *mut c_void, d_ids: *mut *mut c_void,
+                                  d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkPair) -> c_int;
+    pub fn tk_encode_pairs(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_parts: u64, validate_utf8: c_int,
+                           opts: *const TkPairOpts, out: *mut TkPair) -> c_int;
+    pub fn tk_free_pair(out: *mut TkPair);
     // chat batches: the ids of text parts joined with control ids per conversation (+ labels, part_index), fused with encode, host form
     pub fn tk_join_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_parts: u64, n_ids: u64,
                                    d_part_ctrl: *const c_void, d_part_flags: *const c_void, d_conv_offsets: *const c_void, n_convs: u64,

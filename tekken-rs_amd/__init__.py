@@ -34,6 +34,10 @@ _UNITS = {"byte": UNIT_BYTE, "char": UNIT_CHAR, "utf16": UNIT_UTF16}   # the off
 DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
 SEQPACK_I64, SEQPACK_POSITIONS, SEQPACK_SEGMENTS, SEQPACK_CU_SEQLENS, SEQPACK_DROP_LAST = 1, 2, 4, 8, 16   # tk_seqpack_opts.flags (the packed entries)
 WINDOW_FIXED, WINDOW_I64, WINDOW_MASK, WINDOW_SPANS = 1, 2, 4, 8   # tk_window_opts.flags (the window entries)
+PAIR_LONGEST_FIRST, PAIR_ONLY_FIRST, PAIR_ONLY_SECOND = 0, 1, 2   # tk_pair_opts.strategy
+PAIR_FIXED, PAIR_I64, PAIR_MASK, PAIR_SPANS, PAIR_TYPE_IDS, PAIR_SEQUENCE_IDS, PAIR_OVERFLOW = 1, 2, 4, 8, 16, 32, 64   # tk_pair_opts.flags (the pair entries)
+PAIR_SEQ_NONE = 255   # sequence_ids: a fixed id or a pad (HF's None)
+_STRATEGIES = {"longest_first": PAIR_LONGEST_FIRST, "only_first": PAIR_ONLY_FIRST, "only_second": PAIR_ONLY_SECOND}   # the truncation keyword of encode_pairs
 CHECK_PARTS = 16   # the join entries: conv_offsets and the control ids are checked (beside CHECK_OFFSETS / CHECK_UTF8 in one word)
 JOIN_NONE = 0xFFFFFFFF   # part_ctrl: the part has no control id
 PART_LABEL_CTRL, PART_LABEL_TEXT = 1, 2   # part_flags
@@ -116,6 +120,21 @@ class _Window(ctypes.Structure):
     _fields_ = [("input_ids", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("window_doc", ctypes.c_void_p),
                 ("window_start", ctypes.c_void_p), ("doc_windows", ctypes.c_void_p), ("spans", ctypes.c_void_p),
                 ("n_docs", ctypes.c_uint64), ("n_windows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_split", ctypes.c_uint64)]
+
+
+class _PairOpts(ctypes.Structure):
+    _fields_ = [("max_length", ctypes.c_uint32), ("strategy", ctypes.c_uint32), ("stride", ctypes.c_uint32), ("max_fixed", ctypes.c_uint32),
+                ("multiple_of", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("n_head", ctypes.c_uint32), ("n_sep", ctypes.c_uint32),
+                ("n_tail", ctypes.c_uint32), ("head", ctypes.c_uint32 * 4), ("sep", ctypes.c_uint32 * 4), ("tail", ctypes.c_uint32 * 4),
+                ("flags", ctypes.c_uint32)]
+
+
+class _Pair(ctypes.Structure):
+    _fields_ = [("input_ids", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("type_ids", ctypes.c_void_p), ("sequence_ids", ctypes.c_void_p),
+                ("lengths", ctypes.c_void_p), ("window_pair", ctypes.c_void_p), ("window_start", ctypes.c_void_p),
+                ("second_start", ctypes.c_void_p), ("spans", ctypes.c_void_p), ("pair_windows", ctypes.c_void_p),
+                ("n_pairs", ctypes.c_uint64), ("n_windows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_truncated", ctypes.c_uint64),
+                ("n_split", ctypes.c_uint64), ("n_fixed_cut", ctypes.c_uint64)]
 
 
 class _JoinOpts(ctypes.Structure):
@@ -363,6 +382,16 @@ def lib():
                            ("tk_encode_batch_%s", [vp, u8p, u64p, u64, ci, ci, ci, op, rp]), ("tk_free_%s", [rp])):
             fn = getattr(L, name % R.PASS)
             fn.restype, fn.argtypes = (None if name == "tk_free_%s" else ci), args
+    if hasattr(L, "tk_pair_from_ids_device"):   # (sentence-pair rows: libraries built before them still load through TK_HIP_LIB)
+        pop, pp = ctypes.POINTER(_PairOpts), ctypes.POINTER(_Pair)
+        L.tk_pair_from_ids_device.restype = ci
+        L.tk_pair_from_ids_device.argtypes = [vp, vp, vp, u64, u64, vp, pop, vp, pp]
+        L.tk_encode_pairs_device.restype = ci
+        L.tk_encode_pairs_device.argtypes = [vp, vp, vp, u64, u64, ci, pop, vp, vpp, vpp, u64p, pp]
+        L.tk_encode_pairs.restype = ci
+        L.tk_encode_pairs.argtypes = [vp, u8p, u64p, u64, ci, pop, pp]
+        L.tk_free_pair.restype = None
+        L.tk_free_pair.argtypes = [pp]
     jop, jp = ctypes.POINTER(_JoinOpts), ctypes.POINTER(_Join)
     if hasattr(L, "tk_ragged_from_dense_device"):
         L.tk_ragged_from_dense_device.restype = ci
@@ -576,6 +605,37 @@ class WindowResult(_LayoutResult):
                ("spans", "<i4", lambda r: (r.n_windows, r.row_len, 2), np.uint32, True))
     COUNTS = ("n_docs", "n_windows", "row_len", "n_split")
     DICT_COUNTS = ("n_windows", "n_split")
+
+
+def _pair_opts(max_length, strategy=PAIR_LONGEST_FIRST, stride=0, max_fixed=0, multiple_of=0, pad_id=0, head=(), sep=(), tail=(), flags=0):
+    # (a list of more than 4 ids keeps its count and its first 4 ids: the entry refuses the count)
+    lists = [(ctypes.c_uint32 * 4)(*[int(x) for x in list(l)[:4]]) for l in (head, sep, tail)]
+    return _PairOpts(int(max_length or 0), int(strategy), int(stride or 0), int(max_fixed or 0), int(multiple_of or 0), int(pad_id),
+                     len(head), len(sep), len(tail), lists[0], lists[1], lists[2], int(flags))
+
+
+def _windows(r):
+    return (r.n_windows, r.row_len)
+
+
+class PairResult(_LayoutResult):
+    """What the device pair entries return (tk_pair): raw device pointers of context-owned buffers, valid until the next pair call
+    on the context.  input_ids_ptr: int32 or int64 [n_windows, row_len]; mask_ptr / type_ids_ptr / sequence_ids_ptr: uint8
+    [n_windows, row_len] or None (sequence_ids: PAIR_SEQ_NONE under a fixed id or a pad); lengths_ptr / window_pair_ptr /
+    window_start_ptr / second_start_ptr: uint32 [n_windows] (views() shows them as int32: each is below 2^31 for every batch a
+    tensor can hold); spans_ptr: uint32 [n_windows, row_len, 2] or None; pair_windows_ptr: uint64 [n_pairs + 1].
+    views(): one view per output in this order, an unselected one None."""
+    STRUCT, PASS, I64 = _Pair, "pair", PAIR_I64
+    OUTPUTS = (("input_ids", None, _windows, None, False), ("mask", "|u1", _windows, np.uint8, True),
+               ("type_ids", "|u1", _windows, np.uint8, True), ("sequence_ids", "|u1", _windows, np.uint8, True),
+               ("lengths", "<i4", lambda r: (r.n_windows,), np.uint32, False),
+               ("window_pair", "<i4", lambda r: (r.n_windows,), np.uint32, False),
+               ("window_start", "<i4", lambda r: (r.n_windows,), np.uint32, False),
+               ("second_start", "<i4", lambda r: (r.n_windows,), np.uint32, False),
+               ("spans", "<i4", lambda r: (r.n_windows, r.row_len, 2), np.uint32, True),
+               ("pair_windows", "<i8", lambda r: (r.n_pairs + 1,), np.uint64, False))
+    COUNTS = ("n_pairs", "n_windows", "row_len", "n_truncated", "n_split", "n_fixed_cut")
+    DICT_COUNTS = ("n_windows", "n_truncated", "n_split", "n_fixed_cut")
 
 
 class JoinResult(_LayoutResult):
@@ -1119,6 +1179,37 @@ class Engine:
         [n_windows, row_len, 2] or None) and the counts n_windows, n_split."""
         o = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags)
         return self._encode_host(WindowResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
+
+    def pair_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, max_length, strategy=PAIR_LONGEST_FIRST, stride=0, max_fixed=0,
+                             multiple_of=0, pad_id=0, head=(), sep=(), tail=(), flags=0, d_spans_ptr=0, stream=0):
+        """tk_pair_from_ids_device: the ragged ids of 2P parts resident in HBM (part 2p the first text, part 2p + 1 the second) ->
+        rows head + A + sep + B + tail [n_windows, row_len] (+ mask, type_ids, sequence_ids, spans from d_spans_ptr by flag, lengths,
+        window_pair, window_start, second_start, pair_windows); the definition is in include/tekken_hip.h.  Returns a PairResult
+        (context-owned device buffers, apart from every other output)."""
+        o = _pair_opts(max_length, strategy, stride, max_fixed, multiple_of, pad_id, head, sep, tail, flags)
+        return self._from_ids_device(PairResult, o, flags, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, (d_spans_ptr,), stream)
+
+    def encode_pairs_device(self, d_bytes_ptr, d_offs_ptr, n_parts, n_bytes, max_length, strategy=PAIR_LONGEST_FIRST, stride=0, max_fixed=0,
+                            multiple_of=0, pad_id=0, head=(), sep=(), tail=(), flags=0, checks=0, stream=0):
+        """tk_encode_pairs_device: the 2P part texts encoded one by one without BOS / EOS (+ the spans pass with PAIR_SPANS) + the
+        pair pass on the same stream.  Returns (d_ids_ptr, d_out_offs_ptr, n_ids, PairResult), all context-owned."""
+        o = _pair_opts(max_length, strategy, stride, max_fixed, multiple_of, pad_id, head, sep, tail, flags)
+        st, d_ids, d_oo, n = _Pair(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        self._call("tk_encode_pairs_device", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_parts, n_bytes, int(checks),
+                   ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(d_ids), ctypes.byref(d_oo), ctypes.byref(n), ctypes.byref(st))
+        return d_ids.value, d_oo.value, int(n.value), PairResult(st, int(flags))
+
+    def encode_pairs(self, data, offs, max_length, strategy=PAIR_LONGEST_FIRST, stride=0, max_fixed=0, multiple_of=0, pad_id=0, head=(),
+                     sep=(), tail=(), flags=0, validate_utf8=False):
+        """tk_encode_pairs, host in / host out: a dict of numpy arrays by output name (PairResult.OUTPUTS; an unselected one: None)
+        and the counts n_windows, n_truncated, n_split, n_fixed_cut."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        o, st = _pair_opts(max_length, strategy, stride, max_fixed, multiple_of, pad_id, head, sep, tail, flags), _Pair()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        self._call("tk_encode_pairs", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(validate_utf8), ctypes.byref(o),
+                   ctypes.byref(st))
+        return PairResult.take(st, int(flags))[1]
 
     def join_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, d_part_ctrl_ptr, d_part_flags_ptr, d_conv_offs_ptr, n_convs,
                              ignore_index=-100, flags=0, checks=0, stream=0):
@@ -1720,6 +1811,79 @@ class Tekkenizer:
         out = {"input_ids": t["input_ids"], "attention_mask": t["mask"], "lengths": t["lengths"], "overflow_to_sample_mapping": t["window_doc"],
                "window_start": t["window_start"], "doc_windows": t["doc_windows"], "offset_mapping": t["spans"],
                "n_windows": t["n_windows"], "n_split": t["n_split"]}
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
+        return out
+
+    def _fixed_ids(self, ids, default):
+        """The head / sep / tail keyword of encode_pairs as a list of ids: None is the default, a name goes through get_control_token."""
+        if ids is None:
+            return default()
+        if isinstance(ids, (str, int)):
+            ids = [ids]
+        return [self.get_control_token(x) if isinstance(x, str) else int(x) for x in ids]
+
+    def encode_pairs(self, first, second, max_length, truncation="longest_first", stride=0, return_overflowing_tokens=False, max_fixed=None,
+                     head=None, sep=(), tail=None, padding="max_length", pad_to_multiple_of=None, pad_id=None, dtype="int64",
+                     return_attention_mask=True, return_token_type_ids=True, return_sequence_ids=False, return_offsets_mapping=False,
+                     offsets_unit="byte", return_tensors="pt", copy=True):
+        """Sentence-pair rows, HF's tokenizer(text, text_pair, ...) (tk_encode_pairs_device / tk_encode_pairs; the definition is in
+        include/tekken_hip.h): row p is head + first[p] + sep + second[p] + tail, the two texts encoded on their own (no token
+        spans the seam).  head / sep / tail: at most 4 ids or control-token names each (defaults [bos], (), [eos]).  truncation
+        "longest_first" cuts both sides on the right to share max_length; "only_second" / "only_first" keep (at most max_fixed
+        ids of) the other side and cut the named one -- or, with return_overflowing_tokens, split it into windows that overlap by
+        `stride` ids and all repeat the other side (extractive QA: the question in front of every slice of the context).
+        {"input_ids": [W, L] of `dtype`, "attention_mask" / "token_type_ids" / "sequence_ids": uint8 [W, L] or None (sequence_ids:
+        0 under first, 1 under second, PAIR_SEQ_NONE = 255 under a fixed id or a pad), "lengths", "overflow_to_sample_mapping",
+        "window_start" (the index in the windowed side's ids of the row's first id of it), "second_start" (the column of the row's
+        first id of second): int32 [W], "pair_windows": int64 [P + 1] the first row of every pair, "offset_mapping": int32
+        [W, L, 2] the (start, end) span under every element relative to its own text ((0, 0) under a fixed id or a pad) or None --
+        in bytes, or with offsets_unit "char" / "utf16" in code points / UTF-16 units --, "n_windows", "n_truncated", "n_split",
+        "n_fixed_cut": int}.  A QA answer's token range in its context (spans_locate) lies in a row at columns
+        second_start + (token - window_start).
+        padding "max_length": L = max_length, "longest": L = the longest row; then rounded up to pad_to_multiple_of.  pad_id None:
+        self.pad_id().  return_tensors "pt": torch tensors on the tokenizer's GPU (copy=False: views of context-owned buffers,
+        valid until the next call on this tokenizer); "np": numpy."""
+        eng = self._device_engine()
+        unit = self._unit(offsets_unit)
+        if len(first) != len(second):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_pairs: %d first texts, %d second texts" % (len(first), len(second)))
+        in_units = unit != UNIT_BYTE and return_offsets_mapping
+        parts = [t for pair in zip(first, second) for t in pair]
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_pairs", parts, False, False, pad_id,
+            truncation in _STRATEGIES and padding in ("longest", "max_length") and dtype in ("int64", "int32") and return_tensors in ("pt", "np"),
+            "truncation / padding / dtype / return_tensors", {"max_length": max_length, "stride": stride, "max_fixed": max_fixed or 0},
+            upload=return_tensors != "np" or in_units)
+        lists = (self._fixed_ids(head, lambda: [self.bos_id()]), self._fixed_ids(sep, list), self._fixed_ids(tail, lambda: [self.eos_id()]))
+        if not all(0 <= x < 2 ** 32 for l in lists for x in l):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_pairs: a head / sep / tail id is outside 0 .. 2^32 - 1")
+        flags = (PAIR_FIXED if padding == "max_length" else 0) | (PAIR_I64 if dtype == "int64" else 0) \
+            | (PAIR_MASK if return_attention_mask else 0) | (PAIR_TYPE_IDS if return_token_type_ids else 0) \
+            | (PAIR_SEQUENCE_IDS if return_sequence_ids else 0) | (PAIR_SPANS if return_offsets_mapping else 0) \
+            | (PAIR_OVERFLOW if return_overflowing_tokens else 0)
+        args = (max_length, _STRATEGIES[truncation], stride, max_fixed or 0, pad_to_multiple_of or 0, pad) + lists + (flags,)
+        names = (("input_ids", "input_ids"), ("attention_mask", "mask"), ("token_type_ids", "type_ids"), ("sequence_ids", "sequence_ids"),
+                 ("lengths", "lengths"), ("overflow_to_sample_mapping", "window_pair"), ("window_start", "window_start"),
+                 ("second_start", "second_start"), ("pair_windows", "pair_windows"), ("offset_mapping", "spans"))
+        if return_tensors == "np" and not in_units:
+            r = eng.encode_pairs(data, offs, *args)
+            signed = {np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
+            out = {k: None if r[n] is None else r[n].astype(signed.get(r[n].dtype, r[n].dtype)) for k, n in names}
+            out.update({k: r[k] for k in PairResult.DICT_COUNTS})
+            return out
+        import torch
+        if in_units:
+            # three calls on the stream: encode, the units pass, the pair pass over the unit spans
+            p_ids, p_oo, p_sp, n = eng.encode_batch_device_spans_units(d_bytes.data_ptr(), d_offs.data_ptr(), len(parts), len(data), False, False,
+                                                                       unit, CHECK_OFFSETS, stream)
+            res = eng.pair_from_ids_device(p_ids, p_oo, len(parts), n, *args, d_spans_ptr=p_sp, stream=stream)
+        else:
+            _, _, _, res = eng.encode_pairs_device(d_bytes.data_ptr(), d_offs.data_ptr(), len(parts), len(data), *args, checks=CHECK_OFFSETS,
+                                                   stream=stream)
+        t = res.tensors(copy)
+        out = {k: t[n] for k, n in names}
+        out.update({k: t[k] for k in PairResult.DICT_COUNTS})
         if return_tensors == "np":
             out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
         return out

@@ -105,6 +105,10 @@ struct JoinBufs { DevBuf ids, offs, labels, pidx, stat, has, cb, start, plocal, 
 // the overlapping windows (tk_window.hip): the tensor, its mask and spans, the per-window arrays, doc_windows; the work arrays
 // (dw_next: the scan that becomes doc_windows once the call is accepted, the counts, the scan workspace, the statistics words)
 struct WindowBufs { DevBuf ids, mask, spans, len, doc, start, dw, dw_next, cnt, bsum, stat; };
+// the sentence-pair rows (tk_pair.hip): the tensor, its mask, type ids, sequence ids and spans, the per-row arrays, pair_windows;
+// the work arrays (pw_next: the scan that becomes pair_windows once the call is accepted, the counts, the scan workspace, the
+// statistics words)
+struct PairBufs { DevBuf ids, mask, type, seq, spans, len, pair, start, second, pw, pw_next, cnt, bsum, stat; };
 // the whole-document rows (tk_rowfit.hip): the four tensors, cu_seqlens, doc_start and the statistics words; the work arrays
 // (lengths and their scans, the jump tables, the row marks, the row openers, the per-document segment numbers, the per-row
 // pad flags and their scan, the scan workspace)
@@ -159,6 +163,7 @@ struct tk_ctx {
     SeqpackBufs seqpack;
     JoinBufs join;
     WindowBufs window;
+    PairBufs pair;
     RowfitBufs rowfit;
     RegroupBufs regroup;
     WordsBufs words;

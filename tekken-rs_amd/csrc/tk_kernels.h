@@ -248,6 +248,40 @@ struct TkWindowArgs {
 hipError_t tk_launch_window_counts(const TkWindowArgs& a, hipStream_t s);   // counts, stat
 hipError_t tk_launch_window(const TkWindowArgs& a, int i64, hipStream_t s); // the outputs; n_rows == 0: nothing is launched
 
+// ---- sentence-pair rows (tk_pair.hip) ----
+struct TkPairArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of the 2P parts, encoded without BOS / EOS
+    const uint64_t* id_offs;   // [2 * n_pairs + 1]
+    const uint32_t* in_spans;  // [2 * n_ids] (start, end) per id, or NULL
+    uint64_t n_pairs;
+    uint32_t max_len, cap;     // T; c = T - x
+    uint32_t strategy;         // TK_PAIR_LONGEST_FIRST / _ONLY_FIRST / _ONLY_SECOND
+    uint32_t overflow;         // TK_PAIR_OVERFLOW: a windowed side longer than its room gives several rows
+    uint32_t stride, max_fixed;    // s; F (resolved: never 0 with an ONLY_ strategy)
+    uint32_t n_head, n_sep, n_tail;
+    uint32_t head[4], sep[4], tail[4];
+    uint32_t pad_id;
+    uint32_t row_len;          // L (< 2^31; 0: only the per-row outputs are written)
+    uint64_t n_rows;           // W (< 2^32)
+    uint32_t* counts;          // [n_pairs] w_p
+    const uint64_t* pair_windows;  // [n_pairs + 1] exclusive scan of counts, strictly increasing
+    void* out;                 // [W * L] int32 or int64
+    uint8_t* mask;             // [W * L] or NULL
+    uint8_t* type_ids;         // [W * L] or NULL
+    uint8_t* seq_ids;          // [W * L] or NULL
+    uint32_t* out_spans;       // [W * L * 2] or NULL
+    uint32_t* lengths;         // [W]
+    uint32_t* window_pair;     // [W]
+    uint32_t* window_start;    // [W]
+    uint32_t* second_start;    // [W]
+    // zeroed by the caller: [0] the longest row and [4] the longest part, clamped to 2^32 - 1 (atomicMax); [1] += pairs that lost
+    // an id, [2] += pairs with w_p > 1, [3] += pairs whose fixed side was cut
+    unsigned long long* stat;
+    uint32_t units, rb, magic; // the launch shape (set by the launcher): units a row, rows a block, 2^32 / units rounded up
+};
+hipError_t tk_launch_pair_counts(const TkPairArgs& a, hipStream_t s);     // counts, stat
+hipError_t tk_launch_pair(const TkPairArgs& a, int i64, hipStream_t s);   // the outputs; n_rows == 0: nothing is launched
+
 // ---- chat batches: parts joined with control ids, plus labels (tk_join.hip) ----
 struct TkJoinArgs {
     const uint32_t* ids;       // [n_ids] packed token ids of all parts, encoded without BOS / EOS

@@ -1,4 +1,4 @@
-// tk_layout.h -- what the layout kernels share (tk_dense.hip, tk_seqpack.hip, tk_join.hip, tk_window.hip, tk_rowfit.hip, tk_regroup.hip: ragged ids into what a model
+// tk_layout.h -- what the layout kernels share (tk_dense.hip, tk_seqpack.hip, tk_join.hip, tk_window.hip, tk_pair.hip, tk_rowfit.hip, tk_regroup.hip: ragged ids into what a model
 // consumes):
 // the 4-wide element access of an int32 / int64 tensor, the searches for "which document / part holds stream position g", the
 // staging of a tile's starts, the grid size and the one-atomic-a-wave tails.  (Names: tky_ -- tkl_ is tk_long_impl.h's.)
