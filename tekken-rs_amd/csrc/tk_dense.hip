@@ -7,12 +7,8 @@
 //   ids[oo[d] + (j < split ? j : j + (n - k))],   split = TRUNC_LEFT ? h : lim - t
 // (nothing is truncated: n - k == 0, every j reads itself).  Row d is those k ids and L - k pads, on the side PAD_LEFT says.
 //
-// Launch shape, shared by both directions: the unit of work is a group of 4 consecutive elements of one row where L % 4 == 0
-// (one 16-byte store for int32, two for int64, one dword of mask), a single element otherwise.  A block takes `rb` consecutive
-// rows (rb * G units <= TKN_TILE, G units a row) and its threads walk the rb * G units in order, so a wave covers several
-// short rows and every lane has work; the row of a unit comes from a per-launch reciprocal (exact below TKN_TILE), not from a
-// division.  A row of more than TKN_TILE units is one block row (rb == 1) split over blockIdx.y.  oo[d], oo[d + 1] and the
-// arithmetic above are per unit; the source ids are dword loads (a row's source run starts at an arbitrary id).  Every output
+// Both directions have the row-group launch shape (tk_rows.h; the block's part: tk_layout.h TkyRowGroup).  oo[d], oo[d + 1] and
+// the arithmetic above are per unit; the source ids are dword loads (a row's source run starts at an arbitrary id).  Every output
 // element is written exactly once, pad included.  The lane that holds a row's first unit writes lengths[d]; the truncated
 // documents are counted per lane across the grid stride and added with one atomic per wave (a scan over the wave's lanes).
 #include <hip/hip_runtime.h>
@@ -21,27 +17,17 @@
 #include "tk_kernels.h"
 #include "tk_layout.h"
 
-#define TKN_TILE 2048u     /* units of a block's row group (8 a thread); the reciprocal is exact for indices below it */
-
-// row of unit li inside the block's row group (li < TKN_TILE when rb > 1)
-__device__ __forceinline__ uint32_t tkn_row_of(const TkDenseArgs& a, uint32_t li) {
-    if (a.rb == 1u) return 0u;
-    return a.units == 1u ? li : __umulhi(li, a.magic);
-}
-
 template <int I64, int MASK, int VEC>
 __global__ __launch_bounds__(TKY_BLOCK) void tk_dense_kernel(TkDenseArgs a) {
     constexpr uint32_t W = VEC ? 4u : 1u;
-    const uint32_t G = a.units, L = a.row_len;
-    const uint64_t n_rb = (a.n_docs + a.rb - 1) / a.rb;
+    const uint32_t G = a.rows.units, L = a.row_len;
+    const uint64_t n_rb = tky_row_groups(a.rows, a.n_docs);
     uint32_t n_trunc = 0;
     for (uint64_t b = blockIdx.x; b < n_rb; b += gridDim.x) {
-        const uint64_t row0 = b * a.rb;
-        const uint32_t nrows = a.n_docs - row0 < a.rb ? (uint32_t)(a.n_docs - row0) : a.rb;
-        const uint32_t total = nrows * G;      // rb > 1: <= TKN_TILE; rb == 1: G < 2^31
-        for (uint32_t li = blockIdx.y * TKY_BLOCK + threadIdx.x; li < total; li += TKY_BLOCK * gridDim.y) {
-            const uint32_t r = tkn_row_of(a, li), cg = li - r * G;
-            const uint64_t d = row0 + r;
+        const TkyRowGroup g(a.rows, a.n_docs, b);
+        for (uint32_t li = g.first(); li < g.total; li += g.step()) {
+            const uint32_t r = tky_row_of(a.rows, li), cg = li - r * G;
+            const uint64_t d = g.row0 + r;
             const uint64_t o0 = a.id_offs[d], n = a.id_offs[d + 1] - o0;
             const uint32_t k = n < (uint64_t)a.lim ? (uint32_t)n : a.lim;
             const uint64_t skip = n - k;                      // ids cut out behind `split`
@@ -62,10 +48,7 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_dense_kernel(TkDenseArgs a) {
             }
             const uint64_t at = d * L + (uint64_t)cg * W;
             tky_store<I64, VEC>(a.out, at, v);
-            if (MASK) {
-                if (VEC) *reinterpret_cast<uint32_t*>(a.mask + at) = mbits;
-                else a.mask[at] = (uint8_t)mbits;
-            }
+            if (MASK) tky_store_plane<VEC>(a.mask, at, mbits);
         }
     }
     if (blockIdx.y == 0) tky_wave_add(a.stat + 1, n_trunc);   // the truncated documents of this wave's row leaders
@@ -75,8 +58,7 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_dense_kernel(TkDenseArgs a) {
 __global__ __launch_bounds__(TKY_BLOCK) void tk_dense_maxlen_kernel(const uint64_t* id_offs, uint64_t n_docs, unsigned long long* stat) {
     uint32_t m = 0;
     for (uint64_t d = (uint64_t)blockIdx.x * TKY_BLOCK + threadIdx.x; d < n_docs; d += (uint64_t)gridDim.x * TKY_BLOCK) {
-        const uint64_t n = id_offs[d + 1] - id_offs[d];
-        const uint32_t n32 = n < 0xFFFFFFFFull ? (uint32_t)n : 0xFFFFFFFFu;
+        const uint32_t n32 = tky_len32(id_offs[d + 1] - id_offs[d]);
         m = m > n32 ? m : n32;
     }
     tky_wave_max(stat, m);
@@ -118,19 +100,17 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_dense_rowlen_kernel(TkRaggedArgs
     }
 }
 
-// out_ids[offs[d] + j] = the j-th element of row d's unpadded end, j < lens[d]; the launch shape of tk_dense_kernel
+// out_ids[offs[d] + j] = the j-th element of row d's unpadded end, j < lens[d]; the row-group launch shape
 template <int I64, int VEC>
-__global__ __launch_bounds__(TKY_BLOCK) void tk_ragged_kernel(TkRaggedArgs a, TkDenseArgs shape) {
+__global__ __launch_bounds__(TKY_BLOCK) void tk_ragged_kernel(TkRaggedArgs a, TkyRows shape) {
     constexpr uint32_t W = VEC ? 4u : 1u;
     const uint32_t G = shape.units, L = a.row_len;
-    const uint64_t n_rb = (a.n_docs + shape.rb - 1) / shape.rb;
+    const uint64_t n_rb = tky_row_groups(shape, a.n_docs);
     for (uint64_t b = blockIdx.x; b < n_rb; b += gridDim.x) {
-        const uint64_t row0 = b * shape.rb;
-        const uint32_t nrows = a.n_docs - row0 < shape.rb ? (uint32_t)(a.n_docs - row0) : shape.rb;
-        const uint32_t total = nrows * G;
-        for (uint32_t li = blockIdx.y * TKY_BLOCK + threadIdx.x; li < total; li += TKY_BLOCK * gridDim.y) {
-            const uint32_t r = tkn_row_of(shape, li), cg = li - r * G;
-            const uint64_t d = row0 + r;
+        const TkyRowGroup g(shape, a.n_docs, b);
+        for (uint32_t li = g.first(); li < g.total; li += g.step()) {
+            const uint32_t r = tky_row_of(shape, li), cg = li - r * G;
+            const uint64_t d = g.row0 + r;
             const uint32_t k = a.lens[d];
             const uint32_t lead = a.pad_left ? L - k : 0u;
             const uint32_t j0 = cg * W - lead;                // (wraps under the left pads)
@@ -149,22 +129,6 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_ragged_kernel(TkRaggedArgs a, Tk
     }
 }
 
-// the launch shape of a [n_docs, row_len] tensor (see the head of this file); false: nothing to launch
-static bool tkn_shape(TkDenseArgs& a, dim3& grid) {
-    if (a.n_docs == 0 || a.row_len == 0) return false;
-    const bool vec = a.row_len % 4u == 0u;
-    a.units = vec ? a.row_len / 4u : a.row_len;
-    a.rb = a.units <= TKN_TILE ? TKN_TILE / a.units : 1u;
-    a.magic = a.units > 1u ? (uint32_t)((1ull << 32) / a.units) + 1u : 0u;
-    uint32_t gy = 1;
-    if (a.rb == 1u) {
-        gy = (a.units + TKN_TILE - 1) / TKN_TILE;
-        if (gy > 64u) gy = 64u;
-    }
-    grid = dim3(tky_blocks(a.n_docs, 1u << 20, a.rb), gy);
-    return true;
-}
-
 template <int I64, int MASK>
 static void tkn_launch2(const TkDenseArgs& a, dim3 grid, hipStream_t s) {
     if (a.row_len % 4u == 0u) hipLaunchKernelGGL((tk_dense_kernel<I64, MASK, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
@@ -173,8 +137,9 @@ static void tkn_launch2(const TkDenseArgs& a, dim3 grid, hipStream_t s) {
 
 hipError_t tk_launch_dense(const TkDenseArgs& args, int i64, hipStream_t s) {
     TkDenseArgs a = args;
-    dim3 grid;
-    if (!tkn_shape(a, grid)) return hipSuccess;
+    const TkyRowsGrid rg = tky_rows_shape(a.n_docs, a.row_len, false, a.rows);
+    if (rg.x == 0u) return hipSuccess;
+    const dim3 grid(rg.x, rg.y);
     if (i64 && a.mask) tkn_launch2<1, 1>(a, grid, s);
     else if (i64) tkn_launch2<1, 0>(a, grid, s);
     else if (a.mask) tkn_launch2<0, 1>(a, grid, s);
@@ -197,15 +162,9 @@ hipError_t tk_launch_ragged_rowlen(const TkRaggedArgs& a, int i64, hipStream_t s
 }
 
 hipError_t tk_launch_ragged_copy(const TkRaggedArgs& a, int i64, hipStream_t s) {
-    TkDenseArgs shape = {};
-    shape.n_docs = a.n_docs;
-    shape.row_len = a.row_len;
-    dim3 grid;
-    if (!tkn_shape(shape, grid)) return hipSuccess;
-    const bool vec = a.row_len % 4u == 0u;
-    if (i64 && vec) hipLaunchKernelGGL((tk_ragged_kernel<1, 1>), grid, dim3(TKY_BLOCK), 0, s, a, shape);
-    else if (i64) hipLaunchKernelGGL((tk_ragged_kernel<1, 0>), grid, dim3(TKY_BLOCK), 0, s, a, shape);
-    else if (vec) hipLaunchKernelGGL((tk_ragged_kernel<0, 1>), grid, dim3(TKY_BLOCK), 0, s, a, shape);
-    else hipLaunchKernelGGL((tk_ragged_kernel<0, 0>), grid, dim3(TKY_BLOCK), 0, s, a, shape);
+    TkyRows shape;
+    const TkyRowsGrid rg = tky_rows_shape(a.n_docs, a.row_len, false, shape);
+    if (rg.x == 0u) return hipSuccess;
+    TKY_LAUNCH_I64_VEC(tk_ragged_kernel, i64, a.row_len % 4u == 0u, dim3(rg.x, rg.y), s, a, shape);
     return hipGetLastError();
 }

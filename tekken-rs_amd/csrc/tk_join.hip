@@ -125,9 +125,8 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_join_kernel(TkJoinArgs a) {
             uint32_t v[4] = {0u, 0u, 0u, 0u}, lab[4] = {0u, 0u, 0u, 0u}, pi[4] = {0u, 0u, 0u, 0u};
             // the common unit: 4 positions of one part's text -- one load of 16 bytes, 4-byte aligned
             if (l + 4u <= len && (k == tile.count || tile.rel(k) >= l + 4u) && !(m.ctrl != TK_JOIN_NONE && pstart == (int64_t)l)) {
-                const tky_u32x4_a4 x = *reinterpret_cast<const tky_u32x4_a4*>(a.ids + (g - m.srcoff));
+                tky_gather4(a.ids + (g - m.srcoff), v);
                 const bool lt = (m.fl & TK_PART_LABEL_TEXT) != 0u;
-                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
 #pragma unroll
                 for (uint32_t q = 0; q < 4u; ++q) { lab[q] = lt ? v[q] : ign; pi[q] = m.pl; }
             } else {

@@ -7,6 +7,7 @@
 #include "../../include/tekken_hip.h"
 #include "tk_encode_impl_args.h"
 #include "tk_flat_args.h"
+#include "tk_rows.h"
 
 // mode 0: pass 1; mode 1: pass 2 (scratch-backed, every launched wave owns a scratch slice);
 // mode 2: split only; mode 3: pass 1 over args.todo_list.  n_waves = waves launched (rounded up to whole 4-wave blocks)
@@ -182,7 +183,7 @@ struct TkDenseArgs {
     uint8_t* mask;             // [n_docs * row_len] or NULL
     uint32_t* lengths;         // [n_docs] kept ids of every row
     unsigned long long* stat;  // [0] longest document (tk_launch_dense_maxlen), [1] += truncated documents (tk_launch_dense)
-    uint32_t units, rb, magic; // the launch shape (set by the launcher): units a row, rows a block, 2^32 / units rounded up
+    TkyRows rows;              // the launch shape (tk_rows.h; set by the launcher)
 };
 // row_len == 0 or n_docs == 0: nothing is launched (the caller zeroes lengths)
 hipError_t tk_launch_dense(const TkDenseArgs& a, int i64, hipStream_t s);
@@ -243,7 +244,7 @@ struct TkWindowArgs {
     uint32_t* window_doc;      // [W]
     uint32_t* window_start;    // [W]
     unsigned long long* stat;  // [0] longest document, clamped to 2^32 - 1 (atomicMax), [1] += documents with w_d > 1: zeroed by the caller
-    uint32_t units, rb, magic; // the launch shape (set by the launcher): units a row, rows a block, 2^32 / units rounded up
+    TkyRows rows;              // the launch shape (tk_rows.h; set by the launcher)
 };
 hipError_t tk_launch_window_counts(const TkWindowArgs& a, hipStream_t s);   // counts, stat
 hipError_t tk_launch_window(const TkWindowArgs& a, int i64, hipStream_t s); // the outputs; n_rows == 0: nothing is launched
@@ -277,7 +278,7 @@ struct TkPairArgs {
     // zeroed by the caller: [0] the longest row and [4] the longest part, clamped to 2^32 - 1 (atomicMax); [1] += pairs that lost
     // an id, [2] += pairs with w_p > 1, [3] += pairs whose fixed side was cut
     unsigned long long* stat;
-    uint32_t units, rb, magic; // the launch shape (set by the launcher): units a row, rows a block, 2^32 / units rounded up
+    TkyRows rows;              // the launch shape (tk_rows.h; set by the launcher)
 };
 hipError_t tk_launch_pair_counts(const TkPairArgs& a, hipStream_t s);     // counts, stat
 hipError_t tk_launch_pair(const TkPairArgs& a, int i64, hipStream_t s);   // the outputs; n_rows == 0: nothing is launched

@@ -1,13 +1,16 @@
-// tk_layout.h -- what the layout kernels share (tk_dense.hip, tk_seqpack.hip, tk_join.hip, tk_window.hip, tk_pair.hip, tk_rowfit.hip, tk_regroup.hip: ragged ids into what a model
-// consumes):
-// the 4-wide element access of an int32 / int64 tensor, the searches for "which document / part holds stream position g", the
-// staging of a tile's starts, the grid size and the one-atomic-a-wave tails.  (Names: tky_ -- tkl_ is tk_long_impl.h's.)
+// tk_layout.h -- what the layout kernels share (tk_dense.hip, tk_seqpack.hip, tk_join.hip, tk_window.hip, tk_pair.hip,
+// tk_rowfit.hip, tk_regroup.hip: ragged ids into what a model consumes):
+// the 4-wide element access of an int32 / int64 tensor and the 4-wide gather of ids and spans at any dword, the stores of a uint8
+// plane and of span pairs, the clamped length, the searches for "which document / part holds stream position g", the staging of a
+// tile's starts, the block's row group of the row-group launch shape (tk_rows.h) and the owner of a row, the grid size, the
+// I64 x VEC launch and the one-atomic-a-wave tails.  (Names: tky_ -- tkl_ is tk_long_impl.h's.)
 #ifndef TK_LAYOUT_H
 #define TK_LAYOUT_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "tk_dpp_scan.h"
+#include "tk_rows.h"
 
 #define TKY_BLOCK 256
 #define TKY_TILE 4096u     /* stream positions of a block's tile (16 a thread) */
@@ -21,6 +24,18 @@ static inline uint32_t tky_blocks(uint64_t n, uint64_t cap, uint64_t per = TKY_B
     const uint64_t b = (n + per - 1) / per;
     return (uint32_t)(b < cap ? b : cap);
 }
+
+// kernel<I64, VEC> by two run-time flags
+#define TKY_LAUNCH_I64_VEC(kernel, i64, vec, grid, s, ...)                                               \
+    do {                                                                                                 \
+        if ((i64) && (vec)) hipLaunchKernelGGL((kernel<1, 1>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); \
+        else if (i64) hipLaunchKernelGGL((kernel<1, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__);       \
+        else if (vec) hipLaunchKernelGGL((kernel<0, 1>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__);       \
+        else hipLaunchKernelGGL((kernel<0, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__);                \
+    } while (0)
+
+// a length as the kernels carry it: clamped to 2^32 - 1 (the host refuses a clamped one before anything derived from it is used)
+__device__ __forceinline__ uint32_t tky_len32(uint64_t n) { return n < 0xFFFFFFFFull ? (uint32_t)n : 0xFFFFFFFFu; }
 
 // v[0 .. W) <-> elements at .. at + W of an int32 (I64 = 0) or int64 tensor, W = VEC ? 4 : 1 (VEC: at is a multiple of 4 and the
 // tensor 16-byte aligned -- one 16-byte access for int32, two for int64)
@@ -54,6 +69,31 @@ __device__ __forceinline__ void tky_load(const void* base, uint64_t at, uint32_t
     } else {
         v[0] = I64 ? (uint32_t)reinterpret_cast<const uint64_t*>(base)[at] : reinterpret_cast<const uint32_t*>(base)[at];
     }
+}
+
+// ---- the 4-wide gather: four consecutive ids that lie at four consecutive source ids ----
+// v[0 .. 4) = src[0 .. 4), src at any dword: ONE unaligned 16-byte load
+__device__ __forceinline__ void tky_gather4(const uint32_t* src, uint32_t* v) {
+    const tky_u32x4 x = *reinterpret_cast<const tky_u32x4_a4*>(src);
+    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+}
+// sp[0 .. 8) = the (start, end) pairs of ids s0 .. s0 + 3: two such loads
+__device__ __forceinline__ void tky_gather4_spans(const uint32_t* spans, uint64_t s0, uint32_t* sp) {
+    tky_gather4(spans + 2u * s0, sp);
+    tky_gather4(spans + 2u * s0 + 4u, sp + 4);
+}
+// elements at .. at + W of a uint8 plane (mask, type_ids, sequence_ids) from the bytes of `bits`: one dword, or one byte
+template <int VEC>
+__device__ __forceinline__ void tky_store_plane(uint8_t* plane, uint64_t at, uint32_t bits) {
+    if (VEC) *reinterpret_cast<uint32_t*>(plane + at) = bits;
+    else plane[at] = (uint8_t)bits;
+}
+// the span pairs sp[0 .. 2 W) of elements at .. at + W of a [.., 2] tensor
+template <int VEC>
+__device__ __forceinline__ void tky_store_spans(uint32_t* out, uint64_t at, const uint32_t* sp) {
+    tky_store<0, VEC>(out, 2u * at, sp);
+    if (VEC) tky_store<0, 1>(out, 2u * at + 4u, sp + 4);
+    else out[2u * at + 1u] = sp[1];
 }
 
 // the wave's sum / maximum of v into *dst with one atomic (none where it is 0); every lane of the wave calls it
@@ -179,6 +219,44 @@ struct TkyTile {
     }
     // where the tile's entry k starts, relative to the tile
     __device__ __forceinline__ int64_t start_of(uint32_t k) const { return k ? (int64_t)rel(k - 1u) : -(int64_t)(g0 - start_lo); }
+};
+
+// ---- the block's part of the row-group launch shape (tk_rows.h) ----
+//   for (uint64_t b = blockIdx.x; b < tky_row_groups(shape, n_rows); b += gridDim.x) {
+//       const TkyRowGroup g(shape, n_rows, b);
+//       for (uint32_t li = g.first(); li < g.total; li += g.step()) {
+//           const uint32_t r = tky_row_of(shape, li), cg = li - r * shape.units;     // unit cg of row g.row0 + r
+struct TkyRowGroup {
+    uint64_t row0;                  // the group's first row
+    uint32_t nrows, total;          // its rows (rb, fewer in the last group) and units: rb > 1: <= TKY_ROWS_TILE; rb == 1: units < 2^31
+    __device__ __forceinline__ TkyRowGroup(const TkyRows& s, uint64_t n_rows, uint64_t b) : row0(b * s.rb) {
+        nrows = n_rows - row0 < s.rb ? (uint32_t)(n_rows - row0) : s.rb;
+        total = nrows * s.units;
+    }
+    __device__ __forceinline__ static uint32_t first() { return blockIdx.y * TKY_BLOCK + threadIdx.x; }
+    __device__ __forceinline__ static uint32_t step() { return TKY_BLOCK * gridDim.y; }
+};
+
+// Which owner (document, pair) holds each row of a row group: starts[0 .. n_owners] is the exclusive scan of the owners' row
+// counts, strictly increasing.  Two waves find, one 64-ary search each, the owners of the group's first and last row; the starts
+// of the owners in between go to LDS relative to the group's first row, and rec(j, e) puts what a unit needs of owner e beside
+// them at [j] (TkyTile::stage).  More than TKY_CAP owners in the run (rows of 4 elements over one-row owners): nothing is staged
+// and the caller reads the same values from global memory where !lds, decided per block.  Per unit, for row r of the group,
+// with the tile's own members:
+//   kd = count_le(r)              [kd] of what rec staged: a binary search over at most rb entries
+//   n_lo - 1 + kd                 the owner's index
+//   r - start_of(kd)              the row's number inside its owner
+// (written out by the kernels: behind accessors of this struct the compiler orders tk_window_kernel's and tk_pair_kernel's
+// instructions otherwise, and with one for the owner's index tk_window_kernel's per-block prologue grows by four instructions).
+// ONE a kernel (it is the kernel's TkyTile<2>).
+struct TkyRowOwners : TkyTile<2> {
+    template <class F>
+    __device__ __forceinline__ TkyRowOwners(const uint64_t* starts, uint64_t n_owners, const TkyRowGroup& g, F rec) : TkyTile<2>(starts, g.row0) {
+        search(n_owners, g.row0, g.row0 + g.nrows - 1u);    // owners that start at or before: the first row (>= 1) | the last row
+        const uint64_t lo = found(0);
+        open(lo, (uint32_t)(found(1) - lo));                // owners that start in (row0, row0 + nrows): < nrows
+        stage(rec);
+    }
 };
 
 #endif

@@ -19,21 +19,16 @@
 // Two steps on the caller's stream, one read by the host in between (W and the longest row size the tensors):
 //   1. tk_pair_counts_kernel: w_p per pair, the longest row and the longest part (wave maxima, one atomic a wave) and the three
 //      counters (tky_wave_add); tk_launch_scan over w_p gives pair_windows.
-//   2. tk_pair_kernel, the launch shape of tk_window_kernel over W rows: the unit is 4 consecutive elements of one row where
-//      L % 4 == 0 (one 16-byte store for int32, two for int64, one dword each of mask / type_ids / sequence_ids, two 16-byte
-//      stores of spans), one element otherwise; a block takes `rb` consecutive rows (rb * G units <= TKP_TILE, G units a row; a
-//      longer row is one block row split over blockIdx.y).  The pairs of the block's rows come from TkyTile over pair_windows,
-//      and beside their starts oo[2p], a and b go to LDS; more than TKY_CAP pairs in the run (rows of 4 elements over one-row
-//      pairs): the same values come from global memory, decided per block.  Every element of every selected output is written
-//      exactly once, pads included; no atomics.  The lane with a row's first unit writes lengths, window_pair, window_start and
-//      second_start.
+//   2. tk_pair_kernel, the row-group launch shape (tk_rows.h) over W rows; a unit of 4 elements stores one dword each of mask /
+//      type_ids / sequence_ids and two 16-byte halves of spans.  The pairs of the block's rows come from TkyRowOwners
+//      (tk_layout.h) over pair_windows, and beside their starts oo[2p], a and b go to LDS; where nothing is staged the same
+//      values come from global memory.  Every element of every selected output is written exactly once, pads included; no
+//      atomics.  The lane with a row's first unit writes lengths, window_pair, window_start and second_start.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "tk_kernels.h"
 #include "tk_layout.h"
-
-#define TKP_TILE 2048u     /* units of a block's row group (8 a thread); the reciprocal is exact for indices below it */
 
 struct TkpKept { uint32_t as, alen, bs, blen; };   // a row keeps A[as : as + alen] and B[bs : bs + blen]
 
@@ -77,8 +72,7 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_pair_counts_kernel(TkPairArgs p)
     uint32_t longest = 0, part = 0, n_trunc = 0, n_split = 0, n_cut = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * TKY_BLOCK + threadIdx.x; i < p.n_pairs; i += (uint64_t)gridDim.x * TKY_BLOCK) {
         const uint64_t o0 = p.id_offs[2u * i], o1 = p.id_offs[2u * i + 1u], o2 = p.id_offs[2u * i + 2u];
-        const uint32_t a = o1 - o0 < 0xFFFFFFFFull ? (uint32_t)(o1 - o0) : 0xFFFFFFFFu;   // (a clamped part is refused by the host
-        const uint32_t b = o2 - o1 < 0xFFFFFFFFull ? (uint32_t)(o2 - o1) : 0xFFFFFFFFu;   //  before anything below is used)
+        const uint32_t a = tky_len32(o1 - o0), b = tky_len32(o2 - o1);
         part = part > a ? part : a;
         part = part > b ? part : b;
         const TkpKept r = tkp_kept(p, a, b, 0u);
@@ -106,42 +100,30 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_pair_counts_kernel(TkPairArgs p)
     tky_wave_max(p.stat + 4, part);
 }
 
-// row of unit li inside the block's row group (li < TKP_TILE when rb > 1)
-__device__ __forceinline__ uint32_t tkp_row_of(const TkPairArgs& p, uint32_t li) {
-    if (p.rb == 1u) return 0u;
-    return p.units == 1u ? li : __umulhi(li, p.magic);
-}
-
 template <int I64, int VEC>
 __global__ __launch_bounds__(TKY_BLOCK) void tk_pair_kernel(TkPairArgs p) {
     constexpr uint32_t W = VEC ? 4u : 1u;
     __shared__ uint64_t s_oo[TKY_CAP + 1u];             // oo[2p] of the block's pairs, [0]: the one that holds its first row
     __shared__ uint32_t s_a[TKY_CAP + 1u];              // a and b of the same
     __shared__ uint32_t s_b[TKY_CAP + 1u];
-    const uint32_t G = p.units, L = p.row_len;
-    const uint64_t n_rb = (p.n_rows + p.rb - 1) / p.rb;
+    const uint32_t G = p.rows.units, L = p.row_len;
+    const uint64_t n_rb = tky_row_groups(p.rows, p.n_rows);
     for (uint64_t blk = blockIdx.x; blk < n_rb; blk += gridDim.x) {
-        const uint64_t row0 = blk * p.rb;
-        const uint32_t nrows = p.n_rows - row0 < p.rb ? (uint32_t)(p.n_rows - row0) : p.rb;
-        const uint32_t total = nrows * G;               // rb > 1: <= TKP_TILE; rb == 1: G < 2^31
-        TkyTile<2> tile(p.pair_windows, row0);
-        tile.search(p.n_pairs, row0, row0 + nrows - 1u);    // pairs that start at or before: the first row (>= 1) | the last row
-        const uint64_t n_lo = tile.found(0);
-        tile.open(n_lo, (uint32_t)(tile.found(1) - n_lo));  // pairs that start in (row0, row0 + nrows): < nrows
-        tile.stage([&](uint32_t j, uint64_t e) {
+        const TkyRowGroup g(p.rows, p.n_rows, blk);
+        const TkyRowOwners pairs(p.pair_windows, p.n_pairs, g, [&](uint32_t j, uint64_t e) {
             const uint64_t o = p.id_offs[2u * e], o1 = p.id_offs[2u * e + 1u];
             s_oo[j] = o;
             s_a[j] = (uint32_t)(o1 - o);
             s_b[j] = (uint32_t)(p.id_offs[2u * e + 2u] - o1);
         });
-        for (uint32_t li = blockIdx.y * TKY_BLOCK + threadIdx.x; li < total; li += TKY_BLOCK * gridDim.y) {
-            const uint32_t r = tkp_row_of(p, li), cg = li - r * G;
-            const uint32_t kd = tile.count_le(r);       // the block's pair that holds row r
-            const uint64_t pr = n_lo - 1u + kd;
-            const uint32_t kw = (uint32_t)((int64_t)r - tile.start_of(kd));   // the row's number inside its pair
+        for (uint32_t li = g.first(); li < g.total; li += g.step()) {
+            const uint32_t r = tky_row_of(p.rows, li), cg = li - r * G;
+            const uint32_t kd = pairs.count_le(r);      // the block's pair that holds row r
+            const uint64_t pr = pairs.n_lo - 1u + kd;
+            const uint32_t kw = (uint32_t)((int64_t)r - pairs.start_of(kd));  // the row's number inside its pair
             uint64_t o0;
             uint32_t a, b;
-            if (tile.lds) {
+            if (pairs.lds) {
                 o0 = s_oo[kd]; a = s_a[kd]; b = s_b[kd];
             } else {
                 o0 = p.id_offs[2u * pr];
@@ -153,7 +135,7 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_pair_kernel(TkPairArgs p) {
             const uint32_t e0 = p.n_head, e1 = e0 + k.alen, e2 = e1 + p.n_sep, e3 = e2 + k.blen, e4 = e3 + p.n_tail;
             const uint64_t oa = o0 + k.as - e0;         // ids[oa + j]: element j of the A run (wraps where as < e0: only sums are used)
             const uint64_t ob = o0 + a + k.bs - e2;     // ids[ob + j]: element j of the B run
-            const uint64_t row = row0 + r;
+            const uint64_t row = g.row0 + r;
             if (cg == 0u) {
                 p.lengths[row] = e4;
                 p.window_pair[row] = (uint32_t)pr;
@@ -168,17 +150,11 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_pair_kernel(TkPairArgs p) {
             const bool in_a = VEC && j0 >= e0 && j0 + 4u <= e1, in_b = VEC && j0 >= e2 && j0 + 4u <= e3;
             if (VEC && (in_a || in_b)) {
                 const uint64_t s0 = (in_a ? oa : ob) + j0;
-                const tky_u32x4 x = *reinterpret_cast<const tky_u32x4_a4*>(p.ids + s0);
-                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+                tky_gather4(p.ids + s0, v);
                 mbits = 0x01010101u;
                 tbits = in_b ? 0x01010101u : 0u;
                 sbits = in_b ? 0x01010101u : 0u;
-                if (p.out_spans) {
-                    const tky_u32x4 p0 = *reinterpret_cast<const tky_u32x4_a4*>(p.in_spans + 2u * s0);
-                    const tky_u32x4 p1 = *reinterpret_cast<const tky_u32x4_a4*>(p.in_spans + 2u * s0 + 4u);
-                    sp[0] = p0.x; sp[1] = p0.y; sp[2] = p0.z; sp[3] = p0.w;
-                    sp[4] = p1.x; sp[5] = p1.y; sp[6] = p1.z; sp[7] = p1.w;
-                }
+                if (p.out_spans) tky_gather4_spans(p.in_spans, s0, sp);
             } else {
 #pragma unroll
                 for (uint32_t q = 0; q < W; ++q) {
@@ -199,23 +175,10 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_pair_kernel(TkPairArgs p) {
             }
             const uint64_t at = row * L + j0;
             tky_store<I64, VEC>(p.out, at, v);
-            if (p.mask) {
-                if (VEC) *reinterpret_cast<uint32_t*>(p.mask + at) = mbits;
-                else p.mask[at] = (uint8_t)mbits;
-            }
-            if (p.type_ids) {
-                if (VEC) *reinterpret_cast<uint32_t*>(p.type_ids + at) = tbits;
-                else p.type_ids[at] = (uint8_t)tbits;
-            }
-            if (p.seq_ids) {
-                if (VEC) *reinterpret_cast<uint32_t*>(p.seq_ids + at) = sbits;
-                else p.seq_ids[at] = (uint8_t)sbits;
-            }
-            if (p.out_spans) {
-                tky_store<0, VEC>(p.out_spans, 2u * at, sp);
-                if (VEC) tky_store<0, 1>(p.out_spans, 2u * at + 4u, sp + 4);
-                else p.out_spans[2u * at + 1u] = sp[1];
-            }
+            if (p.mask) tky_store_plane<VEC>(p.mask, at, mbits);
+            if (p.type_ids) tky_store_plane<VEC>(p.type_ids, at, tbits);
+            if (p.seq_ids) tky_store_plane<VEC>(p.seq_ids, at, sbits);
+            if (p.out_spans) tky_store_spans<VEC>(p.out_spans, at, sp);
         }
     }
 }
@@ -229,21 +192,9 @@ hipError_t tk_launch_pair_counts(const TkPairArgs& a, hipStream_t s) {
 }
 
 hipError_t tk_launch_pair(const TkPairArgs& args, int i64, hipStream_t s) {
-    if (args.n_rows == 0) return hipSuccess;
     TkPairArgs a = args;
-    const bool vec = a.row_len != 0u && a.row_len % 4u == 0u;
-    a.units = vec ? a.row_len / 4u : a.row_len ? a.row_len : 1u;   // (L == 0: one unit a row, which writes the per-row outputs)
-    a.rb = a.units <= TKP_TILE ? TKP_TILE / a.units : 1u;
-    a.magic = a.units > 1u ? (uint32_t)((1ull << 32) / a.units) + 1u : 0u;
-    uint32_t gy = 1;
-    if (a.rb == 1u) {
-        gy = (a.units + TKP_TILE - 1) / TKP_TILE;
-        if (gy > 64u) gy = 64u;
-    }
-    const dim3 grid(tky_blocks(a.n_rows, 1u << 20, a.rb), gy);
-    if (i64 && vec) hipLaunchKernelGGL((tk_pair_kernel<1, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else if (i64) hipLaunchKernelGGL((tk_pair_kernel<1, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else if (vec) hipLaunchKernelGGL((tk_pair_kernel<0, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((tk_pair_kernel<0, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
+    const TkyRowsGrid rg = tky_rows_shape(a.n_rows, a.row_len, true, a.rows);   // (L == 0: one unit a row, which writes the per-row outputs)
+    if (rg.x == 0u) return hipSuccess;
+    TKY_LAUNCH_I64_VEC(tk_pair_kernel, i64, a.row_len != 0u && a.row_len % 4u == 0u, dim3(rg.x, rg.y), s, a);
     return hipGetLastError();
 }

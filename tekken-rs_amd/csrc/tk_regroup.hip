@@ -193,12 +193,8 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_regroup_gather_kernel(TkRegroupA
             // the common unit: 4 positions of one document -- one load of 16 bytes, 4-byte aligned
             if (l + 4u <= len && (k == tile.count || tile.rel(k) >= l + 4u)) {
                 const uint64_t s = sb + (uint64_t)((int64_t)l - start);
-                const tky_u32x4_a4 x = *reinterpret_cast<const tky_u32x4_a4*>(a.ids + s);
-                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-                if (a.out_lab) {
-                    const tky_u32x4_a4 y = *reinterpret_cast<const tky_u32x4_a4*>(a.lab + s);
-                    lb[0] = y.x; lb[1] = y.y; lb[2] = y.z; lb[3] = y.w;
-                }
+                tky_gather4(a.ids + s, v);
+                if (a.out_lab) tky_gather4(reinterpret_cast<const uint32_t*>(a.lab + s), lb);
             } else {
 #pragma unroll
                 for (uint32_t q = 0; q < 4u; ++q) {

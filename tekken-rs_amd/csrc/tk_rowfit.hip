@@ -163,12 +163,8 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_rowfit_kernel(TkRowfitArgs a) {
             // the common unit: 4 elements of one document's head, or of its kept tail -- one load of 16 bytes, 4-byte aligned
             if (VEC && (k == tile.count || tile.rel(k) >= l + 4u) && k0 + 4u <= e && (n <= L || k0 + 4u <= head || k0 >= head)) {
                 const uint64_t src = n > L && k0 >= head ? m.o1 - (L - k0) : m.o0 + k0;
-                const tky_u32x4_a4 x = *reinterpret_cast<const tky_u32x4_a4*>(a.ids + src);
-                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-                if (a.out_lab) {
-                    const tky_u32x4_a4 y = *reinterpret_cast<const tky_u32x4_a4*>(a.lab + src);
-                    lb[0] = y.x; lb[1] = y.y; lb[2] = y.z; lb[3] = y.w;
-                }
+                tky_gather4(a.ids + src, v);
+                if (a.out_lab) tky_gather4(reinterpret_cast<const uint32_t*>(a.lab + src), lb);
 #pragma unroll
                 for (uint32_t q = 0; q < 4u; ++q) { p[q] = (uint32_t)k0 + q; sg[q] = m.sg; }
             } else {
@@ -253,11 +249,7 @@ hipError_t tk_launch_rowfit_place(const TkRowfitArgs& a, hipStream_t s) {
 hipError_t tk_launch_rowfit(const TkRowfitArgs& a, int i64, hipStream_t s) {
     if (a.n_rows == 0) return hipSuccess;
     const dim3 grid(tky_blocks(a.n_rows * a.row_len, 1u << 20, TKY_TILE));
-    const bool vec = a.row_len % 4u == 0u;
-    if (i64 && vec) hipLaunchKernelGGL((tk_rowfit_kernel<1, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else if (i64) hipLaunchKernelGGL((tk_rowfit_kernel<1, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else if (vec) hipLaunchKernelGGL((tk_rowfit_kernel<0, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((tk_rowfit_kernel<0, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
+    TKY_LAUNCH_I64_VEC(tk_rowfit_kernel, i64, a.row_len % 4u == 0u, grid, s, a);
     return hipGetLastError();
 }
 

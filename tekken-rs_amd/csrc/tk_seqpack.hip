@@ -160,11 +160,7 @@ hipError_t tk_launch_seqpack(const TkSeqpackArgs& args, int i64, hipStream_t s) 
     TkSeqpackArgs a = args;
     a.ids_al16 = ((uintptr_t)a.ids & 15u) == 0u;
     const dim3 grid(tky_blocks(a.n_rows * a.row_len, 1u << 20, TKY_TILE));
-    const bool vec = a.row_len % 4u == 0u;
-    if (i64 && vec) hipLaunchKernelGGL((tk_seqpack_kernel<1, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else if (i64) hipLaunchKernelGGL((tk_seqpack_kernel<1, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else if (vec) hipLaunchKernelGGL((tk_seqpack_kernel<0, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((tk_seqpack_kernel<0, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
+    TKY_LAUNCH_I64_VEC(tk_seqpack_kernel, i64, a.row_len % 4u == 0u, grid, s, a);
     return hipGetLastError();
 }
 

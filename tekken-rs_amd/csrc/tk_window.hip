@@ -19,29 +19,22 @@
 // Two steps on the caller's stream, one read by the host in between (W sizes the tensor):
 //   1. tk_window_counts_kernel: w_d per document, the longest document (a wave maximum, one atomic a wave) and the number of
 //      split documents (tky_wave_add); tk_launch_scan over w_d gives doc_windows.
-//   2. tk_window_kernel, the launch shape of tk_dense_kernel over W rows: the unit is 4 consecutive elements of one row where
-//      L % 4 == 0 (one 16-byte store for int32, two for int64, one dword of mask, two 16-byte stores of spans), one element
-//      otherwise; a block takes `rb` consecutive rows (rb * G units <= TKW_TILE, G units a row; a longer row is one block row
-//      split over blockIdx.y), the row of a unit comes from a per-launch reciprocal.  Two waves of the block find, one 64-ary
-//      search over doc_windows each, the documents of its first and last row; the window starts of the documents in between go to
-//      LDS relative to the block's first row (TkyTile), and beside them oo[d] and n_d; a unit finds its document there with a
-//      binary search over at most rb entries.  More than TKY_CAP documents in the run (rows of 4 elements over one-window
-//      documents): the same values come from global memory, decided per block.  Every element of every selected output is written
-//      exactly once, pads included.  The lane with a row's first unit writes lengths, window_doc and window_start.
+//   2. tk_window_kernel, the row-group launch shape (tk_rows.h) over W rows; a unit of 4 elements also stores two 16-byte
+//      halves of spans.  The documents of the block's rows come from TkyRowOwners (tk_layout.h) over doc_windows, and beside
+//      their window starts oo[d] and n_d go to LDS; where nothing is staged the same values come from global memory.  Every
+//      element of every selected output is written exactly once, pads included.  The lane with a row's first unit writes
+//      lengths, window_doc and window_start.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "tk_kernels.h"
 #include "tk_layout.h"
 
-#define TKW_TILE 2048u     /* units of a block's row group (8 a thread); the reciprocal is exact for indices below it */
-
 __global__ __launch_bounds__(TKY_BLOCK) void tk_window_counts_kernel(TkWindowArgs a) {
     const uint32_t T = a.max_len;
     uint32_t longest = 0, n_split = 0;
     for (uint64_t d = (uint64_t)blockIdx.x * TKY_BLOCK + threadIdx.x; d < a.n_docs; d += (uint64_t)gridDim.x * TKY_BLOCK) {
-        const uint64_t n = a.id_offs[d + 1] - a.id_offs[d];
-        const uint32_t n32 = n < 0xFFFFFFFFull ? (uint32_t)n : 0xFFFFFFFFu;
+        const uint32_t n32 = tky_len32(a.id_offs[d + 1] - a.id_offs[d]);
         longest = longest > n32 ? longest : n32;
         uint32_t w = 1;
         if (n32 > T) {                                  // (a clamped n32 is refused by the host before w is used)
@@ -54,41 +47,29 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_window_counts_kernel(TkWindowArg
     tky_wave_add(a.stat + 1, n_split);
 }
 
-// row of unit li inside the block's row group (li < TKW_TILE when rb > 1)
-__device__ __forceinline__ uint32_t tkw_row_of(const TkWindowArgs& a, uint32_t li) {
-    if (a.rb == 1u) return 0u;
-    return a.units == 1u ? li : __umulhi(li, a.magic);
-}
-
 template <int I64, int MASK, int VEC>
 __global__ __launch_bounds__(TKY_BLOCK) void tk_window_kernel(TkWindowArgs a) {
     constexpr uint32_t W = VEC ? 4u : 1u;
     __shared__ uint64_t s_oo[TKY_CAP + 1u];             // oo[d] of the block's documents, [0]: the one that holds its first row
     __shared__ uint32_t s_n[TKY_CAP + 1u];              // n_d of the same
-    const uint32_t G = a.units, L = a.row_len, T = a.max_len, h = a.keep_head, t = a.keep_tail;
+    const uint32_t G = a.rows.units, L = a.row_len, T = a.max_len, h = a.keep_head, t = a.keep_tail;
     const uint32_t cap = T - h - t;
-    const uint64_t n_rb = (a.n_rows + a.rb - 1) / a.rb;
+    const uint64_t n_rb = tky_row_groups(a.rows, a.n_rows);
     for (uint64_t b = blockIdx.x; b < n_rb; b += gridDim.x) {
-        const uint64_t row0 = b * a.rb;
-        const uint32_t nrows = a.n_rows - row0 < a.rb ? (uint32_t)(a.n_rows - row0) : a.rb;
-        const uint32_t total = nrows * G;               // rb > 1: <= TKW_TILE; rb == 1: G < 2^31
-        TkyTile<2> tile(a.doc_windows, row0);
-        tile.search(a.n_docs, row0, row0 + nrows - 1u); // documents that start at or before: the first row (>= 1) | the last row
-        const uint64_t n_lo = tile.found(0);
-        tile.open(n_lo, (uint32_t)(tile.found(1) - n_lo));   // documents that start in (row0, row0 + nrows): < nrows
-        tile.stage([&](uint32_t j, uint64_t e) {
+        const TkyRowGroup g(a.rows, a.n_rows, b);
+        const TkyRowOwners docs(a.doc_windows, a.n_docs, g, [&](uint32_t j, uint64_t e) {
             const uint64_t o = a.id_offs[e];
             s_oo[j] = o;
             s_n[j] = (uint32_t)(a.id_offs[e + 1u] - o);
         });
-        for (uint32_t li = blockIdx.y * TKY_BLOCK + threadIdx.x; li < total; li += TKY_BLOCK * gridDim.y) {
-            const uint32_t r = tkw_row_of(a, li), cg = li - r * G;
-            const uint32_t kd = tile.count_le(r);       // the block's document that holds row r
-            const uint64_t d = n_lo - 1u + kd;
-            const uint32_t kw = (uint32_t)((int64_t)r - tile.start_of(kd));   // the window's number inside its document
+        for (uint32_t li = g.first(); li < g.total; li += g.step()) {
+            const uint32_t r = tky_row_of(a.rows, li), cg = li - r * G;
+            const uint32_t kd = docs.count_le(r);       // the block's document that holds row r
+            const uint64_t d = docs.n_lo - 1u + kd;
+            const uint32_t kw = (uint32_t)((int64_t)r - docs.start_of(kd));   // the window's number inside its document
             uint64_t o0;
             uint32_t n;
-            if (tile.lds) {
+            if (docs.lds) {
                 o0 = s_oo[kd]; n = s_n[kd];
             } else {
                 o0 = a.id_offs[d]; n = (uint32_t)(a.id_offs[d + 1u] - o0);
@@ -102,7 +83,7 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_window_kernel(TkWindowArgs a) {
                 blen = body - bs < cap ? body - bs : cap;
             }
             const uint32_t hb = hh + blen, len = hb + tt;
-            const uint64_t row = row0 + r;
+            const uint64_t row = g.row0 + r;
             if (cg == 0u) {
                 const uint64_t ws = (uint64_t)h + (uint64_t)kw * a.step;
                 a.lengths[row] = len;
@@ -124,15 +105,9 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_window_kernel(TkWindowArgs a) {
                 run4 = src(j0 + 3u) == s0 + 3u;
             }
             if (VEC && run4) {
-                const tky_u32x4 x = *reinterpret_cast<const tky_u32x4_a4*>(a.ids + s0);
-                v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+                tky_gather4(a.ids + s0, v);
                 mbits = 0x01010101u;
-                if (a.out_spans) {
-                    const tky_u32x4 p0 = *reinterpret_cast<const tky_u32x4_a4*>(a.in_spans + 2u * s0);
-                    const tky_u32x4 p1 = *reinterpret_cast<const tky_u32x4_a4*>(a.in_spans + 2u * s0 + 4u);
-                    sp[0] = p0.x; sp[1] = p0.y; sp[2] = p0.z; sp[3] = p0.w;
-                    sp[4] = p1.x; sp[5] = p1.y; sp[6] = p1.z; sp[7] = p1.w;
-                }
+                if (a.out_spans) tky_gather4_spans(a.in_spans, s0, sp);
             } else {
 #pragma unroll
                 for (uint32_t q = 0; q < W; ++q) {
@@ -149,15 +124,8 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_window_kernel(TkWindowArgs a) {
             }
             const uint64_t at = row * L + j0;
             tky_store<I64, VEC>(a.out, at, v);
-            if (MASK) {
-                if (VEC) *reinterpret_cast<uint32_t*>(a.mask + at) = mbits;
-                else a.mask[at] = (uint8_t)mbits;
-            }
-            if (a.out_spans) {
-                tky_store<0, VEC>(a.out_spans, 2u * at, sp);
-                if (VEC) tky_store<0, 1>(a.out_spans, 2u * at + 4u, sp + 4);
-                else a.out_spans[2u * at + 1u] = sp[1];
-            }
+            if (MASK) tky_store_plane<VEC>(a.mask, at, mbits);
+            if (a.out_spans) tky_store_spans<VEC>(a.out_spans, at, sp);
         }
     }
 }
@@ -175,18 +143,11 @@ static void tkw_launch2(const TkWindowArgs& a, bool vec, dim3 grid, hipStream_t 
 }
 
 hipError_t tk_launch_window(const TkWindowArgs& args, int i64, hipStream_t s) {
-    if (args.n_rows == 0) return hipSuccess;
     TkWindowArgs a = args;
+    const TkyRowsGrid rg = tky_rows_shape(a.n_rows, a.row_len, true, a.rows);   // (L == 0: one unit a row, which writes the per-row outputs)
+    if (rg.x == 0u) return hipSuccess;
     const bool vec = a.row_len != 0u && a.row_len % 4u == 0u;
-    a.units = vec ? a.row_len / 4u : a.row_len ? a.row_len : 1u;   // (L == 0: one unit a row, which writes the per-row outputs)
-    a.rb = a.units <= TKW_TILE ? TKW_TILE / a.units : 1u;
-    a.magic = a.units > 1u ? (uint32_t)((1ull << 32) / a.units) + 1u : 0u;
-    uint32_t gy = 1;
-    if (a.rb == 1u) {
-        gy = (a.units + TKW_TILE - 1) / TKW_TILE;
-        if (gy > 64u) gy = 64u;
-    }
-    const dim3 grid(tky_blocks(a.n_rows, 1u << 20, a.rb), gy);
+    const dim3 grid(rg.x, rg.y);
     if (i64 && a.mask) tkw_launch2<1, 1>(a, vec, grid, s);
     else if (i64) tkw_launch2<1, 0>(a, vec, grid, s);
     else if (a.mask) tkw_launch2<0, 1>(a, vec, grid, s);

@@ -210,6 +210,27 @@ def test_spans_output_on_made_up_spans(tk, eng_bench, shape):
         assert_same(got, exp, (shape, m, flags))
 
 
+def test_row_longer_than_a_block_tile(tk, eng_bench):
+    """T = 9 001: the units of one row are split over blockIdx.y, element by element (L = 9 001) and in units of 4 (L = 9 004)."""
+    rng = np.random.default_rng(53)
+    T, s = 9001, 100
+    n = [3000, 20000, 0, 5, 9000, 9001, 10, 9002, 20000, 120, 4500, 8998, 1, 1]
+    oo = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    ids = rng.integers(0, 2**31 - 1, int(oo[-1])).astype(np.uint32)
+    g = np.arange(len(ids), dtype=np.uint64)
+    sp = np.stack([(g * 2 + 1) & 0xFFFFFFFF, (g * 3 + 7) & 0xFFFFFFFF], axis=1).astype(np.uint32)   # index-derived: a wrong source index shows
+    d_ids, d_oo = on_device(ids, oo)
+    d_sp = dev(sp.reshape(-1), np.uint32)
+    for m in (0, 4):
+        for h, t in ((2, 3), (3, 2)):
+            flags = FIXED | MASK | SPANS
+            exp = expected_windows(ids, oo, T, s, h, t, m, P_MADE_UP, flags, sp)
+            assert exp["row_len"] == T + 3 * (m == 4) and exp["lengths"].max() == T and exp["n_split"] > 0
+            for fl in (flags, flags | I64):
+                _, got = windows_of(eng_bench, d_ids, d_oo, len(ids), T, s, h, t, m, P_MADE_UP, fl, d_sp)
+                assert_same({**got, "input_ids": got["input_ids"].astype(np.int32)}, exp, (m, h, t, fl))
+
+
 # ---- the fused and host entries ----
 
 @pytest.mark.parametrize("vname", ["test", "bench"])
