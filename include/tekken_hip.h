@@ -567,6 +567,85 @@ void tk_free_rowfit(tk_rowfit* out);
  * the pass launched nothing (n_ids == 0) or was refused.  A NULL pointer is skipped. */
 void tk_last_rowfit_ms(const tk_ctx* ctx, float* placement_ms, float* fill_ms, float* cu_ms);
 
+/* ---- special-token strings parsed out of text on the device (tiktoken's allowed_special / disallowed_special; no reference
+ * equivalent: the reference calls CoreBPE::encode with an empty allowed set, src/tekkenizer.rs:384-386, and so does every encode
+ * entry above) ----
+ * A chat template renders a conversation to one string ("<s>[INST] ... [/INST] ...</s>"), a pre-training shard carries "</s>"
+ * between documents: this pass finds the occurrences of special-token strings in the packed text of D documents, takes them out and
+ * returns what tk_encode_parts_device_join needs.  Inputs: bytes / doc_offsets[D + 1] as encode takes them; the context's special
+ * strings S_0 .. S_{n-1} (tk_ctx_set_special_tokens; n = num_special_tokens): S_i is the string of id i, the one decode prints
+ * for id i under TK_POLICY_KEEP; modes, uint8[n] or NULL, with modes[i] one of TK_SPECIAL_TEXT (never matched: the string stays text,
+ * which is what every other entry does), TK_SPECIAL_PARSE, TK_SPECIAL_RAISE.  NULL means PARSE for every string.
+ *   1. Match set.  A = { i : modes[i] != TEXT }.  TK_ERR_INVALID_ARG before any work: a string of A that is empty or longer than
+ *      255 bytes; no strings set on the context; n_modes != num_special_tokens (with modes != NULL); an unknown mode value.  Where
+ *      two strings of A are equal bytes, the lower id stands for both.
+ *   2. Matches, per document, alone.  p = 0; while p < len: among the i in A with doc[p : p + |S_i|] == S_i (wholly inside the
+ *      document) the longest wins: emit (p, |S_i|, i) and continue at p + |S_i|; none: continue at p + 1.  Leftmost-longest,
+ *      non-overlapping, on bytes; a match never crosses a document boundary.  It is tiktoken's and HF's result whenever no string
+ *      of A is a prefix of another, which holds for every Tekken vocabulary.  On valid UTF-8 a match begins and ends on a
+ *      character boundary.
+ *   3. Raise.  An emitted match whose id has mode RAISE fails the call as a whole with TK_ERR_SPECIAL_POLICY; nothing of an
+ *      earlier result is touched.  *bad (optional) receives the first such document; the message names the document, the
+ *      document-relative byte position and the id.
+ *   4. Parts.  Document d with matches (s_1, l_1, i_1) .. (s_m, l_m, i_m): part 0 has part_ctrl = the context's BOS id with
+ *      TK_SPECIALS_BOS, else TK_JOIN_NONE, and the text doc[0 : s_1) (the whole document if m == 0); part j (1 <= j <= m) has
+ *      part_ctrl = i_j and the text doc[s_j + l_j : s_{j+1}), s_{m+1} = len; with TK_SPECIALS_EOS one more part, the EOS id and
+ *      empty text.  conv_offsets (uint64, D + 1) = the exclusive prefix sum of the parts per document; n_parts = P =
+ *      conv_offsets[D].  part_offsets (uint64, P + 1) and bytes: the parts' texts concatenated in order, which is the input with
+ *      exactly the matched strings removed.  n_matches = sum m, n_removed = sum l, n_bytes = the input's n_bytes - n_removed.
+ *      part_src (uint64, P, only with TK_SPECIALS_PART_SRC, else NULL): the offset in the INPUT buffer at which part p's text
+ *      begins, so a byte span inside part p maps back to the caller's document by one addition.
+ *   5. The encoding it defines.  J_d = the join of document d's parts (steps 1-2 of the join above) = [bos] + enc(seg_0) + [i_1] +
+ *      enc(seg_1) + .. + [i_m] + enc(seg_m) + [eos].  With every mode TEXT, or on text that holds no string of A, J_d is bit for
+ *      bit what tk_encode_batch returns for the same add_bos / add_eos.
+ *   6. Valid and empty: D == 0; empty documents (one part, empty text); a document that is one special string and nothing else;
+ *      n_bytes == 0; A empty (no device work beyond the part tables).  When n_removed == 0, out->bytes may be the caller's own
+ *      d_bytes (no copy): it is then valid as long as the caller keeps that buffer.
+ *   7. TK_ERR_INVALID_ARG beside step 1: an unknown flag (opts or checks), a NULL required argument, D >= 2^32 - 16, 2^32 - 16
+ *      candidates or more.  checks: TK_CHECK_OFFSETS / TK_CHECK_UTF8 as in tk_encode_batch_device_ex, on the INPUT, before the
+ *      split.  Without TK_CHECK_OFFSETS malformed offsets give parts that mean nothing but are never out-of-bounds indexing in
+ *      this pass.  A failed allocation is TK_ERR_RUNTIME.
+ *   8. out's buffers are device buffers owned by the context, valid until the next specials call on it, and SEPARATE from every
+ *      other pass's; an earlier result stays readable when a call is refused.
+ * A separate pass in front of the unchanged encode pipeline (csrc/tk_specials.hip).  Candidates: every text byte is
+ * read once; a byte outside the 256-bit first-byte mask of A costs one test, any other a walk of a byte trie over the strings that
+ * is bounded by the longest string, not by their number.  The matches are the candidates reachable from the first one under
+ * nxt(c) = the first candidate at or behind c's end -- one chain over the whole batch, marked by the pointer doubling that the
+ * rowfit and regroup passes have.  The part tables need one search per document and no scan; the text is compacted in 16-byte
+ * stores.  Two host reads (the number of candidates; n_matches, n_removed and the RAISE word) and one more wait; without a
+ * candidate the pass ends behind the first read with the part tables alone. */
+#define TK_SPECIAL_TEXT 0
+#define TK_SPECIAL_PARSE 1
+#define TK_SPECIAL_RAISE 2
+#define TK_SPECIALS_BOS 1
+#define TK_SPECIALS_EOS 2
+#define TK_SPECIALS_PART_SRC 4
+typedef struct tk_specials_opts { const uint8_t* modes; uint32_t n_modes; uint32_t flags; } tk_specials_opts;
+typedef struct tk_specials { uint8_t* bytes; uint64_t* part_offsets; uint32_t* part_ctrl; uint64_t* conv_offsets; uint64_t* part_src;
+                             uint64_t n_docs, n_parts, n_bytes, n_matches, n_removed; } tk_specials;
+/* Text on the device -> the parts.  opts->modes is a HOST pointer, copied per call.  The work is enqueued on hip_stream and the
+ * call returns after the stream has drained. */
+int tk_specials_split_device(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, int checks,
+                             const tk_specials_opts* opts, void* hip_stream, tk_specials* out, uint64_t* bad);
+/* The split + tk_encode_parts_device_join over its parts on the same stream: *out is J (step 5), *parts the split's result.
+ * Everything that can be refused (opts, jopts, the checks, RAISE) is refused before anything is encoded.  jopts' labels and part_index
+ * work as in the join; part_flags is NULL: a caller who wants labels per part calls the two halves. */
+int tk_encode_batch_device_parsed(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                  int checks, const tk_specials_opts* opts, const tk_join_opts* jopts, void* hip_stream,
+                                  tk_specials* parts, tk_join* out, uint64_t* bad);
+/* Host in / host out.  out's (and, where parts is not NULL, parts') buffers are pinned host memory, released with tk_free_join /
+ * tk_free_specials (an unselected output is NULL). */
+int tk_encode_batch_parsed(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int validate_utf8,
+                           const tk_specials_opts* opts, const tk_join_opts* jopts, tk_specials* parts, tk_join* out, uint64_t* bad);
+void tk_free_specials(tk_specials* out);
+/* As tk_last_regroup_ms, for tools/specials_time.py: GPU time of the stages of the context's last specials pass, from events on
+ * its stream: ms[0] the candidates (both launches and the scan; the host read between them is not counted), ms[1] the chain
+ * (nxt, the doubling rounds, the marks and their scan), ms[2] the part tables, ms[3] the text compaction.  All 0 where the pass
+ * was refused; a stage that launched nothing is 0 or the cost of two event records. */
+void tk_last_specials_ms(const tk_ctx* ctx, float ms[4]);
+/* The text bytes of a tile of the candidate kernel (tests place matches across its boundaries). */
+uint32_t tk_specials_tile(void);
+
 /* ---- encoded documents selected, reordered and cut into batches on the device (no reference equivalent) ----
  * What a data pipeline does between "encode" and "batch": drop documents, put the rest into another order (shuffled, by length, by
  * length within shuffled groups), cut that order into batches under a padded-token budget.  Ragged in, ragged out: the result's
@@ -897,6 +976,10 @@ int tk_tokenizer_encode(tk_tokenizer* t, const char* text, size_t len, int add_b
 int tk_tokenizer_encode_batch(tk_tokenizer* t, const uint8_t* bytes, const uint64_t* doc_offsets,
                               uint64_t n_docs, int add_bos, int add_eos, tk_result* out);
 void tk_free_ids(uint32_t* ids);
+/* tk_encode_batch_parsed for one document (the specials pass above, through the same kernels): modes as tk_specials_opts.modes
+ * (NULL: every special string is parsed), n_modes = num_special_tokens; *ids is malloc'ed, free with tk_free_ids. */
+int tk_tokenizer_encode_parsed(tk_tokenizer* t, const char* text, size_t len, int add_bos, int add_eos, const uint8_t* modes,
+                               uint32_t n_modes, uint32_t** ids, size_t* n_ids);
 /* Tekkenizer::encode + the byte span of every id (see tk_token_spans_device for the definition); *ids and *spans (2 * n_ids
  * entries) are malloc'ed, free both with tk_free_ids.  The spans are computed on the host from the ids and the rank table (no
  * second launch); they equal what the spans kernel gives for the same ids. */

@@ -280,6 +280,32 @@ pub struct TkWords {
     pub n_ids: u64,
     pub n_words: u64,
 }
+// special-token strings parsed out of text (tk_specials_opts.modes / .flags; include/tekken_hip.h has the definition)
+pub const TK_SPECIAL_TEXT: u8 = 0;
+pub const TK_SPECIAL_PARSE: u8 = 1;
+pub const TK_SPECIAL_RAISE: u8 = 2;
+pub const TK_SPECIALS_BOS: u32 = 1;
+pub const TK_SPECIALS_EOS: u32 = 2;
+pub const TK_SPECIALS_PART_SRC: u32 = 4;
+#[repr(C)]
+pub struct TkSpecialsOpts {
+    pub modes: *const u8,
+    pub n_modes: u32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkSpecials {
+    pub bytes: *mut u8,
+    pub part_offsets: *mut u64,
+    pub part_ctrl: *mut u32,
+    pub conv_offsets: *mut u64,
+    pub part_src: *mut u64,
+    pub n_docs: u64,
+    pub n_parts: u64,
+    pub n_bytes: u64,
+    pub n_matches: u64,
+    pub n_removed: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -403,6 +429,20 @@ extern "C" {
                                    validate_utf8: c_int, opts: *const TkRegroupOpts, out: *mut TkRegroup) -> c_int;
     pub fn tk_free_regroup(out: *mut TkRegroup);
     pub fn tk_last_regroup_ms(ctx: *const TkCtx, ms: *mut f32);
+    pub fn tk_specials_split_device(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                    checks: c_int, opts: *const TkSpecialsOpts, hip_stream: *mut c_void, out: *mut TkSpecials,
+                                    bad: *mut u64) -> c_int;
+    pub fn tk_encode_batch_device_parsed(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                         checks: c_int, opts: *const TkSpecialsOpts, jopts: *const TkJoinOpts, hip_stream: *mut c_void,
+                                         parts: *mut TkSpecials, out: *mut TkJoin, bad: *mut u64) -> c_int;
+    pub fn tk_encode_batch_parsed(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, validate_utf8: c_int,
+                                  opts: *const TkSpecialsOpts, jopts: *const TkJoinOpts, parts: *mut TkSpecials, out: *mut TkJoin,
+                                  bad: *mut u64) -> c_int;
+    pub fn tk_free_specials(out: *mut TkSpecials);
+    pub fn tk_last_specials_ms(ctx: *const TkCtx, ms: *mut f32);
+    pub fn tk_specials_tile() -> u32;
+    pub fn tk_tokenizer_encode_parsed(t: *mut TkTokenizer, text: *const c_char, len: usize, add_bos: c_int, add_eos: c_int, modes: *const u8,
+                                      n_modes: u32, ids: *mut *mut u32, n_ids: *mut usize) -> c_int;
     pub fn tk_words_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
                                     d_bytes: *const c_void, d_doc_offsets: *const c_void, n_bytes: u64, checks: c_int,
                                     opts: *const TkWordsOpts, hip_stream: *mut c_void, out: *mut TkWords, bad: *mut u64) -> c_int;

@@ -48,6 +48,8 @@ REGROUP_DESC, REGROUP_LABELS, REGROUP_PERM, REGROUP_BATCHES, REGROUP_BATCH_OFFSE
 WORD_NONE = 0xFFFFFFFF   # word_ids: a special id (HF's None)
 WORDS_FIRST = 1   # tk_words_opts.flags (the words entries)
 WORDS_CHECK_ALIGNED = 32   # the words entries' check (beside CHECK_OFFSETS / CHECK_UTF8 in one word)
+SPECIAL_TEXT, SPECIAL_PARSE, SPECIAL_RAISE = 0, 1, 2   # tk_specials_opts.modes: what a special-token string found in text becomes
+SPECIALS_BOS, SPECIALS_EOS, SPECIALS_PART_SRC = 1, 2, 4   # tk_specials_opts.flags (the specials entries)
 _ORDERS = {"keep": REGROUP_ORDER_KEEP, "length": REGROUP_ORDER_LENGTH, "shuffle": REGROUP_ORDER_SHUFFLE, "grouped": REGROUP_ORDER_GROUPED}   # the order keyword of encode_batch_regrouped
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
@@ -168,6 +170,16 @@ class _Regroup(ctypes.Structure):
                 ("batch_offsets", ctypes.c_void_p), ("batch_rowlen", ctypes.c_void_p), ("n_docs", ctypes.c_uint64), ("n_ids", ctypes.c_uint64),
                 ("n_masked", ctypes.c_uint64), ("n_short", ctypes.c_uint64), ("n_long", ctypes.c_uint64), ("n_batches", ctypes.c_uint64),
                 ("n_oversize", ctypes.c_uint64), ("n_batch_pad", ctypes.c_uint64)]
+
+
+class _SpecialsOpts(ctypes.Structure):
+    _fields_ = [("modes", ctypes.POINTER(ctypes.c_uint8)), ("n_modes", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class _Specials(ctypes.Structure):
+    _fields_ = [("bytes", ctypes.c_void_p), ("part_offsets", ctypes.c_void_p), ("part_ctrl", ctypes.c_void_p), ("conv_offsets", ctypes.c_void_p),
+                ("part_src", ctypes.c_void_p), ("n_docs", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64),
+                ("n_matches", ctypes.c_uint64), ("n_removed", ctypes.c_uint64)]
 
 
 class _WordsOpts(ctypes.Structure):
@@ -426,6 +438,23 @@ def lib():
         L.tk_free_words.argtypes = [wp]
         L.tk_last_words_ms.restype = None
         L.tk_last_words_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 4)]
+    if hasattr(L, "tk_specials_split_device"):   # (special strings parsed out of text: libraries built before it still load through TK_HIP_LIB)
+        sop, sp = ctypes.POINTER(_SpecialsOpts), ctypes.POINTER(_Specials)
+        L.tk_specials_split_device.restype = ci
+        L.tk_specials_split_device.argtypes = [vp, vp, vp, u64, u64, ci, sop, vp, sp, u64p]
+        L.tk_encode_batch_device_parsed.restype = ci
+        L.tk_encode_batch_device_parsed.argtypes = [vp, vp, vp, u64, u64, ci, sop, jop, vp, sp, jp, u64p]
+        L.tk_encode_batch_parsed.restype = ci
+        L.tk_encode_batch_parsed.argtypes = [vp, u8p, u64p, u64, ci, sop, jop, sp, jp, u64p]
+        L.tk_free_specials.restype = None
+        L.tk_free_specials.argtypes = [sp]
+        L.tk_last_specials_ms.restype = None
+        L.tk_last_specials_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 4)]
+        L.tk_specials_tile.restype = ctypes.c_uint32
+        L.tk_specials_tile.argtypes = []
+        L.tk_tokenizer_encode_parsed.restype = ci
+        L.tk_tokenizer_encode_parsed.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ci, ci, u8p, ctypes.c_uint32, ctypes.POINTER(u32p),
+                                                 ctypes.POINTER(ctypes.c_size_t)]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -713,6 +742,31 @@ class WordsResult(_LayoutResult):
                ("word_first", "<i4", lambda r: (r.n_words,), np.uint32, True))
     COUNTS = ("n_docs", "n_ids", "n_words")
     DICT_COUNTS = ("n_words",)
+
+
+def _specials_opts(modes, flags):
+    """(tk_specials_opts, the array it points into -- to be kept alive through the call).  modes None: every string is parsed."""
+    if modes is None:
+        return _SpecialsOpts(None, 0, int(flags)), None
+    m = np.ascontiguousarray(modes, dtype=np.uint8)
+    buf = m if len(m) else np.zeros(1, np.uint8)
+    return _SpecialsOpts(_p(buf, ctypes.c_uint8), len(m), int(flags)), buf
+
+
+class SpecialsResult(_LayoutResult):
+    """What the device specials entries return (tk_specials): raw device pointers of context-owned buffers, valid until the next
+    specials call on the context.  bytes_ptr: uint8 [n_bytes], the text without the matched strings (the caller's own buffer where
+    n_removed == 0); part_offsets_ptr: uint64 [n_parts + 1]; part_ctrl_ptr: uint32 [n_parts] (JOIN_NONE: views() shows it as
+    int32, -1); conv_offsets_ptr: uint64 [n_docs + 1]; part_src_ptr: uint64 [n_parts] or None (SPECIALS_PART_SRC).
+    views(): one view per output in this order, the offsets as int64."""
+    STRUCT, PASS = _Specials, "specials"
+    OUTPUTS = (("bytes", "|u1", lambda r: (r.n_bytes,), np.uint8, False),
+               ("part_offsets", "<i8", lambda r: (r.n_parts + 1,), np.uint64, False),
+               ("part_ctrl", "<i4", lambda r: (r.n_parts,), np.uint32, False),
+               ("conv_offsets", "<i8", lambda r: (r.n_docs + 1,), np.uint64, False),
+               ("part_src", "<i8", lambda r: (r.n_parts,), np.uint64, True))
+    COUNTS = ("n_docs", "n_parts", "n_bytes", "n_matches", "n_removed")
+    DICT_COUNTS = ("n_parts", "n_bytes", "n_matches", "n_removed")
 
 
 class Engine:
@@ -1127,6 +1181,60 @@ class Engine:
         _, out = WordsResult.take(st)
         ids, oo = _take_result(res)
         return ids, oo, out
+
+    # ---- special-token strings parsed out of text (tk_specials): the entries take the text, so they are the pass's own
+    def split_specials_device(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, modes=None, flags=0, checks=0, stream=0):
+        """tk_specials_split_device: text resident in HBM -> the text without the special-token strings found in it, cut into the
+        parts that encode_parts_device_join takes (the definition is in include/tekken_hip.h).  modes: None (every string is
+        parsed) or one SPECIAL_TEXT / SPECIAL_PARSE / SPECIAL_RAISE per special id; flags: SPECIALS_BOS | SPECIALS_EOS |
+        SPECIALS_PART_SRC; checks: CHECK_OFFSETS | CHECK_UTF8.  A SPECIAL_RAISE match raises with .bad_doc set.  Returns a
+        SpecialsResult (context-owned device buffers, apart from every other output)."""
+        (o, keep), st, bad = _specials_opts(modes, flags), _Specials(), ctypes.c_uint64(0)
+        rc = _need("tk_specials_split_device")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_docs, n_bytes,
+                                               int(checks), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(st), ctypes.byref(bad))
+        if rc != TK_OK:
+            self._words_raise(rc, bad)
+        return SpecialsResult(st)
+
+    def encode_batch_device_parsed(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, modes=None, flags=0,
+                                   ignore_index=-100, join_flags=0, checks=0, stream=0):
+        """tk_encode_batch_device_parsed: the split + encode_parts_device_join over its parts on the same stream.  add_bos / add_eos
+        are SPECIALS_BOS / SPECIALS_EOS of flags.  Returns (SpecialsResult, JoinResult), both context-owned."""
+        f = int(flags) | (SPECIALS_BOS if add_bos else 0) | (SPECIALS_EOS if add_eos else 0)
+        (o, keep), st, j, bad = _specials_opts(modes, f), _Specials(), _Join(), ctypes.c_uint64(0)
+        jo = _JoinOpts(int(ignore_index), int(join_flags))
+        rc = _need("tk_encode_batch_device_parsed")(self._h, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_docs,
+                                                    n_bytes, int(checks), ctypes.byref(o), ctypes.byref(jo), ctypes.c_void_p(stream),
+                                                    ctypes.byref(st), ctypes.byref(j), ctypes.byref(bad))
+        if rc != TK_OK:
+            self._words_raise(rc, bad)
+        return SpecialsResult(st), JoinResult(j)
+
+    def encode_batch_parsed(self, data, offs, add_bos=True, add_eos=True, modes=None, flags=0, ignore_index=-100, join_flags=0,
+                            validate_utf8=False, return_parts=False):
+        """tk_encode_batch_parsed, host in / host out: the join's dict (ids uint32 [N], offsets uint64 [D + 1], labels, part_index,
+        the counts) and, with return_parts, the split's (bytes, part_offsets, part_ctrl, conv_offsets, part_src, the counts) as a
+        second dict."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        f = int(flags) | (SPECIALS_BOS if add_bos else 0) | (SPECIALS_EOS if add_eos else 0)
+        (o, keep), st, j, bad = _specials_opts(modes, f), _Specials(), _Join(), ctypes.c_uint64(0)
+        jo = _JoinOpts(int(ignore_index), int(join_flags))
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        rc = _need("tk_encode_batch_parsed")(self._h, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(validate_utf8),
+                                             ctypes.byref(o), ctypes.byref(jo), ctypes.byref(st) if return_parts else None, ctypes.byref(j),
+                                             ctypes.byref(bad))
+        if rc != TK_OK:
+            self._words_raise(rc, bad)
+        out = JoinResult.take(j)[1]
+        return (out, SpecialsResult.take(st)[1]) if return_parts else out
+
+    def last_specials_ms(self):
+        """tk_last_specials_ms: GPU time of the stages of the last specials pass on this context: (candidates, chain, part tables,
+        text compaction)."""
+        ms = (ctypes.c_float * 4)()
+        _need("tk_last_specials_ms")(self._h, ctypes.byref(ms))
+        return tuple(ms)
 
     def last_words_ms(self):
         """tk_last_words_ms: GPU milliseconds of the last words pass -- (split launch, words kernel, scan, word_first)."""
@@ -2110,6 +2218,60 @@ class Tekkenizer:
             raise self._err(rc)
         ids, oo = _take_result(res)
         return [ids[int(oo[d]):int(oo[d + 1])].tolist() for d in range(len(docs))]
+
+    def _special_modes(self, allowed, disallowed):
+        """One SPECIAL_* per special id from tiktoken's two keywords ("all" or an iterable of special-token names); None: every
+        string is parsed.  A name in neither is SPECIAL_TEXT."""
+        if isinstance(allowed, str) and allowed != "all" or isinstance(disallowed, str) and disallowed != "all":
+            raise ValueError("allowed / disallowed: 'all' or an iterable of special-token names")
+        if allowed == "all" and disallowed == "all":
+            raise ValueError("allowed and disallowed cannot both be 'all'")
+        a = None if allowed == "all" else {self.get_control_token(x) for x in allowed}      # (an unknown name: TokenNotFound)
+        d = None if disallowed == "all" else {self.get_control_token(x) for x in disallowed}
+        if a is not None and d is not None and a & d:
+            raise ValueError("special token ids %s are both allowed and disallowed" % sorted(a & d))
+        if a is None and not d:
+            return None
+        modes = np.full(self.num_special_tokens(), SPECIAL_PARSE if a is None else SPECIAL_RAISE if d is None else SPECIAL_TEXT, np.uint8)
+        for ids, m in ((a, SPECIAL_PARSE), (d, SPECIAL_RAISE)):
+            if ids:
+                modes[sorted(ids)] = m
+        return modes
+
+    def encode_with_specials(self, text, add_bos=False, add_eos=False, allowed="all", disallowed=()):
+        """encode, with the special-token strings found in the text turned into their ids (tiktoken's allowed_special /
+        disallowed_special; tk_tokenizer_encode_parsed, the definition is in include/tekken_hip.h): allowed / disallowed are "all" or
+        an iterable of special-token names; a string of a disallowed token in the text raises; a name in neither stays text."""
+        modes = self._special_modes(allowed, disallowed)
+        raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        if add_bos:
+            self.bos_id()      # (TokenNotFound when the vocabulary has no such control token, as encode)
+        if add_eos:
+            self.eos_id()
+        ids = ctypes.POINTER(ctypes.c_uint32)()
+        n = ctypes.c_size_t(0)
+        rc = _need("tk_tokenizer_encode_parsed")(self._h, raw, len(raw), int(add_bos), int(add_eos),
+                                                 None if modes is None else _p(modes, ctypes.c_uint8), 0 if modes is None else len(modes),
+                                                 ctypes.byref(ids), ctypes.byref(n))
+        if rc != TK_OK:
+            raise self._err(rc)
+        out = [ids[i] for i in range(n.value)]
+        lib().tk_free_ids(ids)
+        return out
+
+    def encode_batch_with_specials(self, docs, add_bos=False, add_eos=False, allowed="all", disallowed=()):
+        """The batch form on the tokenizer's engine context (tk_encode_batch_parsed): {"ids": uint32 [N], "id_offsets": uint64
+        [D + 1], "n_matches"}."""
+        eng = self._device_engine()
+        modes = self._special_modes(allowed, disallowed)
+        if add_bos:
+            self.bos_id()
+        if add_eos:
+            self.eos_id()
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        j = eng.encode_batch_parsed(data, offs, add_bos, add_eos, modes=modes)
+        # (every match, BOS and EOS is one part with a control id: the text itself does not come back for the count)
+        return {"ids": j["ids"], "id_offsets": j["offsets"], "n_matches": j["n_ctrl"] - len(docs) * (bool(add_bos) + bool(add_eos))}
 
     def decode(self, ids, policy=SpecialTokenPolicy.Ignore):
         """Tekkenizer::decode (src/tekkenizer.rs:436-443)."""

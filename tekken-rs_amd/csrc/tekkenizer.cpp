@@ -928,6 +928,12 @@ extern "C" int tk_tokenizer_encode(tk_tokenizer* h, const char* text, size_t len
     return TK_OK;
 }
 
+// (tk_capi_specials.cpp: tk_tokenizer_encode_parsed runs on the engine's context and reports through the tokenizer)
+int tk_tokenizer_fail(tk_tokenizer* h, int code, const std::string& message) {
+    h->err = message;
+    return code;
+}
+
 // The spans of one document on the host: an exclusive prefix sum of the ids' byte lengths from the rank table (a special id:
 // 0) -- what tk_spans_kernel computes, without a second launch.
 extern "C" int tk_tokenizer_encode_with_spans(tk_tokenizer* h, const char* text, size_t len, int add_bos, int add_eos,

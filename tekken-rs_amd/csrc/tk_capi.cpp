@@ -310,5 +310,9 @@ extern "C" int tk_ctx_set_special_tokens(tk_ctx* c, const uint8_t* blob, const u
     int rc;
     if ((rc = upload(c, c->t_spblob, blob, n ? offs[n] : 0)) || (rc = upload(c, c->t_spoffs, offs, ((size_t)n + 1) * 4))) return rc;
     c->have_specials = true;
+    // (the host copy the specials pass builds its byte trie from, at its first call behind this one)
+    c->specials.h_blob.assign(blob, blob + (n ? offs[n] : 0));
+    c->specials.h_offs.assign(offs, offs + n + 1);
+    c->specials.trie_ready = false;
     return TK_OK;
 }

@@ -54,19 +54,25 @@ static int validate_utf8_device(tk_ctx* c, const uint8_t* d_bytes, const uint64_
     return TK_OK;
 }
 
+int check_text_device(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, int checks, void* hip_stream) {
+    if (!d_doc_offsets || (!d_bytes && n_bytes)) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
+    int rc = enter_device(c, n_docs);
+    if (rc != TK_OK) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    uint32_t bad = 0;
+    rc = count_invalid(c, s, &bad, [&](uint32_t* d_bad) { return tk_launch_check_offsets((const uint64_t*)d_doc_offsets, n_docs, n_bytes, d_bad, s); });
+    if (rc != TK_OK) return rc;
+    if (bad) { c->err = "doc_offsets must start at 0, be non-decreasing and end at n_bytes (" + std::to_string(bad) + " violation(s))"; return TK_ERR_INVALID_ARG; }
+    if ((checks & TK_CHECK_UTF8) && (rc = validate_utf8_device(c, (const uint8_t*)d_bytes, (const uint64_t*)d_doc_offsets, n_docs, s)) != TK_OK) return rc;
+    return TK_OK;
+}
+
 // (the body of tk_encode_batch_device_ex; the caller holds c->mu and has refused unknown flags)
 int encode_device_checked(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, int add_bos,
                           int add_eos, int checks, void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids) {
     if (checks) {
-        if (!d_doc_offsets || (!d_bytes && n_bytes)) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-        int rc = enter_device(c, n_docs);
+        const int rc = check_text_device(c, d_bytes, d_doc_offsets, n_docs, n_bytes, checks, hip_stream);
         if (rc != TK_OK) return rc;
-        hipStream_t s = (hipStream_t)hip_stream;
-        uint32_t bad = 0;
-        rc = count_invalid(c, s, &bad, [&](uint32_t* d_bad) { return tk_launch_check_offsets((const uint64_t*)d_doc_offsets, n_docs, n_bytes, d_bad, s); });
-        if (rc != TK_OK) return rc;
-        if (bad) { c->err = "doc_offsets must start at 0, be non-decreasing and end at n_bytes (" + std::to_string(bad) + " violation(s))"; return TK_ERR_INVALID_ARG; }
-        if ((checks & TK_CHECK_UTF8) && (rc = validate_utf8_device(c, (const uint8_t*)d_bytes, (const uint64_t*)d_doc_offsets, n_docs, s)) != TK_OK) return rc;
     }
     return encode_device(c, d_bytes, d_doc_offsets, n_docs, n_bytes, add_bos, add_eos, hip_stream, d_ids, d_out_offsets, n_ids);
 }

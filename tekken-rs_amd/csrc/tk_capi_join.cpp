@@ -6,7 +6,7 @@
 #define TK_JOIN_ALL_FLAGS (TK_JOIN_LABELS | TK_JOIN_PART_INDEX)
 
 // what can be refused before anything is on the device (step 6 of the definition)
-static int join_check_args(tk_ctx* c, uint64_t n_parts, uint64_t n_convs, const tk_join_opts* o) {
+int join_check_args(tk_ctx* c, uint64_t n_parts, uint64_t n_convs, const tk_join_opts* o) {
     if (!o) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
     if (o->flags & ~(uint32_t)TK_JOIN_ALL_FLAGS) { c->err = "unknown join flag"; return TK_ERR_INVALID_ARG; }
     int rc = check_n_docs(c, n_parts);

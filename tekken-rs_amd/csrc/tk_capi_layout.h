@@ -1,7 +1,8 @@
 // tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _rowfit / _regroup / _pair.cpp) share, and
 // only they include: ONE description of the outputs of each result struct, from which tk_free_<pass> and the copy-out of the host
 // entries are made, and the three entries around a pass (ids on the device | text on the device | text on the host) written once.
-// (tk_capi_words.cpp takes the description of tk_words from here and has entries of its own: they take the text.)
+// (tk_capi_words.cpp and tk_capi_specials.cpp take the descriptions of tk_words / tk_specials from here and have entries of their
+// own: they take the text.)
 #ifndef TK_CAPI_LAYOUT_H
 #define TK_CAPI_LAYOUT_H
 #include <type_traits>
@@ -72,6 +73,13 @@ template <class F> static inline void layout_outputs(tk_regroup& r, uint64_t, ui
     f(r.perm, r.n_docs * 4, r.perm != nullptr);
     f(r.batch_offsets, (r.n_batches + 1) * 8, r.batch_offsets != nullptr);
     f(r.batch_rowlen, r.n_batches * 4, r.batch_rowlen != nullptr);
+}
+template <class F> static inline void layout_outputs(tk_specials& r, uint64_t, uint64_t, F&& f) {
+    f(r.bytes, r.n_bytes, true);                // (no byte: the block alone, as a join's ids)
+    f(r.part_offsets, (r.n_parts + 1) * 8, true);
+    f(r.part_ctrl, r.n_parts * 4, true);
+    f(r.conv_offsets, (r.n_docs + 1) * 8, true);
+    f(r.part_src, r.n_parts * 8, r.part_src != nullptr);
 }
 template <class F> static inline void layout_outputs(tk_words& r, uint64_t, uint64_t, F&& f) {
     f(r.word_ids, r.n_ids * 4, true);

@@ -134,6 +134,22 @@ struct WordsBufs {
     Event ev[6];                   // the stages of the last words call (tk_last_words_ms), created at the first one
     float ms[4] = {0.f, 0.f, 0.f, 0.f};   // split launch | words kernel | scan | word_first
 };
+// the special-token strings parsed out of text (tk_specials.hip): the text without them, the part tables; the host copy of the
+// context's strings and the byte trie over them (built at the first call behind tk_ctx_set_special_tokens: edges, term; str_of:
+// the distinct string of every id, TKS_NONE for one that is empty or too long), the per-call eff words; the work arrays (the
+// tile counts and their scan, the candidates, the jump tables, the marks, the matches, the match lengths and their scan, the
+// matches' positions, the segments, the scan workspace, the statistics words); the host entry's copies of the text and its offsets
+struct SpecialsBufs {
+    DevBuf bytes, poffs, ctrl, conv, psrc;
+    std::vector<uint8_t> h_blob;
+    std::vector<uint32_t> h_offs, str_of, h_eff;
+    uint32_t n_distinct = 0, edge_mask = 0;
+    bool trie_ready = false;
+    DevBuf edges, term, eff;
+    DevBuf tcnt, tpos, cpos, clen, cid, cdoc, ja, jb, row, open, flen, remc, mpos, sout, ssrc, bsum, stat, in_bytes, in_offs;
+    Event ev[8];                   // the stages of the last specials call (tk_last_specials_ms), created at the first one
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};   // candidates | chain | part tables | text compaction
+};
 
 struct tk_ctx {
     int device = 0;
@@ -167,6 +183,7 @@ struct tk_ctx {
     RowfitBufs rowfit;
     RegroupBufs regroup;
     WordsBufs words;
+    SpecialsBufs specials;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -258,6 +275,8 @@ int run_pipeline(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs, uint
 TkEncodeArgs encode_args(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* d_offs, uint64_t n_docs, int add_bos, int add_eos);
 // tk_capi_encode.cpp
 int check_offsets(tk_ctx* c, const uint64_t* doc_offsets, uint64_t n_docs);
+// TK_CHECK_OFFSETS / TK_CHECK_UTF8 over text on the device (checks != 0: one small kernel and one host wait each)
+int check_text_device(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, int checks, void* hip_stream);
 int encode_device_checked(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, int add_bos,
                           int add_eos, int checks, void* hip_stream, void** d_ids, void** d_out_offsets, uint64_t* n_ids);
 // Where the device copy of a host batch and of its result lives once encode_batch returns (the spans and dense passes read them):
@@ -276,6 +295,8 @@ int encode_batch_for_layout(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc
 int encode_parts_device_join(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
                              const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
                              int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out);
+// ... and what it refuses before anything is on the device (tk_capi_specials.cpp asks before it splits the text)
+int join_check_args(tk_ctx* c, uint64_t n_parts, uint64_t n_convs, const tk_join_opts* o);
 // tk_capi_decode.cpp: the decode kernels' tables (also what the spans kernel reads), built at the first call that needs them
 int token_tables(tk_ctx* c);
 template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // ... as the decode and spans kernels take them

@@ -402,6 +402,61 @@ hipError_t tk_launch_regroup_pyramid(const TkRegroupArgs& a, hipStream_t s);   /
 hipError_t tk_launch_regroup_nxt(const TkRegroupArgs& a, hipStream_t s);       // jump, row, bmax
 hipError_t tk_launch_regroup_batches(const TkRegroupArgs& a, hipStream_t s);   // batch_offs, batch_rowlen, stat[8..10] (behind tk_launch_chain_rounds)
 
+// ---- special-token strings parsed out of text: matches, parts, the text without them (tk_specials.hip) ----
+#define TKS_TILE 4096u         /* text bytes of a block's tile of the candidate kernel (16 a thread) */
+#define TKS_MAXLEN 255u        /* the longest string that can be matched: the look-ahead behind a tile is TKS_MAXLEN - 1 bytes */
+#define TKS_NONE 0xFFFFFFFFu
+#define TKS_RAISE 0x80000000u  /* the bit of a candidate's id that says its mode is TK_SPECIAL_RAISE */
+// the automaton's transition table: open addressing, an entry is (key + 1) << 32 | child with key = node << 8 | byte, 0 = empty
+static inline __host__ __device__ uint32_t tks_edge_slot(uint32_t key, uint32_t mask) {
+    uint32_t h = key * 0x9E3779B1u;
+    h ^= h >> 15;
+    return h & mask;
+}
+struct TkSpecialsArgs {
+    const uint8_t* bytes;      // [n_bytes] the text
+    const uint64_t* doc_offs;  // [n_docs + 1]
+    uint64_t n_docs, n_bytes;
+    const uint64_t* edges;     // [edge_mask + 1] the byte trie over the context's strings (node 0: the root)
+    uint32_t edge_mask;
+    const uint32_t* term;      // [n_nodes] the distinct string that ends at the node, or TKS_NONE
+    const uint32_t* eff;       // [n_distinct] per call: the lowest id of the match set with that string (| TKS_RAISE), or TKS_NONE
+    uint32_t first[8];         // 256 bits: the first bytes of the match set
+    uint32_t bos, eos;         // part 0's control id or TK_JOIN_NONE | the id of the closing part (eos_part != 0)
+    uint32_t eos_part;         // 1 with TK_SPECIALS_EOS
+    uint64_t n_tiles;          // ceil(n_bytes / TKS_TILE)
+    uint32_t* tile_cnt;        // [n_tiles] candidates that start in the tile
+    const uint64_t* tile_pos;  // [n_tiles + 1] exclusive scan of tile_cnt
+    uint64_t n_cand;           // NC: known behind the first host read
+    uint64_t* cpos;            // [NC + 1] where candidate c starts in the text, increasing; [NC] = n_bytes
+    uint32_t* clen;            // [NC] the length of the longest string of the match set there (inside the document)
+    uint32_t* cid;             // [NC] its id | TKS_RAISE
+    uint32_t* cdoc;            // [NC] its document
+    uint64_t* jump;            // [NC + 1] the chain's first links (TkRowfitArgs.jump_a)
+    uint32_t* row;             // [NC + 1] the number of the match a candidate is, 0xFFFFFFFF = none; [NC] = n_matches
+    const uint64_t* open;      // [n_matches + 1] the candidates that are matches, increasing; [n_matches] = NC
+    uint32_t* flen;            // [NC] clen of a match, 0 of any other candidate
+    const uint64_t* remc;      // [NC + 1] exclusive scan of flen: the bytes removed in front of candidate c; [NC] = n_removed
+    uint64_t n_matches, n_removed;   // M, sum l: known behind the second host read
+    uint64_t* mpos;            // [M] where match r starts in the text
+    uint64_t* seg_out;         // [M + 1] where the text behind match r - 1 (r = 0: the head of the text) starts in the output, non-decreasing
+    uint64_t* seg_src;         // [M + 1] ... and in the input
+    uint8_t* out_bytes;        // [n_bytes - n_removed]
+    uint64_t* part_offs;       // [P + 1], P = n_docs * (1 + eos_part) + M
+    uint32_t* part_ctrl;       // [P]
+    uint64_t* conv_offs;       // [n_docs + 1]
+    uint64_t* part_src;        // [P] or NULL
+    unsigned long long* stat;  // [0] = NC (tk_launch_specials_count_end); [1]: the first candidate that is a RAISE match (atomicMin: ~0 from
+                               // the caller); [8..13]: the chain's own ([11] = M)
+};
+hipError_t tk_launch_specials_cand(const TkSpecialsArgs& a, int write, hipStream_t s);   // write = 0: tile_cnt | 1: cpos, clen, cid, cdoc (behind the scan of tile_cnt)
+hipError_t tk_launch_specials_count_end(const TkSpecialsArgs& a, hipStream_t s);   // stat[0] = tile_pos[n_tiles]
+hipError_t tk_launch_specials_nxt(const TkSpecialsArgs& a, hipStream_t s);         // jump, row (then tk_launch_chain_rounds)
+hipError_t tk_launch_specials_mark(const TkSpecialsArgs& a, hipStream_t s);        // flen, stat[1] (behind the chain)
+hipError_t tk_launch_specials_matches(const TkSpecialsArgs& a, hipStream_t s);     // mpos, seg_out, seg_src, the parts behind the matches (M known)
+hipError_t tk_launch_specials_docs(const TkSpecialsArgs& a, hipStream_t s);        // conv_offs, the first and the closing part of every document, part_offs[P]
+hipError_t tk_launch_specials_compact(const TkSpecialsArgs& a, hipStream_t s);     // out_bytes; nothing left: nothing is launched
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
