@@ -646,6 +646,96 @@ void tk_last_specials_ms(const tk_ctx* ctx, float ms[4]);
 /* The text bytes of a tile of the candidate kernel (tests place matches across its boundaries). */
 uint32_t tk_specials_tile(void);
 
+/* ---- fill-in-the-middle rows: documents cut in two places and reordered on the device (no reference equivalent; the
+ * [PREFIX] / [SUFFIX] / [MIDDLE] control tokens of a Tekken vocabulary are what it is for) ----
+ * A document is cut at two random places into prefix P, middle M and suffix S and becomes "[SUFFIX] S [PREFIX] P M" (SPM without
+ * a middle id: Mistral / Codestral) or "[PREFIX] P [SUFFIX] S [MIDDLE] M" (PSM).  This pass makes the cuts, the part tables that
+ * tk_encode_parts_device_join / tk_join_from_ids_device take, and the text (or the ids) copied once in the new order; no token
+ * spans a part boundary, which is the seam as inference sees it.  ONE definition over units: a unit is a byte for the text
+ * entries and an id (uint32) for the ids entries.  Inputs: units, offsets[D + 1] (uint64, as encode takes them), tk_fim_opts, and
+ * optionally cuts, uint64[D][2], document-relative; TK_FIM_NO_CUT in slot 0 means "leave this document alone".
+ *   1. Body.  Text entries: head = tail = 0 (refused otherwise); the body is the whole document, n = len.  Ids entries: the first
+ *      `head` and last `tail` ids (a stored BOS / EOS) stay in place, the body is what lies between, n = len - head - tail.  A
+ *      document with len < head + tail is never transformed: its body is the whole document, its head and tail are empty.
+ *   2. Draws, all arithmetic mod 2^32, h exactly as at TK_REGROUP_ORDER_SHUFFLE below:  s_k = h(seed, 0x46494D00 + k),
+ *      u_k = h(s_k, d), k = 0..3 (epoch e and e + 1 share no draw).  Without cuts document d is a candidate iff u_0 < rate_q32; a
+ *      candidate is transformed iff len >= head + tail and n >= max(min_units, 1) and n < 2^32 - 1; its cuts are
+ *      c_i = (uint64(u_{2+i}) * (n + 1)) >> 32, uniform over 0..n.  With cuts every document whose slot 0 is not TK_FIM_NO_CUT is a
+ *      candidate, transformed iff len >= head + tail and n < 2^32 - 1; its cuts are the two given values, each clamped to n;
+ *      rate_q32 and min_units play no part.  n_skipped = the candidates that are not transformed.  Order: SPM iff
+ *      u_1 < spm_q32, else PSM.
+ *   3. Snap (text entries with TK_FIM_SNAP only).  For each cut c, at most 3 times: while 0 < c < n and (byte[c] & 0xC0) == 0x80:
+ *      c -= 1.  Defined on bytes, so total on malformed UTF-8; on valid UTF-8 every cut lands on a character start.  Then
+ *      lo = min, hi = max; P = body[0 : lo), M = body[lo : hi), S = body[hi : n).
+ *   4. Parts.  Every document gives exactly 5 parts: conv_offsets[d] = 5 d, n_parts = 5 D.
+ *          part      untransformed                 PSM                 SPM
+ *          0 head    text entries: no text, ctrl = the BOS id with TK_FIM_BOS, else TK_JOIN_NONE; ids entries: the head ids, no ctrl
+ *          1         (NONE, body)                  (prefix_id, P)      (suffix_id, S)
+ *          2         (NONE, empty)                 (suffix_id, S)      (prefix_id, P)
+ *          3         (NONE, empty)                 (middle_id, M)      (middle_id, M)
+ *          4 tail    the mirror of part 0: the EOS id with TK_FIM_EOS, or the tail ids
+ *      Each of the three ids may be TK_JOIN_NONE (Mistral: SPM with middle_id = NONE).  units holds the parts' units in part
+ *      order: document d keeps its range [offsets[d], offsets[d+1]), permuted; n_units is the input's.  part_offsets
+ *      (uint64, 5 D + 1) are the parts' starts in units; part_src (uint64, 5 D, only with TK_FIM_PART_SRC, else NULL) is where
+ *      each part's first unit lies in the INPUT buffer (an empty part: where its text would begin; the empty parts 2 and 3 of an
+ *      untransformed document: the body's end).
+ *   5. Labels.  part_flags (uint32, 5 D) = TK_PART_LABEL_CTRL | TK_PART_LABEL_TEXT on every part; with TK_FIM_LABEL_MIDDLE a
+ *      transformed document's parts 0..2 get 0, part 3 TK_PART_LABEL_TEXT alone, part 4 both.  Untransformed documents stay fully
+ *      labelled.
+ *   6. Also out: cuts (uint64 [D][2]) = (lo, hi) behind the snap, or TK_FIM_NO_CUT twice; mode (uint8 [D]): 0 none, 1 PSM, 2 SPM;
+ *      n_transformed, n_spm, n_skipped.
+ *   7. The encoding it defines.  J_d = the join of the document's five parts.  For an untransformed document it is bit for bit
+ *      what tk_encode_batch returns with the same BOS / EOS (text), or the input ids (ids).  With rate_q32 == 0 and no cuts
+ *      out->units may be the caller's own buffer, not copied.
+ *   8. Valid and empty: D == 0, empty documents, n_units == 0.  TK_ERR_INVALID_ARG, nothing written, an earlier result stays
+ *      readable: an unknown flag (opts or checks); TK_FIM_BOS / TK_FIM_EOS on an ids entry; rate_q32 or spm_q32 above 2^32; head or
+ *      tail non-zero on a text entry; an id that is neither TK_JOIN_NONE nor < num_special_tokens; D >= 2^32 - 16; a NULL required
+ *      argument.  checks (text entries): TK_CHECK_OFFSETS / TK_CHECK_UTF8 as in tk_encode_batch_device_ex, on the INPUT.  Without
+ *      TK_CHECK_OFFSETS malformed offsets give parts that mean nothing, but nothing outside [units, units + n_units) is read.
+ *      out's buffers are device buffers owned by the context, SEPARATE from every other pass's and valid until the next FIM call.
+ * A separate pass in front of the unchanged encode pipeline (csrc/tk_fim.hip): one thread a document makes the
+ * draws, the snap (at most 3 byte reads a cut) and the five part records; the permute kernel has the shape of the join, regroup
+ * and compaction kernels -- a block takes tiles of output units, two wave searches over offsets, the tile's documents' cuts in
+ * LDS, a thread resolves 16 bytes: one 16-byte load at any byte and one 16-byte store where they lie in one of the document's
+ * shifted ranges, unit by unit over the seams.  No scan, no host read before the last wait, which fetches the three counters. */
+#define TK_FIM_NO_CUT (~0ull)
+#define TK_FIM_SNAP 1
+#define TK_FIM_BOS 2
+#define TK_FIM_EOS 4
+#define TK_FIM_PART_SRC 8
+#define TK_FIM_LABEL_MIDDLE 16
+typedef struct tk_fim_opts { uint64_t rate_q32, spm_q32; uint32_t seed, prefix_id, suffix_id, middle_id, head, tail, min_units, flags; } tk_fim_opts;
+typedef struct tk_fim { void* units; uint64_t* part_offsets; uint32_t* part_ctrl; uint32_t* part_flags; uint64_t* conv_offsets;
+                        uint64_t* part_src; uint64_t* cuts; uint8_t* mode;
+                        uint64_t n_docs, n_parts, n_units, n_transformed, n_spm, n_skipped; } tk_fim;
+/* Text on the device -> the parts (units: uint8).  d_cuts: uint64[n_docs][2] on the device, or NULL.  The work is enqueued on
+ * hip_stream and the call returns after the stream has drained. */
+int tk_fim_split_device(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes, const void* d_cuts,
+                        int checks, const tk_fim_opts* opts, void* hip_stream, tk_fim* out);
+/* Ids on the device (encode's own output, or stored ids) -> the parts (units: uint32); part_offsets are then the d_id_offsets of
+ * tk_join_from_ids_device. */
+int tk_fim_split_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids, const void* d_cuts,
+                            const tk_fim_opts* opts, void* hip_stream, tk_fim* out);
+/* The text split + tk_encode_parts_device_join over its parts (part_flags included) on the same stream: *out is J (step 7),
+ * *parts (optional) the split's result.  Everything that can be refused is refused before anything is encoded. */
+int tk_encode_batch_device_fim(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                               const void* d_cuts, int checks, const tk_fim_opts* opts, const tk_join_opts* jopts, void* hip_stream,
+                               tk_fim* parts, tk_join* out);
+/* The ids split + tk_join_from_ids_device: a new draw every epoch over documents tokenised once (cuts at token boundaries). */
+int tk_fim_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids, const void* d_cuts,
+                           const tk_fim_opts* opts, const tk_join_opts* jopts, void* hip_stream, tk_fim* parts, tk_join* out);
+/* Host in / host out (cuts: a host array or NULL).  out's (and, where parts is not NULL, parts') buffers are pinned host memory,
+ * released with tk_free_join / tk_free_fim (an unselected output is NULL). */
+int tk_encode_batch_fim(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, const uint64_t* cuts,
+                        int validate_utf8, const tk_fim_opts* opts, const tk_join_opts* jopts, tk_fim* parts, tk_join* out);
+void tk_free_fim(tk_fim* out);
+/* GPU time of the context's last FIM pass from events on its stream: ms[0] the cut kernel, ms[1] the permute kernel (0 where
+ * nothing was copied).  Both 0 where the pass was refused. */
+void tk_last_fim_ms(const tk_ctx* ctx, float ms[2]);
+/* The output units of a tile of the permute kernel for units of unit_bytes (1 or 4; anything else: 0): tests place seams on its
+ * borders. */
+uint32_t tk_fim_tile(int unit_bytes);
+
 /* ---- encoded documents selected, reordered and cut into batches on the device (no reference equivalent) ----
  * What a data pipeline does between "encode" and "batch": drop documents, put the rest into another order (shuffled, by length, by
  * length within shuffled groups), cut that order into batches under a padded-token budget.  Ragged in, ragged out: the result's

@@ -306,6 +306,43 @@ pub struct TkSpecials {
     pub n_matches: u64,
     pub n_removed: u64,
 }
+// fill-in-the-middle rows (tk_fim_opts.flags, tk_fim.cuts / .mode; include/tekken_hip.h has the definition)
+pub const TK_FIM_NO_CUT: u64 = !0;
+pub const TK_FIM_SNAP: u32 = 1;
+pub const TK_FIM_BOS: u32 = 2;
+pub const TK_FIM_EOS: u32 = 4;
+pub const TK_FIM_PART_SRC: u32 = 8;
+pub const TK_FIM_LABEL_MIDDLE: u32 = 16;
+#[repr(C)]
+pub struct TkFimOpts {
+    pub rate_q32: u64,
+    pub spm_q32: u64,
+    pub seed: u32,
+    pub prefix_id: u32,
+    pub suffix_id: u32,
+    pub middle_id: u32,
+    pub head: u32,
+    pub tail: u32,
+    pub min_units: u32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkFim {
+    pub units: *mut c_void,
+    pub part_offsets: *mut u64,
+    pub part_ctrl: *mut u32,
+    pub part_flags: *mut u32,
+    pub conv_offsets: *mut u64,
+    pub part_src: *mut u64,
+    pub cuts: *mut u64,
+    pub mode: *mut u8,
+    pub n_docs: u64,
+    pub n_parts: u64,
+    pub n_units: u64,
+    pub n_transformed: u64,
+    pub n_spm: u64,
+    pub n_skipped: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -443,6 +480,22 @@ extern "C" {
     pub fn tk_specials_tile() -> u32;
     pub fn tk_tokenizer_encode_parsed(t: *mut TkTokenizer, text: *const c_char, len: usize, add_bos: c_int, add_eos: c_int, modes: *const u8,
                                       n_modes: u32, ids: *mut *mut u32, n_ids: *mut usize) -> c_int;
+    pub fn tk_fim_split_device(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                               d_cuts: *const c_void, checks: c_int, opts: *const TkFimOpts, hip_stream: *mut c_void, out: *mut TkFim) -> c_int;
+    pub fn tk_fim_split_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                   d_cuts: *const c_void, opts: *const TkFimOpts, hip_stream: *mut c_void, out: *mut TkFim) -> c_int;
+    pub fn tk_encode_batch_device_fim(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                      d_cuts: *const c_void, checks: c_int, opts: *const TkFimOpts, jopts: *const TkJoinOpts,
+                                      hip_stream: *mut c_void, parts: *mut TkFim, out: *mut TkJoin) -> c_int;
+    pub fn tk_fim_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                  d_cuts: *const c_void, opts: *const TkFimOpts, jopts: *const TkJoinOpts, hip_stream: *mut c_void,
+                                  parts: *mut TkFim, out: *mut TkJoin) -> c_int;
+    pub fn tk_encode_batch_fim(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, cuts: *const u64,
+                               validate_utf8: c_int, opts: *const TkFimOpts, jopts: *const TkJoinOpts, parts: *mut TkFim,
+                               out: *mut TkJoin) -> c_int;
+    pub fn tk_free_fim(out: *mut TkFim);
+    pub fn tk_last_fim_ms(ctx: *const TkCtx, ms: *mut f32);
+    pub fn tk_fim_tile(unit_bytes: c_int) -> u32;
     pub fn tk_words_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
                                     d_bytes: *const c_void, d_doc_offsets: *const c_void, n_bytes: u64, checks: c_int,
                                     opts: *const TkWordsOpts, hip_stream: *mut c_void, out: *mut TkWords, bad: *mut u64) -> c_int;

@@ -50,6 +50,9 @@ WORDS_FIRST = 1   # tk_words_opts.flags (the words entries)
 WORDS_CHECK_ALIGNED = 32   # the words entries' check (beside CHECK_OFFSETS / CHECK_UTF8 in one word)
 SPECIAL_TEXT, SPECIAL_PARSE, SPECIAL_RAISE = 0, 1, 2   # tk_specials_opts.modes: what a special-token string found in text becomes
 SPECIALS_BOS, SPECIALS_EOS, SPECIALS_PART_SRC = 1, 2, 4   # tk_specials_opts.flags (the specials entries)
+FIM_NO_CUT = 0xFFFFFFFFFFFFFFFF   # cuts[d][0]: leave document d alone; cuts out: the document was not transformed
+FIM_SNAP, FIM_BOS, FIM_EOS, FIM_PART_SRC, FIM_LABEL_MIDDLE = 1, 2, 4, 8, 16   # tk_fim_opts.flags (the fill-in-the-middle entries)
+FIM_NONE, FIM_PSM, FIM_SPM = 0, 1, 2   # tk_fim.mode
 _ORDERS = {"keep": REGROUP_ORDER_KEEP, "length": REGROUP_ORDER_LENGTH, "shuffle": REGROUP_ORDER_SHUFFLE, "grouped": REGROUP_ORDER_GROUPED}   # the order keyword of encode_batch_regrouped
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
@@ -180,6 +183,19 @@ class _Specials(ctypes.Structure):
     _fields_ = [("bytes", ctypes.c_void_p), ("part_offsets", ctypes.c_void_p), ("part_ctrl", ctypes.c_void_p), ("conv_offsets", ctypes.c_void_p),
                 ("part_src", ctypes.c_void_p), ("n_docs", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_bytes", ctypes.c_uint64),
                 ("n_matches", ctypes.c_uint64), ("n_removed", ctypes.c_uint64)]
+
+
+class _FimOpts(ctypes.Structure):
+    _fields_ = [("rate_q32", ctypes.c_uint64), ("spm_q32", ctypes.c_uint64), ("seed", ctypes.c_uint32), ("prefix_id", ctypes.c_uint32),
+                ("suffix_id", ctypes.c_uint32), ("middle_id", ctypes.c_uint32), ("head", ctypes.c_uint32), ("tail", ctypes.c_uint32),
+                ("min_units", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class _Fim(ctypes.Structure):
+    _fields_ = [("units", ctypes.c_void_p), ("part_offsets", ctypes.c_void_p), ("part_ctrl", ctypes.c_void_p), ("part_flags", ctypes.c_void_p),
+                ("conv_offsets", ctypes.c_void_p), ("part_src", ctypes.c_void_p), ("cuts", ctypes.c_void_p), ("mode", ctypes.c_void_p),
+                ("n_docs", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_units", ctypes.c_uint64), ("n_transformed", ctypes.c_uint64),
+                ("n_spm", ctypes.c_uint64), ("n_skipped", ctypes.c_uint64)]
 
 
 class _WordsOpts(ctypes.Structure):
@@ -455,6 +471,24 @@ def lib():
         L.tk_tokenizer_encode_parsed.restype = ci
         L.tk_tokenizer_encode_parsed.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t, ci, ci, u8p, ctypes.c_uint32, ctypes.POINTER(u32p),
                                                  ctypes.POINTER(ctypes.c_size_t)]
+    if hasattr(L, "tk_fim_split_device"):   # (fill-in-the-middle rows: libraries built before them still load through TK_HIP_LIB)
+        fop, fp = ctypes.POINTER(_FimOpts), ctypes.POINTER(_Fim)
+        L.tk_fim_split_device.restype = ci
+        L.tk_fim_split_device.argtypes = [vp, vp, vp, u64, u64, vp, ci, fop, vp, fp]
+        L.tk_fim_split_ids_device.restype = ci
+        L.tk_fim_split_ids_device.argtypes = [vp, vp, vp, u64, u64, vp, fop, vp, fp]
+        L.tk_encode_batch_device_fim.restype = ci
+        L.tk_encode_batch_device_fim.argtypes = [vp, vp, vp, u64, u64, vp, ci, fop, jop, vp, fp, jp]
+        L.tk_fim_from_ids_device.restype = ci
+        L.tk_fim_from_ids_device.argtypes = [vp, vp, vp, u64, u64, vp, fop, jop, vp, fp, jp]
+        L.tk_encode_batch_fim.restype = ci
+        L.tk_encode_batch_fim.argtypes = [vp, u8p, u64p, u64, u64p, ci, fop, jop, fp, jp]
+        L.tk_free_fim.restype = None
+        L.tk_free_fim.argtypes = [fp]
+        L.tk_last_fim_ms.restype = None
+        L.tk_last_fim_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 2)]
+        L.tk_fim_tile.restype = ctypes.c_uint32
+        L.tk_fim_tile.argtypes = [ci]
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
@@ -767,6 +801,44 @@ class SpecialsResult(_LayoutResult):
                ("part_src", "<i8", lambda r: (r.n_parts,), np.uint64, True))
     COUNTS = ("n_docs", "n_parts", "n_bytes", "n_matches", "n_removed")
     DICT_COUNTS = ("n_parts", "n_bytes", "n_matches", "n_removed")
+
+
+def fim_q32(rate):
+    """A probability as tk_fim_opts carries it: min(2^32, round(rate * 2^32))."""
+    if not 0.0 <= float(rate) <= 1.0:
+        raise TokenizerError(TK_ERR_INVALID_ARG, "fim: a rate of %r is not in [0, 1]" % (rate,))
+    return min(1 << 32, int(round(float(rate) * (1 << 32))))
+
+
+def _fim_opts(rate_q32=0, spm_q32=0, seed=0, prefix_id=JOIN_NONE, suffix_id=JOIN_NONE, middle_id=JOIN_NONE, head=0, tail=0, min_units=0, flags=0):
+    return _FimOpts(int(rate_q32), int(spm_q32), int(seed) & 0xFFFFFFFF, int(prefix_id), int(suffix_id), int(middle_id), int(head), int(tail),
+                    int(min_units), int(flags))
+
+
+class FimResult(_LayoutResult):
+    """What the device fill-in-the-middle entries return (tk_fim): raw device pointers of context-owned buffers, valid until the
+    next FIM call on the context.  units_ptr: uint8 [n_units] (text entries) or uint32 [n_units] (ids entries; views() shows them
+    as int32), each document's units in part order -- the caller's own buffer where nothing could be transformed;
+    part_offsets_ptr: uint64 [n_parts + 1]; part_ctrl_ptr / part_flags_ptr: uint32 [n_parts] (JOIN_NONE: -1 in views());
+    conv_offsets_ptr: uint64 [n_docs + 1]; part_src_ptr: uint64 [n_parts] or None (FIM_PART_SRC); cuts_ptr: uint64 [n_docs, 2]
+    ((lo, hi), FIM_NO_CUT twice for an untransformed document: -1 in views()); mode_ptr: uint8 [n_docs].
+    views(): one view per output in this order, the offsets as int64.  unit_bytes: 1 or 4."""
+    STRUCT, PASS = _Fim, "fim"
+    OUTPUTS = (("units", None, lambda r: (r.n_units,), np.uint8, False),
+               ("part_offsets", "<i8", lambda r: (r.n_parts + 1,), np.uint64, False),
+               ("part_ctrl", "<i4", lambda r: (r.n_parts,), np.uint32, False),
+               ("part_flags", "<i4", lambda r: (r.n_parts,), np.uint32, False),
+               ("conv_offsets", "<i8", lambda r: (r.n_docs + 1,), np.uint64, False),
+               ("part_src", "<i8", lambda r: (r.n_parts,), np.uint64, True),
+               ("cuts", "<i8", lambda r: (r.n_docs, 2), np.uint64, False),
+               ("mode", "|u1", lambda r: (r.n_docs,), np.uint8, False))
+    COUNTS = ("n_docs", "n_parts", "n_units", "n_transformed", "n_spm", "n_skipped")
+    DICT_COUNTS = ("n_parts", "n_units", "n_transformed", "n_spm", "n_skipped")
+
+    def __init__(self, st, flags=0, n_docs=None, unit_bytes=1):
+        super().__init__(st, flags)
+        self.unit_bytes = int(unit_bytes)
+        self.typestr = "|u1" if self.unit_bytes == 1 else "<i4"   # (of units: the host entry takes text, so its array is uint8)
 
 
 class Engine:
@@ -1235,6 +1307,71 @@ class Engine:
         ms = (ctypes.c_float * 4)()
         _need("tk_last_specials_ms")(self._h, ctypes.byref(ms))
         return tuple(ms)
+
+    # ---- fill-in-the-middle rows (tk_fim): a pass in front of encode (text) or of the join (ids), so the entries are its own.
+    # opts: the keywords of _fim_opts (rate_q32, spm_q32, seed, prefix_id, suffix_id, middle_id, head, tail, min_units, flags)
+    def fim_split_device(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, d_cuts_ptr=0, checks=0, stream=0, **opts):
+        """tk_fim_split_device: text resident in HBM -> every chosen document cut in two places and reordered inside its own range,
+        with the part tables that encode_parts_device_join takes (the definition is in include/tekken_hip.h).  d_cuts_ptr: uint64
+        [n_docs, 2] on the device or 0 (drawn from seed); checks: CHECK_OFFSETS | CHECK_UTF8.  Returns a FimResult (context-owned
+        device buffers, apart from every other output)."""
+        o, st = _fim_opts(**opts), _Fim()
+        self._call("tk_fim_split_device", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_docs, n_bytes,
+                   ctypes.c_void_p(d_cuts_ptr or None), int(checks), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(st))
+        return FimResult(st, unit_bytes=1)
+
+    def fim_split_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_cuts_ptr=0, stream=0, **opts):
+        """tk_fim_split_ids_device: the same over ids resident in HBM (head / tail ids stay in place).  Returns a FimResult whose
+        units are uint32 and whose part_offsets are the id offsets join_from_ids_device takes."""
+        o, st = _fim_opts(**opts), _Fim()
+        self._call("tk_fim_split_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr or None), n_docs, n_ids,
+                   ctypes.c_void_p(d_cuts_ptr or None), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(st))
+        return FimResult(st, unit_bytes=4)
+
+    def encode_batch_device_fim(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, d_cuts_ptr=0, ignore_index=-100, join_flags=0, checks=0,
+                                stream=0, **opts):
+        """tk_encode_batch_device_fim: the text split + encode_parts_device_join over its parts (part_flags included) on the same
+        stream.  Returns (FimResult, JoinResult), both context-owned."""
+        o, st, j, jo = _fim_opts(**opts), _Fim(), _Join(), _JoinOpts(int(ignore_index), int(join_flags))
+        self._call("tk_encode_batch_device_fim", ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_docs, n_bytes,
+                   ctypes.c_void_p(d_cuts_ptr or None), int(checks), ctypes.byref(o), ctypes.byref(jo), ctypes.c_void_p(stream),
+                   ctypes.byref(st), ctypes.byref(j))
+        return FimResult(st, unit_bytes=1), JoinResult(j)
+
+    def fim_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_cuts_ptr=0, ignore_index=-100, join_flags=0, stream=0, **opts):
+        """tk_fim_from_ids_device: the ids split + join_from_ids_device (documents tokenised once, a new draw every epoch).
+        Returns (FimResult, JoinResult), both context-owned."""
+        o, st, j, jo = _fim_opts(**opts), _Fim(), _Join(), _JoinOpts(int(ignore_index), int(join_flags))
+        self._call("tk_fim_from_ids_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr or None), n_docs, n_ids,
+                   ctypes.c_void_p(d_cuts_ptr or None), ctypes.byref(o), ctypes.byref(jo), ctypes.c_void_p(stream), ctypes.byref(st),
+                   ctypes.byref(j))
+        return FimResult(st, unit_bytes=4), JoinResult(j)
+
+    def encode_batch_fim(self, data, offs, cuts=None, ignore_index=-100, join_flags=0, validate_utf8=False, return_parts=False, **opts):
+        """tk_encode_batch_fim, host in / host out: the join's dict (ids uint32 [N], offsets uint64 [D + 1], labels, part_index, the
+        counts) and, with return_parts, the split's (FimResult.OUTPUTS and the counts) as a second dict.  cuts: None or uint64
+        [D, 2]."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        D = len(offs) - 1
+        cbuf = None
+        if cuts is not None:
+            cbuf = np.ascontiguousarray(cuts, dtype=np.uint64).reshape(-1)
+            if len(cbuf) != 2 * D:
+                raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_fim: cuts must be [n_docs, 2]")
+            cbuf = cbuf if D else np.zeros(2, np.uint64)
+        o, st, j, jo = _fim_opts(**opts), _Fim(), _Join(), _JoinOpts(int(ignore_index), int(join_flags))
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        self._call("tk_encode_batch_fim", _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), D, None if cbuf is None else _p(cbuf, ctypes.c_uint64),
+                   int(validate_utf8), ctypes.byref(o), ctypes.byref(jo), ctypes.byref(st) if return_parts else None, ctypes.byref(j))
+        out = JoinResult.take(j)[1]
+        return (out, FimResult.take(st)[1]) if return_parts else out
+
+    def last_fim_ms(self):
+        """tk_last_fim_ms: GPU milliseconds of the last FIM pass on this context -- (cut kernel, permute kernel)."""
+        ms = (ctypes.c_float * 2)()
+        _need("tk_last_fim_ms")(self._h, ctypes.byref(ms))
+        return tuple(float(x) for x in ms)
 
     def last_words_ms(self):
         """tk_last_words_ms: GPU milliseconds of the last words pass -- (split launch, words kernel, scan, word_first)."""
@@ -2272,6 +2409,105 @@ class Tekkenizer:
         j = eng.encode_batch_parsed(data, offs, add_bos, add_eos, modes=modes)
         # (every match, BOS and EOS is one part with a control id: the text itself does not come back for the count)
         return {"ids": j["ids"], "id_offsets": j["offsets"], "n_matches": j["n_ctrl"] - len(docs) * (bool(add_bos) + bool(add_eos))}
+
+    # ---- fill-in-the-middle rows (tk_fim; the definition is in include/tekken_hip.h)
+    def _fim_opts_of(self, method, fim_rate, spm_rate, seed, format, train_on, add_bos, add_eos, min_length, return_tensors):
+        """The keywords of the engine's FIM entries from those of the Tekkenizer methods.  "mistral": always suffix first and no
+        middle token, "[SUFFIX] S [PREFIX] P M"; "psm_spm": "[PREFIX] P [SUFFIX] S [MIDDLE] M", or suffix first with probability
+        spm_rate.  The ids come from get_control_token (TokenNotFound where the vocabulary lacks one)."""
+        if format not in ("mistral", "psm_spm") or train_on not in ("all", "middle") or return_tensors not in ("pt", "np"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "%s: unknown format / train_on / return_tensors value" % method)
+        if not 0 <= int(min_length) < 2 ** 32:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "%s: min_length %r" % (method, min_length))
+        if add_bos:
+            self.bos_id()
+        if add_eos:
+            self.eos_id()
+        mistral = format == "mistral"
+        return dict(rate_q32=fim_q32(fim_rate), spm_q32=(1 << 32) if mistral else fim_q32(spm_rate), seed=seed,
+                    prefix_id=self.get_control_token("[PREFIX]"), suffix_id=self.get_control_token("[SUFFIX]"),
+                    middle_id=JOIN_NONE if mistral else self.get_control_token("[MIDDLE]"), min_units=min_length,
+                    flags=FIM_SNAP | (FIM_BOS if add_bos else 0) | (FIM_EOS if add_eos else 0) | (FIM_LABEL_MIDDLE if train_on == "middle" else 0))
+
+    @staticmethod
+    def _fim_cuts(cuts, n_docs):
+        """cuts of the Tekkenizer methods -- None, or per document None or a pair of byte positions -- as uint64 [D, 2]."""
+        if cuts is None:
+            return None
+        if len(cuts) != n_docs:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "fim: one cuts entry per document (None, or a pair of byte positions)")
+        out = np.full((n_docs, 2), FIM_NO_CUT, np.uint64)
+        for d, c in enumerate(cuts):
+            if c is not None:
+                out[d] = (int(c[0]), int(c[1]))
+        return out
+
+    def encode_batch_fim(self, docs, fim_rate=0.5, spm_rate=0.5, seed=0, format="mistral", train_on="all", add_bos=True, add_eos=True,
+                         cuts=None, min_length=0, ignore_index=-100, return_tensors="np", copy=True):
+        """Fill-in-the-middle rows for a code / infill model (tk_encode_batch_device_fim / tk_encode_batch_fim): with probability
+        fim_rate a document is cut at two byte positions drawn from (seed, its index), snapped back to character starts, and
+        encoded as "[SUFFIX] S [PREFIX] P M" (format "mistral") or "[PREFIX] P [SUFFIX] S [MIDDLE] M" / suffix first with probability
+        spm_rate ("psm_spm"); every piece is encoded on its own, so no token spans a cut -- the seam inference sees (encode_fim).
+        Another seed is another draw: pass the epoch.  cuts: None, or per document None (leave it alone) or (a, b) byte positions,
+        which replace the draws (fim_rate and min_length then play no part).  min_length: shorter documents (in bytes) are left
+        alone.  train_on "middle": only the middle and what closes the row are labelled in transformed documents.
+        -> {"input_ids": [N] all rows back to back, "offsets": [D + 1], "labels": [N] int32, "cuts": [D, 2] the cuts made (FIM_NO_CUT:
+        none), "mode": uint8 [D] (FIM_NONE / FIM_PSM / FIM_SPM), "n_transformed", "n_spm", "n_skipped", "n_labelled"}.  return_tensors
+        "np": numpy; "pt": torch tensors on the tokenizer's GPU (copy=False: views of context-owned buffers)."""
+        eng = self._device_engine()
+        opts = self._fim_opts_of("encode_batch_fim", fim_rate, spm_rate, seed, format, train_on, add_bos, add_eos, min_length, return_tensors)
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        c = self._fim_cuts(cuts, len(docs))
+        if return_tensors == "np":
+            j, f = eng.encode_batch_fim(data, offs, c, ignore_index, JOIN_LABELS, return_parts=True, **opts)
+        else:
+            import torch
+            d_bytes, d_offs, stream = _upload(data, offs)
+            d_cuts = None if c is None else torch.from_numpy((c if len(c) else np.zeros((1, 2), np.uint64)).view(np.int64)).cuda()
+            fr, jr = eng.encode_batch_device_fim(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), 0 if d_cuts is None else d_cuts.data_ptr(),
+                                                 ignore_index, JOIN_LABELS, CHECK_OFFSETS, stream, **opts)
+            j, f = jr.tensors(copy), fr.tensors(copy)
+        return {"input_ids": j["ids"], "offsets": j["offsets"], "labels": j["labels"], "cuts": f["cuts"], "mode": f["mode"],
+                "n_transformed": f["n_transformed"], "n_spm": f["n_spm"], "n_skipped": f["n_skipped"], "n_labelled": j["n_labelled"]}
+
+    def encode_batch_fim_packed(self, docs, seq_len, fim_rate=0.5, spm_rate=0.5, seed=0, format="mistral", train_on="all", add_bos=True,
+                                add_eos=True, cuts=None, min_length=0, ignore_index=-100, pad_id=None, dtype="int64", return_position_ids=True,
+                                return_segment_ids=True, return_cu_seqlens=True, return_doc_start=True, return_tensors="pt", copy=True):
+        """encode_batch_fim packed for training: the split, then encode_parts_device_rowfit over its parts -- whole rows placed
+        next-fit into rows of seq_len, never cut, with labels; one upload and nothing through the host in between.  -> what
+        encode_chat_packed returns, and "n_transformed", "n_spm", "n_skipped"."""
+        eng = self._device_engine()
+        opts = self._fim_opts_of("encode_batch_fim_packed", fim_rate, spm_rate, seed, format, train_on, add_bos, add_eos, min_length, return_tensors)
+        if dtype not in ("int64", "int32") or not 0 <= int(seq_len) < 2 ** 32:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "encode_batch_fim_packed: dtype %r, seq_len %r" % (dtype, seq_len))
+        import torch
+        pad = self.pad_id() if pad_id is None else int(pad_id)
+        flags = self._rowfit_flags(dtype, return_position_ids, return_segment_ids, return_cu_seqlens, return_doc_start) | ROWFIT_LABELS
+        data, offs = pack_docs([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+        c = self._fim_cuts(cuts, len(docs))
+        d_bytes, d_offs, stream = _upload(data, offs)
+        d_cuts = None if c is None else torch.from_numpy((c if len(c) else np.zeros((1, 2), np.uint64)).view(np.int64)).cuda()
+        f = eng.fim_split_device(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), 0 if d_cuts is None else d_cuts.data_ptr(),
+                                 CHECK_OFFSETS, stream, **opts)
+        res, fit = eng.encode_parts_device_rowfit(f.units_ptr, f.part_offsets_ptr, f.n_parts, f.n_units, f.part_ctrl_ptr, f.part_flags_ptr,
+                                                  f.conv_offsets_ptr, len(docs), seq_len, pad, 0, flags, ignore_index, JOIN_LABELS, 0, stream)
+        out = fit.tensors(copy)
+        # (the labels are int32 with negative values: int32 elements through the pass, widened here -- which sign-extends)
+        if dtype == "int64":
+            out["labels"] = out["labels"].to(torch.int64)
+        out.update(n_labelled=res.n_labelled, n_transformed=f.n_transformed, n_spm=f.n_spm, n_skipped=f.n_skipped)
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() if torch.is_tensor(v) else v for k, v in out.items()}
+        return out
+
+    def encode_fim(self, prefix, suffix, add_bos=True):
+        """The inference prompt of a Mistral / Codestral infill model: [BOS, SUFFIX, enc(suffix), PREFIX, enc(prefix)], each text
+        encoded on its own (encode_parts_join) -- what encode_batch_fim(format="mistral") gives for prefix + middle + suffix cut at
+        the two seams, without the middle and EOS.  The model continues with the middle."""
+        eng = self._device_engine()
+        parts = ([(self.bos_id(), "", False)] if add_bos else []) + [(self.get_control_token("[SUFFIX]"), suffix, False),
+                                                                     (self.get_control_token("[PREFIX]"), prefix, False)]
+        return [int(x) for x in eng.encode_parts_join(*self._parts_of([parts]))["ids"]]
 
     def decode(self, ids, policy=SpecialTokenPolicy.Ignore):
         """Tekkenizer::decode (src/tekkenizer.rs:436-443)."""

@@ -60,9 +60,9 @@ static int check_parts_device(tk_ctx* c, const uint32_t* d_ctrl, const uint64_t*
 // The join over ids on the device into the context's c->join buffers; *out gets the device pointers.  The outputs are sized for
 // n_ids + n_parts elements, so nothing is read before the launches; ONE wait at the end (N, n_ctrl, n_labelled).  Nothing of an
 // earlier result is touched before every argument has been accepted.  The caller holds c->mu.
-static int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t P, uint64_t n_ids, const uint32_t* d_ctrl,
-                    const uint32_t* d_pflags, const uint64_t* d_conv, uint64_t C, bool check_parts, const tk_join_opts* o, hipStream_t s,
-                    tk_join* out) {
+int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t P, uint64_t n_ids, const uint32_t* d_ctrl,
+             const uint32_t* d_pflags, const uint64_t* d_conv, uint64_t C, bool check_parts, const tk_join_opts* o, hipStream_t s,
+             tk_join* out) {
     int rc = join_check_args(c, P, C, o);
     if (rc != TK_OK) return rc;
     if (P == 0 && n_ids) { c->err = "join: ids without a part"; return TK_ERR_INVALID_ARG; }

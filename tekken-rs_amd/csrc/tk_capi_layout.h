@@ -1,8 +1,8 @@
 // tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _rowfit / _regroup / _pair.cpp) share, and
 // only they include: ONE description of the outputs of each result struct, from which tk_free_<pass> and the copy-out of the host
 // entries are made, and the three entries around a pass (ids on the device | text on the device | text on the host) written once.
-// (tk_capi_words.cpp and tk_capi_specials.cpp take the descriptions of tk_words / tk_specials from here and have entries of their
-// own: they take the text.)
+// (tk_capi_words.cpp, tk_capi_specials.cpp and tk_capi_fim.cpp take the descriptions of tk_words / tk_specials / tk_fim from here
+// and have entries of their own: they take the text, or stand in front of encode.)
 #ifndef TK_CAPI_LAYOUT_H
 #define TK_CAPI_LAYOUT_H
 #include <type_traits>
@@ -80,6 +80,16 @@ template <class F> static inline void layout_outputs(tk_specials& r, uint64_t, u
     f(r.part_ctrl, r.n_parts * 4, true);
     f(r.conv_offsets, (r.n_docs + 1) * 8, true);
     f(r.part_src, r.n_parts * 8, r.part_src != nullptr);
+}
+template <class F> static inline void layout_outputs(tk_fim& r, uint64_t esz, uint64_t, F&& f) {
+    f(r.units, r.n_units * esz, true);          // (esz: the bytes of a unit, 1 for text and 4 for ids)
+    f(r.part_offsets, (r.n_parts + 1) * 8, true);
+    f(r.part_ctrl, r.n_parts * 4, true);
+    f(r.part_flags, r.n_parts * 4, true);
+    f(r.conv_offsets, (r.n_docs + 1) * 8, true);
+    f(r.part_src, r.n_parts * 8, r.part_src != nullptr);
+    f(r.cuts, r.n_docs * 16, true);
+    f(r.mode, r.n_docs, true);
 }
 template <class F> static inline void layout_outputs(tk_words& r, uint64_t, uint64_t, F&& f) {
     f(r.word_ids, r.n_ids * 4, true);

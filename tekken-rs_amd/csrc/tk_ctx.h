@@ -150,6 +150,13 @@ struct SpecialsBufs {
     Event ev[8];                   // the stages of the last specials call (tk_last_specials_ms), created at the first one
     float ms[4] = {0.f, 0.f, 0.f, 0.f};   // candidates | chain | part tables | text compaction
 };
+// the fill-in-the-middle pass (tk_fim.hip): the units in the new order, the part tables, cuts and mode, the three counters; the
+// host entry's copies of the text, its offsets and the caller's cuts
+struct FimBufs {
+    DevBuf units, poffs, ctrl, pflags, conv, psrc, cuts, mode, stat, in_units, in_offs, in_cuts;
+    Event ev[3];                   // the stages of the last FIM call (tk_last_fim_ms), created at the first one
+    float ms[2] = {0.f, 0.f};      // cut kernel | permute kernel
+};
 
 struct tk_ctx {
     int device = 0;
@@ -184,6 +191,7 @@ struct tk_ctx {
     RegroupBufs regroup;
     WordsBufs words;
     SpecialsBufs specials;
+    FimBufs fim;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -295,8 +303,12 @@ int encode_batch_for_layout(tk_ctx* c, const uint8_t* bytes, const uint64_t* doc
 int encode_parts_device_join(tk_ctx* c, const void* d_bytes, const void* d_doc_offsets, uint64_t n_parts, uint64_t n_bytes,
                              const void* d_part_ctrl, const void* d_part_flags, const void* d_conv_offsets, uint64_t n_convs,
                              int checks, const tk_join_opts* opts, void* hip_stream, tk_join* out);
-// ... and what it refuses before anything is on the device (tk_capi_specials.cpp asks before it splits the text)
+// ... and what it refuses before anything is on the device (tk_capi_specials.cpp and tk_capi_fim.cpp ask before they split the text)
 int join_check_args(tk_ctx* c, uint64_t n_parts, uint64_t n_convs, const tk_join_opts* o);
+// ... and the join itself over ids on the device (tk_capi_fim.cpp runs it behind the ids split under one lock)
+int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t P, uint64_t n_ids, const uint32_t* d_ctrl,
+             const uint32_t* d_pflags, const uint64_t* d_conv, uint64_t C, bool check_parts, const tk_join_opts* o, hipStream_t s,
+             tk_join* out);
 // tk_capi_decode.cpp: the decode kernels' tables (also what the spans kernel reads), built at the first call that needs them
 int token_tables(tk_ctx* c);
 template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // ... as the decode and spans kernels take them

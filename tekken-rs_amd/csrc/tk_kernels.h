@@ -457,6 +457,42 @@ hipError_t tk_launch_specials_matches(const TkSpecialsArgs& a, hipStream_t s);  
 hipError_t tk_launch_specials_docs(const TkSpecialsArgs& a, hipStream_t s);        // conv_offs, the first and the closing part of every document, part_offs[P]
 hipError_t tk_launch_specials_compact(const TkSpecialsArgs& a, hipStream_t s);     // out_bytes; nothing left: nothing is launched
 
+// ---- fill-in-the-middle rows: documents cut in two places and reordered (tk_fim.hip) ----
+#define TKI_TILE1 16384u       /* output bytes of a block's tile of the permute kernel over text: 64 a thread */
+#define TKI_TILE4 4096u        /* output ids of a block's tile of the permute kernel over ids: 16 a thread */
+#define TKI_SEED_BASE 0x46494D00u
+#define TKI_HT 4u              /* the bit of a staged mode word that says the document has its head and tail */
+// h(seed, d) of the regroup pass (include/tekken_hip.h TK_REGROUP_ORDER_SHUFFLE); the host makes the four s_k with it
+static inline __host__ __device__ uint32_t tki_hash(uint32_t seed, uint32_t d) {
+    uint32_t x = d * 0x9E3779B1u + seed;
+    x ^= x >> 16; x *= 0x85EBCA6Bu;
+    x ^= x >> 13; x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+struct TkFimArgs {
+    const void* units;         // [n_units] bytes or ids
+    const uint64_t* offs;      // [n_docs + 1]
+    uint64_t n_docs, n_units;
+    const uint64_t* in_cuts;   // [n_docs][2] the caller's cuts, or NULL: drawn
+    uint64_t rate, spm;        // rate_q32, spm_q32
+    uint32_t s[4];             // s_k = h(seed, TKI_SEED_BASE + k)
+    uint32_t ctrl[3];          // prefix_id, suffix_id, middle_id
+    uint32_t head, tail, min_units, flags;
+    uint32_t bos, eos;         // the control ids of parts 0 and 4 (TK_JOIN_NONE: none)
+    void* out_units;           // [n_units]
+    uint64_t* part_offs;       // [5 n_docs + 1]
+    uint32_t* part_ctrl;       // [5 n_docs]
+    uint32_t* part_flags;      // [5 n_docs]
+    uint64_t* conv_offs;       // [n_docs + 1]
+    uint64_t* part_src;        // [5 n_docs] or NULL
+    uint64_t* cuts;            // [n_docs][2] (lo, hi) behind the snap, or TK_FIM_NO_CUT twice
+    uint8_t* mode;             // [n_docs] 0 none | 1 PSM | 2 SPM
+    unsigned long long* stat;  // [0] n_transformed, [1] n_spm, [2] n_skipped (zeroed by the caller)
+};
+hipError_t tk_launch_fim_cut(const TkFimArgs& a, int unit_bytes, hipStream_t s);       // everything but out_units
+hipError_t tk_launch_fim_permute(const TkFimArgs& a, int unit_bytes, hipStream_t s);   // out_units (behind tk_launch_fim_cut); no unit: nothing is launched
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
