@@ -736,6 +736,105 @@ void tk_last_fim_ms(const tk_ctx* ctx, float ms[2]);
  * borders. */
 uint32_t tk_fim_tile(int unit_bytes);
 
+/* ---- masked-LM and span-corruption rows: a noise pass over encoded ids (no reference equivalent; HF's
+ * DataCollatorForLanguageModeling(mlm=True) / DataCollatorForWholeWordMask, SpanBERT's spans, MNTP; T5 / UL2 span corruption) ----
+ * One hash-drawn (or caller-given) choice of tokens, words or spans per document, and two things made of it: the ids with the
+ * chosen ones masked and the labels (replace mode), or the documents with every chosen run replaced by one sentinel and the
+ * targets that spell the runs out (spans mode).  A new draw every epoch over documents tokenised once: the seed is the epoch.
+ * Inputs: ids (uint32 [N]), id_offsets (uint64 [D + 1]), optionally word_ids (uint32 [N], exactly as tk_words_from_ids_device
+ * writes them), optionally sel (uint8 [N]), tk_noise_opts.  V = the context's vocabulary size (ranks + special tokens),
+ * S0 = num_special_tokens.
+ *   1. Eligibility and unit.  Id i sits in document d at document-relative position p.  It is eligible iff ids[i] >= S0 and, under
+ *      TK_NOISE_UNIT_WORD, word_ids[i] != TK_WORD_NONE.  Its unit index x_i is p under TK_NOISE_UNIT_TOKEN and word_ids[i] under
+ *      TK_NOISE_UNIT_WORD (which needs word_ids, unless sel is given).
+ *   2. Draws, all arithmetic mod 2^32, h exactly as at TK_REGROUP_ORDER_SHUFFLE below:  s_k = h(seed, 0x4E4F4900 + k), k = 0..3;
+ *      t_k = h(s_k, d).  Per unit index x of document d:
+ *          start(x)   iff h(t_0, x) < start_q32
+ *          len(x)     = span_min + ((uint64(h(t_1, x)) * (span_max - span_min + 1)) >> 32)
+ *          covered(x) iff some q with x - span_max < q <= x, q >= 0, has start(q) and q + len(q) > x
+ *      The draws are over indices and do not look at eligibility: a special id's position can start a span.
+ *      selected(i) = eligible(i) and covered(x_i).  With sel: selected(i) = eligible(i) and sel[i] != 0; start_q32 and the span
+ *      lengths then play no part.  1 <= span_min <= span_max <= TK_NOISE_SPAN_LIMIT; start_q32 <= 2^32.
+ *   3. Replace mode (tk_noise_replace_device).  The offsets are the input's.  r = h(t_2, p), v = h(t_3, p), and
+ *          input_ids[i] = ids[i]                                   if not selected
+ *                       = mask_id                                  if r < mask_q32
+ *                       = S0 + ((uint64(v) * (V - S0)) >> 32)      if r < mask_q32 + random_q32   (64-bit; the sum <= 2^32)
+ *                       = ids[i]                                   otherwise
+ *      labels (int32 [N]) = ids[i] where selected, else ignore_index; selected (uint8 [N], 0 / 1) only with TK_NOISE_SELECTED, else
+ *      NULL.  mask_id is any id < V (Tekken has no [MASK]: a <SPECIAL_n> control id or an ordinary token).  n_selected, n_masked,
+ *      n_random count the three.  n_sentinels, sentinel_first, final_id and the other flags play no part.
+ *   4. Spans mode (tk_noise_spans_device).  A run is a maximal sequence of consecutive selected ids inside one document: runs
+ *      never join across a document boundary, and an ineligible id inside a covered stretch splits a run.  Run k, numbered from
+ *      0 in its document, is kept iff k < n_sentinels; the ids of a dropped run count as not selected (n_runs_dropped counts the
+ *      runs).  The sentinel of run k is sentinel_first + k, with TK_NOISE_DESC sentinel_first - k; every sentinel the options can
+ *      produce must be < S0.  Per document: inputs_d = the document's ids in order with every kept run replaced by its sentinel;
+ *      targets_d = for every kept run in order its sentinel followed by its ids, then final_id unless that is TK_JOIN_NONE.
+ *      TK_NOISE_SPLIT: inputs / input_offsets (uint64 [D + 1]) and targets / target_offsets, two ragged batches that feed the
+ *      dense pass as they are.  TK_NOISE_JOINED: joined / joined_offsets / joined_labels with joined_d = inputs_d ++ targets_d
+ *      and joined_labels (int32) the id on the targets' elements, ignore_index on the inputs' (the decoder-only form).  At least
+ *      one of the two; an unselected output is NULL.  n_selected (behind the drop), n_runs (kept), n_runs_dropped, n_inputs,
+ *      n_targets.  A document without a kept run: inputs_d is the document, targets_d is empty or final_id alone.  mask_id, the
+ *      two rates of step 3 and TK_NOISE_SELECTED play no part.
+ *   5. Valid and empty: D == 0, empty documents, N == 0, start_q32 == 0, n_sentinels == 0 (everything dropped).
+ *      TK_ERR_INVALID_ARG, nothing written, an earlier result stays readable: an unknown flag or unit; the span limits violated; a
+ *      rate above 2^32, or mask_q32 + random_q32 above it; mask_id >= V; a sentinel that the options can produce, or a final_id
+ *      other than TK_JOIN_NONE, that is not < S0; neither TK_NOISE_SPLIT nor TK_NOISE_JOINED (spans mode); TK_NOISE_UNIT_WORD
+ *      without word_ids and without sel; D >= 2^32 - 16; a document of 2^32 - 1 ids or more (spans mode: of 2^32 - 2 -
+ *      n_sentinels or more, so that the lengths of inputs_d and targets_d stay in 32 bits); a NULL required argument.  Without
+ *      well-formed id_offsets the outputs mean nothing, but nothing outside [ids, ids + N) (and the same range of word_ids and sel)
+ *      is read and nothing outside the outputs written.  out's buffers are device buffers owned by the context, SEPARATE from
+ *      every other pass's, and valid until the next noise call (replace and spans share them).
+ * A separate pass behind the unchanged encode pipeline (csrc/tk_noise.hip).  Replace mode is one kernel: tiles of
+ * ids, every thread the hashes of its own 4 positions, covered from a prefix maximum over the tile with a halo of span_max - 1
+ * positions recomputed from their hashes (word unit: from the at most span_max candidate starts of the id's word); 16-byte loads
+ * and stores, no scan launch, no host read before the last wait.  Spans mode: the selection, per-tile and per-document counts of
+ * selected ids and run starts, two scans over tiles and two over documents, one host read that sizes the outputs, and a fill
+ * kernel in which every id computes where it goes. */
+#define TK_NOISE_UNIT_TOKEN 0
+#define TK_NOISE_UNIT_WORD 1
+#define TK_NOISE_SELECTED 1
+#define TK_NOISE_DESC 2
+#define TK_NOISE_SPLIT 4
+#define TK_NOISE_JOINED 8
+#define TK_NOISE_SPAN_LIMIT 64
+typedef struct tk_noise_opts { uint64_t start_q32, mask_q32, random_q32; uint32_t seed, unit, span_min, span_max, mask_id, n_sentinels,
+                               sentinel_first, final_id, flags; int32_t ignore_index; } tk_noise_opts;
+typedef struct tk_noise_replace { uint32_t* input_ids; int32_t* labels; uint8_t* selected;
+                                  uint64_t n_docs, n_ids, n_selected, n_masked, n_random; } tk_noise_replace;
+typedef struct tk_noise_spans { uint32_t* inputs; uint64_t* input_offsets; uint32_t* targets; uint64_t* target_offsets; uint32_t* joined;
+                                uint64_t* joined_offsets; int32_t* joined_labels;
+                                uint64_t n_docs, n_selected, n_runs, n_runs_dropped, n_inputs, n_targets; } tk_noise_spans;
+/* ids already on the device (encode's own outputs, or stored ids).  d_word_ids: NULL or uint32 [n_ids]; d_sel: NULL or uint8
+ * [n_ids].  The work is enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_noise_replace_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids, const void* d_word_ids,
+                            const void* d_sel, const tk_noise_opts* opts, void* hip_stream, tk_noise_replace* out);
+int tk_noise_spans_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids, const void* d_word_ids,
+                          const void* d_sel, const tk_noise_opts* opts, void* hip_stream, tk_noise_spans* out);
+/* tk_encode_batch_device_ex, with TK_NOISE_UNIT_WORD the words pass, and the noise pass on the same stream.  Everything that can
+ * be refused is refused before anything is encoded.  *d_ids / *d_out_offsets / *n_ids as tk_encode_batch_device: with
+ * start_q32 == 0 (replace mode) out->input_ids holds the same ids bit for bit. */
+int tk_encode_batch_device_noise_replace(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                         int add_bos, int add_eos, int checks, const tk_noise_opts* opts, void* hip_stream, void** d_ids,
+                                         void** d_out_offsets, uint64_t* n_ids, tk_noise_replace* out);
+int tk_encode_batch_device_noise_spans(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                       int add_bos, int add_eos, int checks, const tk_noise_opts* opts, void* hip_stream, void** d_ids,
+                                       void** d_out_offsets, uint64_t* n_ids, tk_noise_spans* out);
+/* Host in / host out: tk_encode_batch + the passes above.  ids_out as tk_encode_batch (tk_free_result): the ids in front of the
+ * noise and their offsets, which are replace mode's.  out's buffers are pinned host memory, released with tk_free_noise_replace /
+ * tk_free_noise_spans (an unselected output is NULL). */
+int tk_encode_batch_noise_replace(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                                  int validate_utf8, const tk_noise_opts* opts, tk_result* ids_out, tk_noise_replace* out);
+int tk_encode_batch_noise_spans(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                                int validate_utf8, const tk_noise_opts* opts, tk_result* ids_out, tk_noise_spans* out);
+void tk_free_noise_replace(tk_noise_replace* out);
+void tk_free_noise_spans(tk_noise_spans* out);
+/* GPU time of the stages of the context's last noise pass, from events on its stream: ms[0] the selection (replace mode: the whole
+ * pass), ms[1] the counts and scans of spans mode (the host read behind them is not counted), ms[2] its fill kernel.  All 0 where
+ * the pass was refused. */
+void tk_last_noise_ms(const tk_ctx* ctx, float ms[3]);
+/* The input ids of a tile of the noise kernels: tests place runs, spans and document boundaries on its borders. */
+uint32_t tk_noise_tile(void);
+
 /* ---- encoded documents selected, reordered and cut into batches on the device (no reference equivalent) ----
  * What a data pipeline does between "encode" and "batch": drop documents, put the rest into another order (shuffled, by length, by
  * length within shuffled groups), cut that order into batches under a padded-token budget.  Ragged in, ragged out: the result's

@@ -343,6 +343,57 @@ pub struct TkFim {
     pub n_spm: u64,
     pub n_skipped: u64,
 }
+// masked-LM and span-corruption rows (tk_noise_opts.unit / .flags; include/tekken_hip.h has the definition)
+pub const TK_NOISE_UNIT_TOKEN: u32 = 0;
+pub const TK_NOISE_UNIT_WORD: u32 = 1;
+pub const TK_NOISE_SELECTED: u32 = 1;
+pub const TK_NOISE_DESC: u32 = 2;
+pub const TK_NOISE_SPLIT: u32 = 4;
+pub const TK_NOISE_JOINED: u32 = 8;
+pub const TK_NOISE_SPAN_LIMIT: u32 = 64;
+#[repr(C)]
+pub struct TkNoiseOpts {
+    pub start_q32: u64,
+    pub mask_q32: u64,
+    pub random_q32: u64,
+    pub seed: u32,
+    pub unit: u32,
+    pub span_min: u32,
+    pub span_max: u32,
+    pub mask_id: u32,
+    pub n_sentinels: u32,
+    pub sentinel_first: u32,
+    pub final_id: u32,
+    pub flags: u32,
+    pub ignore_index: i32,
+}
+#[repr(C)]
+pub struct TkNoiseReplace {
+    pub input_ids: *mut u32,
+    pub labels: *mut i32,
+    pub selected: *mut u8,
+    pub n_docs: u64,
+    pub n_ids: u64,
+    pub n_selected: u64,
+    pub n_masked: u64,
+    pub n_random: u64,
+}
+#[repr(C)]
+pub struct TkNoiseSpans {
+    pub inputs: *mut u32,
+    pub input_offsets: *mut u64,
+    pub targets: *mut u32,
+    pub target_offsets: *mut u64,
+    pub joined: *mut u32,
+    pub joined_offsets: *mut u64,
+    pub joined_labels: *mut i32,
+    pub n_docs: u64,
+    pub n_selected: u64,
+    pub n_runs: u64,
+    pub n_runs_dropped: u64,
+    pub n_inputs: u64,
+    pub n_targets: u64,
+}
 
 extern "C" {
     // engine level: replaces CoreBPE::new / CoreBPE::encode (src/tekkenizer.rs:125, :384-386)
@@ -496,6 +547,29 @@ extern "C" {
     pub fn tk_free_fim(out: *mut TkFim);
     pub fn tk_last_fim_ms(ctx: *const TkCtx, ms: *mut f32);
     pub fn tk_fim_tile(unit_bytes: c_int) -> u32;
+    pub fn tk_noise_replace_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                   d_word_ids: *const c_void, d_sel: *const c_void, opts: *const TkNoiseOpts, hip_stream: *mut c_void,
+                                   out: *mut TkNoiseReplace) -> c_int;
+    pub fn tk_noise_spans_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                 d_word_ids: *const c_void, d_sel: *const c_void, opts: *const TkNoiseOpts, hip_stream: *mut c_void,
+                                 out: *mut TkNoiseSpans) -> c_int;
+    pub fn tk_encode_batch_device_noise_replace(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64,
+                                                n_bytes: u64, add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkNoiseOpts,
+                                                hip_stream: *mut c_void, d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void,
+                                                n_ids: *mut u64, out: *mut TkNoiseReplace) -> c_int;
+    pub fn tk_encode_batch_device_noise_spans(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                              add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkNoiseOpts, hip_stream: *mut c_void,
+                                              d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64,
+                                              out: *mut TkNoiseSpans) -> c_int;
+    pub fn tk_encode_batch_noise_replace(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int,
+                                         add_eos: c_int, validate_utf8: c_int, opts: *const TkNoiseOpts, ids_out: *mut TkResult,
+                                         out: *mut TkNoiseReplace) -> c_int;
+    pub fn tk_encode_batch_noise_spans(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                       validate_utf8: c_int, opts: *const TkNoiseOpts, ids_out: *mut TkResult, out: *mut TkNoiseSpans) -> c_int;
+    pub fn tk_free_noise_replace(out: *mut TkNoiseReplace);
+    pub fn tk_free_noise_spans(out: *mut TkNoiseSpans);
+    pub fn tk_last_noise_ms(ctx: *const TkCtx, ms: *mut f32);
+    pub fn tk_noise_tile() -> u32;
     pub fn tk_words_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
                                     d_bytes: *const c_void, d_doc_offsets: *const c_void, n_bytes: u64, checks: c_int,
                                     opts: *const TkWordsOpts, hip_stream: *mut c_void, out: *mut TkWords, bad: *mut u64) -> c_int;

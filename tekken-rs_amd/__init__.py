@@ -53,6 +53,10 @@ SPECIALS_BOS, SPECIALS_EOS, SPECIALS_PART_SRC = 1, 2, 4   # tk_specials_opts.fla
 FIM_NO_CUT = 0xFFFFFFFFFFFFFFFF   # cuts[d][0]: leave document d alone; cuts out: the document was not transformed
 FIM_SNAP, FIM_BOS, FIM_EOS, FIM_PART_SRC, FIM_LABEL_MIDDLE = 1, 2, 4, 8, 16   # tk_fim_opts.flags (the fill-in-the-middle entries)
 FIM_NONE, FIM_PSM, FIM_SPM = 0, 1, 2   # tk_fim.mode
+NOISE_UNIT_TOKEN, NOISE_UNIT_WORD = 0, 1   # tk_noise_opts.unit (the noise entries: masked-LM and span-corruption rows)
+NOISE_SELECTED, NOISE_DESC, NOISE_SPLIT, NOISE_JOINED = 1, 2, 4, 8   # tk_noise_opts.flags
+NOISE_SPAN_LIMIT = 64   # the largest span_max
+_NOISE_UNITS = {"token": NOISE_UNIT_TOKEN, "word": NOISE_UNIT_WORD}   # the unit keyword of encode_batch_mlm / encode_batch_span_corruption
 _ORDERS = {"keep": REGROUP_ORDER_KEEP, "length": REGROUP_ORDER_LENGTH, "shuffle": REGROUP_ORDER_SHUFFLE, "grouped": REGROUP_ORDER_GROUPED}   # the order keyword of encode_batch_regrouped
 TK_ERR_INVALID_CONFIG = -1
 TK_ERR_RUNTIME = -2
@@ -196,6 +200,25 @@ class _Fim(ctypes.Structure):
                 ("conv_offsets", ctypes.c_void_p), ("part_src", ctypes.c_void_p), ("cuts", ctypes.c_void_p), ("mode", ctypes.c_void_p),
                 ("n_docs", ctypes.c_uint64), ("n_parts", ctypes.c_uint64), ("n_units", ctypes.c_uint64), ("n_transformed", ctypes.c_uint64),
                 ("n_spm", ctypes.c_uint64), ("n_skipped", ctypes.c_uint64)]
+
+
+class _NoiseOpts(ctypes.Structure):
+    _fields_ = [("start_q32", ctypes.c_uint64), ("mask_q32", ctypes.c_uint64), ("random_q32", ctypes.c_uint64), ("seed", ctypes.c_uint32),
+                ("unit", ctypes.c_uint32), ("span_min", ctypes.c_uint32), ("span_max", ctypes.c_uint32), ("mask_id", ctypes.c_uint32),
+                ("n_sentinels", ctypes.c_uint32), ("sentinel_first", ctypes.c_uint32), ("final_id", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("ignore_index", ctypes.c_int32)]
+
+
+class _NoiseReplace(ctypes.Structure):
+    _fields_ = [("input_ids", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("selected", ctypes.c_void_p), ("n_docs", ctypes.c_uint64),
+                ("n_ids", ctypes.c_uint64), ("n_selected", ctypes.c_uint64), ("n_masked", ctypes.c_uint64), ("n_random", ctypes.c_uint64)]
+
+
+class _NoiseSpans(ctypes.Structure):
+    _fields_ = [("inputs", ctypes.c_void_p), ("input_offsets", ctypes.c_void_p), ("targets", ctypes.c_void_p), ("target_offsets", ctypes.c_void_p),
+                ("joined", ctypes.c_void_p), ("joined_offsets", ctypes.c_void_p), ("joined_labels", ctypes.c_void_p), ("n_docs", ctypes.c_uint64),
+                ("n_selected", ctypes.c_uint64), ("n_runs", ctypes.c_uint64), ("n_runs_dropped", ctypes.c_uint64), ("n_inputs", ctypes.c_uint64),
+                ("n_targets", ctypes.c_uint64)]
 
 
 class _WordsOpts(ctypes.Structure):
@@ -492,6 +515,26 @@ def lib():
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
+    if hasattr(L, "tk_noise_replace_device"):   # (masked-LM and span-corruption rows: libraries built before them still load through TK_HIP_LIB)
+        nop = ctypes.POINTER(_NoiseOpts)
+        for mode, st in (("replace", _NoiseReplace), ("spans", _NoiseSpans)):
+            np_ = ctypes.POINTER(st)
+            fn = getattr(L, "tk_noise_%s_device" % mode)
+            fn.restype = ci
+            fn.argtypes = [vp, vp, vp, u64, u64, vp, vp, nop, vp, np_]
+            fn = getattr(L, "tk_encode_batch_device_noise_" + mode)
+            fn.restype = ci
+            fn.argtypes = [vp, vp, vp, u64, u64, ci, ci, ci, nop, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, np_]
+            fn = getattr(L, "tk_encode_batch_noise_" + mode)
+            fn.restype = ci
+            fn.argtypes = [vp, u8p, u64p, u64, ci, ci, ci, nop, ctypes.POINTER(_Result), np_]
+            fn = getattr(L, "tk_free_noise_" + mode)
+            fn.restype = None
+            fn.argtypes = [np_]
+        L.tk_last_noise_ms.restype = None
+        L.tk_last_noise_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 3)]
+        L.tk_noise_tile.restype = ctypes.c_uint32
+        L.tk_noise_tile.argtypes = []
     return L
 
 
@@ -839,6 +882,70 @@ class FimResult(_LayoutResult):
         super().__init__(st, flags)
         self.unit_bytes = int(unit_bytes)
         self.typestr = "|u1" if self.unit_bytes == 1 else "<i4"   # (of units: the host entry takes text, so its array is uint8)
+
+
+def noise_start_q32(rate, span_min=1, span_max=1):
+    """The start_q32 of tk_noise_opts under which the expected covered fraction of the units is `rate`.  A unit x is left alone iff
+    none of the span_max units q = x - j, j = 0 .. span_max - 1, starts a span longer than j; starts are independent with
+    probability s and len is uniform over span_min .. span_max, so P(len > j) = 1 for j < span_min, (span_max - j) / (span_max -
+    span_min + 1) behind it, and  1 - prod_j (1 - s P(len > j)) = rate  is solved for s by bisection (the left side grows with s)."""
+    rate, lo_n, hi_n = float(rate), int(span_min), int(span_max)
+    if not 0.0 <= rate <= 1.0 or not 1 <= lo_n <= hi_n <= NOISE_SPAN_LIMIT:
+        raise TokenizerError(TK_ERR_INVALID_ARG, "noise: rate %r / span (%r, %r) out of range" % (rate, span_min, span_max))
+    longer = [1.0 if j < lo_n else (hi_n - j) / (hi_n - lo_n + 1.0) for j in range(hi_n)]
+
+    def covered(s):
+        left = 1.0
+        for pj in longer:
+            left *= 1.0 - s * pj
+        return 1.0 - left
+
+    if rate in (0.0, 1.0):                              # (exactly none, exactly all)
+        return int(rate) << 32
+    lo, hi = 0.0, 1.0
+    for _ in range(64):
+        mid = 0.5 * (lo + hi)
+        if covered(mid) < rate:
+            lo = mid
+        else:
+            hi = mid
+    return min(1 << 32, int(round(hi * (1 << 32))))
+
+
+def _noise_opts(start_q32=0, mask_q32=0, random_q32=0, seed=0, unit=NOISE_UNIT_TOKEN, span_min=1, span_max=1, mask_id=0, n_sentinels=0,
+                sentinel_first=0, final_id=JOIN_NONE, flags=0, ignore_index=-100):
+    return _NoiseOpts(int(start_q32), int(mask_q32), int(random_q32), int(seed) & 0xFFFFFFFF, int(unit), int(span_min), int(span_max), int(mask_id),
+                      int(n_sentinels), int(sentinel_first), int(final_id), int(flags), int(ignore_index))
+
+
+class NoiseReplaceResult(_LayoutResult):
+    """What the device replace-mode noise entries return (tk_noise_replace): raw device pointers of context-owned buffers, valid
+    until the next noise call on the context.  input_ids_ptr: uint32 [n_ids] (views(): int32); labels_ptr: int32 [n_ids];
+    selected_ptr: uint8 [n_ids] or None (NOISE_SELECTED).  The offsets are the input's."""
+    STRUCT, PASS = _NoiseReplace, "noise_replace"
+    OUTPUTS = (("input_ids", "<i4", lambda r: (r.n_ids,), np.uint32, False), ("labels", "<i4", lambda r: (r.n_ids,), np.int32, False),
+               ("selected", "|u1", lambda r: (r.n_ids,), np.uint8, True))
+    COUNTS = ("n_docs", "n_ids", "n_selected", "n_masked", "n_random")
+    DICT_COUNTS = ("n_selected", "n_masked", "n_random")
+
+
+class NoiseSpansResult(_LayoutResult):
+    """What the device spans-mode noise entries return (tk_noise_spans): raw device pointers of context-owned buffers, valid until
+    the next noise call on the context.  inputs_ptr / targets_ptr: uint32 [n_inputs] / [n_targets] with input_offsets_ptr /
+    target_offsets_ptr: uint64 [n_docs + 1] (NOISE_SPLIT, else None); joined_ptr: uint32 [n_inputs + n_targets], joined_offsets_ptr:
+    uint64 [n_docs + 1], joined_labels_ptr: int32 [n_inputs + n_targets] (NOISE_JOINED, else None).  views(): ids as int32,
+    offsets as int64."""
+    STRUCT, PASS = _NoiseSpans, "noise_spans"
+    OUTPUTS = (("inputs", "<i4", lambda r: (r.n_inputs,), np.uint32, True), ("input_offsets", "<i8", lambda r: (r.n_docs + 1,), np.uint64, True),
+               ("targets", "<i4", lambda r: (r.n_targets,), np.uint32, True), ("target_offsets", "<i8", lambda r: (r.n_docs + 1,), np.uint64, True),
+               ("joined", "<i4", lambda r: (r.n_inputs + r.n_targets,), np.uint32, True),
+               ("joined_offsets", "<i8", lambda r: (r.n_docs + 1,), np.uint64, True),
+               ("joined_labels", "<i4", lambda r: (r.n_inputs + r.n_targets,), np.int32, True))
+    COUNTS = ("n_docs", "n_selected", "n_runs", "n_runs_dropped", "n_inputs", "n_targets")
+    DICT_COUNTS = ("n_selected", "n_runs", "n_runs_dropped", "n_inputs", "n_targets")
+
+
+_NOISE = {"replace": (_NoiseReplace, NoiseReplaceResult), "spans": (_NoiseSpans, NoiseSpansResult)}
 
 
 class Engine:
@@ -1371,6 +1478,73 @@ class Engine:
         """tk_last_fim_ms: GPU milliseconds of the last FIM pass on this context -- (cut kernel, permute kernel)."""
         ms = (ctypes.c_float * 2)()
         _need("tk_last_fim_ms")(self._h, ctypes.byref(ms))
+        return tuple(float(x) for x in ms)
+
+    # ---- masked-LM and span-corruption rows (tk_noise_replace / tk_noise_spans): a pass over ids with two optional second inputs,
+    # so the entries are its own.  opts: the keywords of _noise_opts (start_q32, mask_q32, random_q32, seed, unit, span_min, span_max,
+    # mask_id, n_sentinels, sentinel_first, final_id, flags, ignore_index)
+    def _noise_device(self, mode, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_word_ids_ptr, d_sel_ptr, stream, opts):
+        S, R = _NOISE[mode]
+        o, st = _noise_opts(**opts), S()
+        self._call("tk_noise_%s_device" % mode, ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr or None), n_docs, n_ids,
+                   ctypes.c_void_p(d_word_ids_ptr or None), ctypes.c_void_p(d_sel_ptr or None), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(st))
+        return R(st)
+
+    def noise_replace_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_word_ids_ptr=0, d_sel_ptr=0, stream=0, **opts):
+        """tk_noise_replace_device: ids resident in HBM -> the ids with a hash-drawn (or, d_sel_ptr: uint8 [n_ids], given) choice of
+        them masked / replaced, and the labels (masked LM; the definition is in include/tekken_hip.h).  d_word_ids_ptr: uint32
+        [n_ids] of the words pass (NOISE_UNIT_WORD).  Returns a NoiseReplaceResult (context-owned device buffers)."""
+        return self._noise_device("replace", d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_word_ids_ptr, d_sel_ptr, stream, opts)
+
+    def noise_spans_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_word_ids_ptr=0, d_sel_ptr=0, stream=0, **opts):
+        """tk_noise_spans_device: the same choice, every chosen run replaced by a sentinel in the inputs and spelt out behind it in
+        the targets (T5 / UL2 span corruption).  flags: NOISE_SPLIT | NOISE_JOINED (| NOISE_DESC).  Returns a NoiseSpansResult."""
+        return self._noise_device("spans", d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_word_ids_ptr, d_sel_ptr, stream, opts)
+
+    def _encode_device_noise(self, mode, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream, opts):
+        S, R = _NOISE[mode]
+        o, st = _noise_opts(**opts), S()
+        d_ids, d_oo, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0)
+        self._call("tk_encode_batch_device_noise_" + mode, ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_docs, n_bytes,
+                   int(add_bos), int(add_eos), int(checks), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(d_ids), ctypes.byref(d_oo),
+                   ctypes.byref(n), ctypes.byref(st))
+        return d_ids.value, d_oo.value, int(n.value), R(st)
+
+    def encode_batch_device_noise_replace(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, checks=0, stream=0, **opts):
+        """tk_encode_batch_device_noise_replace: encode_batch_device, the words pass where unit is NOISE_UNIT_WORD, and the noise pass
+        on the same stream.  Returns (d_ids_ptr, d_out_offs_ptr, n_ids, NoiseReplaceResult), all context-owned."""
+        return self._encode_device_noise("replace", d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream, opts)
+
+    def encode_batch_device_noise_spans(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos=True, add_eos=True, checks=0, stream=0, **opts):
+        """tk_encode_batch_device_noise_spans: the same in front of spans mode.  Returns (d_ids_ptr, d_out_offs_ptr, n_ids,
+        NoiseSpansResult)."""
+        return self._encode_device_noise("spans", d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream, opts)
+
+    def _encode_host_noise(self, mode, data, offs, add_bos, add_eos, validate_utf8, opts):
+        S, R = _NOISE[mode]
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        o, st, res = _noise_opts(**opts), S(), _Result()
+        dbuf = data if len(data) else np.zeros(1, np.uint8)
+        self._call("tk_encode_batch_noise_" + mode, _p(dbuf, ctypes.c_uint8), _p(offs, ctypes.c_uint64), len(offs) - 1, int(add_bos), int(add_eos),
+                   int(validate_utf8), ctypes.byref(o), ctypes.byref(res), ctypes.byref(st))
+        _, out = R.take(st)
+        ids, oo = _take_result(res)
+        return ids, oo, out
+
+    def encode_batch_noise_replace(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, **opts):
+        """tk_encode_batch_noise_replace, host in / host out: (ids uint32 [T] in front of the noise, out_offsets uint64 [D + 1],
+        {"input_ids": uint32 [T], "labels": int32 [T], "selected": uint8 [T] or None, the counts})."""
+        return self._encode_host_noise("replace", data, offs, add_bos, add_eos, validate_utf8, opts)
+
+    def encode_batch_noise_spans(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False, **opts):
+        """tk_encode_batch_noise_spans, host in / host out: (ids, out_offsets, {NoiseSpansResult.OUTPUTS and the counts})."""
+        return self._encode_host_noise("spans", data, offs, add_bos, add_eos, validate_utf8, opts)
+
+    def last_noise_ms(self):
+        """tk_last_noise_ms: GPU milliseconds of the last noise pass on this context -- (selection, counts and scans, fill kernel)."""
+        ms = (ctypes.c_float * 3)()
+        _need("tk_last_noise_ms")(self._h, ctypes.byref(ms))
         return tuple(float(x) for x in ms)
 
     def last_words_ms(self):
@@ -1918,6 +2092,118 @@ class Tekkenizer:
         words = dense(w.word_ids_ptr, WORD_NONE, flags)["ids"]
         out = {"input_ids": d["ids"], "attention_mask": d["mask"], "lengths": d["lengths"], "n_truncated": d["n_truncated"],
                "word_ids": words.to(torch.int64) if i64 else words}
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
+        return out
+
+    def _dense_pair(self, eng, ids_ptr, labels_ptr, offs_ptr, D, N, stream, max_length, padding, truncation_side, padding_side,
+                    pad_to_multiple_of, pad, dtype, ignore_index, return_mask, keep_head=0, keep_tail=0):
+        """The dense pass over ragged ids and over their labels, one after the other with the same options (the labels as int32
+        elements padded with ignore_index, widened here -- which sign-extends), as encode_chat_padded runs it."""
+        import torch
+        flags = (DENSE_FIXED if padding == "max_length" else 0) | (DENSE_TRUNC_LEFT if truncation_side == "left" else 0) \
+            | (DENSE_PAD_LEFT if padding_side == "left" else 0)
+        i64 = dtype == "int64"
+
+        def dense(ptr, pad_value, fl):
+            return eng.dense_from_ids_device(ptr if N else 0, offs_ptr, D, N, max_length, pad_to_multiple_of, pad_value, keep_head, keep_tail,
+                                             fl, stream).tensors(True)
+
+        d = dense(ids_ptr, pad, flags | (DENSE_I64 if i64 else 0) | (DENSE_MASK if return_mask else 0))
+        labels = dense(labels_ptr, int(ignore_index) & 0xFFFFFFFF, flags)["ids"]
+        return {"input_ids": d["ids"], "attention_mask": d["mask"], "labels": labels.to(torch.int64) if i64 else labels, "lengths": d["lengths"],
+                "n_truncated": d["n_truncated"]}
+
+    def _token_id(self, token, default_name):
+        if token is None:
+            return self.get_control_token(default_name)
+        return self.get_control_token(token) if isinstance(token, str) else int(token)
+
+    def encode_batch_mlm(self, docs, mlm_probability=0.15, unit="token", span=(1, 1), mask_token=None, mask_rate=0.8, random_rate=0.1, seed=0,
+                         add_bos=False, add_eos=False, padding=None, max_length=None, truncation_side="right", padding_side="right",
+                         pad_to_multiple_of=None, pad_id=None, dtype="int64", ignore_index=-100, return_mask=True, return_selected=False,
+                         return_tensors="pt"):
+        """Masked-LM rows (tk_encode_batch_device_noise_replace; the definition is in include/tekken_hip.h): HF's
+        DataCollatorForLanguageModeling(mlm=True) (unit "token"), DataCollatorForWholeWordMask (unit "word": the words of
+        encode_batch_with_words) and SpanBERT's contiguous spans (span=(min, max) units), drawn on the device from `seed` -- the
+        epoch.  mlm_probability is the expected fraction of units covered (noise_start_q32); of the chosen ids mask_rate become
+        mask_token (an id, or a control token's name; None: "<unk>" -- Tekken has no [MASK]), random_rate a random ordinary token,
+        the rest stay.  padding None: ragged {"input_ids" int32 [N], "offsets" int64 [D + 1], "labels" int32 [N] (ignore_index where
+        not chosen), "selected" uint8 [N] or None, "n_selected", "n_masked", "n_random"}.  padding "longest" | "max_length": the
+        dense pass over the ids and over the labels as encode_chat_padded runs it -- {"input_ids", "attention_mask", "labels",
+        "lengths", "n_truncated"} and the counts (of the rows before truncation).  torch tensors on the tokenizer's GPU;
+        return_tensors "np": numpy copies."""
+        eng = self._device_engine()
+        ok = unit in _NOISE_UNITS and padding in (None, "longest", "max_length") and truncation_side in ("left", "right") \
+            and padding_side in ("left", "right") and dtype in ("int64", "int32") and return_tensors in ("pt", "np")
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude("encode_batch_mlm", docs, add_bos, add_eos, pad_id if padding else 0, ok,
+                                                                       "unit / padding / side / dtype / return_tensors")
+        import torch
+        D = len(docs)
+        d_ids, d_oo, N, res = eng.encode_batch_device_noise_replace(
+            d_bytes.data_ptr(), d_offs.data_ptr(), D, len(data), add_bos, add_eos, CHECK_OFFSETS, stream,
+            start_q32=noise_start_q32(mlm_probability, span[0], span[1]), mask_q32=fim_q32(mask_rate), random_q32=fim_q32(random_rate), seed=seed,
+            unit=_NOISE_UNITS[unit], span_min=span[0], span_max=span[1], mask_id=self._token_id(mask_token, "<unk>"),
+            flags=NOISE_SELECTED if return_selected else 0, ignore_index=ignore_index)
+        if padding is None:
+            t = res.tensors(True)
+            out = {"input_ids": t["input_ids"], "offsets": _torch_wrap(DeviceView(d_oo, D + 1, "<i8"), True), "labels": t["labels"],
+                   "selected": t["selected"]}
+        else:
+            out = self._dense_pair(eng, res.input_ids_ptr, res.labels_ptr, d_oo, D, N, stream, max_length, padding, truncation_side, padding_side,
+                                   pad_to_multiple_of, pad, dtype, ignore_index, return_mask, int(bool(add_bos)), int(bool(add_eos)))
+        out.update(res._counts())
+        if return_tensors == "np":
+            out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
+        return out
+
+    def encode_batch_span_corruption(self, docs, noise_density=0.15, span=(1, 5), sentinels=None, final=None, unit="token", seed=0,
+                                     form="seq2seq", add_bos=False, add_eos=False, padding=None, max_length=None, truncation_side="right",
+                                     padding_side="right", pad_to_multiple_of=None, pad_id=None, dtype="int64", ignore_index=-100,
+                                     return_mask=True, return_tensors="pt"):
+        """Span-corruption rows (tk_encode_batch_device_noise_spans): T5 / UL2 denoising drawn on the device from `seed`.  Spans of
+        span=(min, max) units (tokens, or words) cover noise_density of each document in expectation; every run of chosen ids is
+        replaced by one sentinel in the inputs, and the targets are the sentinels followed by what they hide, then `final` (an id
+        or a control token's name; None: nothing).  sentinels = (first, count, descending): control ids first, first +- 1, ...;
+        runs beyond `count` in a document stay as they are.  form "seq2seq": {"input_ids", "input_offsets", "labels",
+        "label_offsets"} -- two ragged batches --, or with padding each through the dense pass: {"input_ids", "attention_mask",
+        "labels" (padded with ignore_index), "lengths", "label_lengths"}.  form "joined" (decoder-only): {"input_ids", "offsets",
+        "labels"} with ignore_index on the inputs' part, padded as encode_batch_mlm pads.  The counts n_selected, n_runs,
+        n_runs_dropped, n_inputs, n_targets come with every form.  torch tensors on the tokenizer's GPU; "np": numpy copies."""
+        eng = self._device_engine()
+        ok = unit in _NOISE_UNITS and form in ("seq2seq", "joined") and padding in (None, "longest", "max_length") \
+            and truncation_side in ("left", "right") and padding_side in ("left", "right") and dtype in ("int64", "int32") \
+            and return_tensors in ("pt", "np") and sentinels is not None and len(sentinels) == 3
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude("encode_batch_span_corruption", docs, add_bos, add_eos,
+                                                                       pad_id if padding else 0, ok,
+                                                                       "unit / form / padding / side / dtype / return_tensors / sentinels")
+        import torch
+        D = len(docs)
+        joined = form == "joined"
+        _, _, _, res = eng.encode_batch_device_noise_spans(
+            d_bytes.data_ptr(), d_offs.data_ptr(), D, len(data), add_bos, add_eos, CHECK_OFFSETS, stream,
+            start_q32=noise_start_q32(noise_density, span[0], span[1]), seed=seed, unit=_NOISE_UNITS[unit], span_min=span[0], span_max=span[1],
+            n_sentinels=sentinels[1], sentinel_first=sentinels[0], final_id=JOIN_NONE if final is None else self._token_id(final, "</s>"),
+            flags=(NOISE_JOINED if joined else NOISE_SPLIT) | (NOISE_DESC if sentinels[2] else 0), ignore_index=ignore_index)
+        n_all = res.n_inputs + res.n_targets
+        if padding is None:
+            t = res.tensors(True)
+            out = {"input_ids": t["joined"], "offsets": t["joined_offsets"], "labels": t["joined_labels"]} if joined else \
+                {"input_ids": t["inputs"], "input_offsets": t["input_offsets"], "labels": t["targets"], "label_offsets": t["target_offsets"]}
+        elif joined:
+            out = self._dense_pair(eng, res.joined_ptr, res.joined_labels_ptr, res.joined_offsets_ptr, D, n_all, stream, max_length, padding,
+                                   truncation_side, padding_side, pad_to_multiple_of, pad, dtype, ignore_index, return_mask)
+        else:
+            fl = (DENSE_FIXED if padding == "max_length" else 0) | (DENSE_TRUNC_LEFT if truncation_side == "left" else 0) \
+                | (DENSE_PAD_LEFT if padding_side == "left" else 0)
+            i64 = DENSE_I64 if dtype == "int64" else 0
+            x = eng.dense_from_ids_device(res.inputs_ptr if res.n_inputs else 0, res.input_offsets_ptr, D, res.n_inputs, max_length, pad_to_multiple_of,
+                                          pad, 0, 0, fl | i64 | (DENSE_MASK if return_mask else 0), stream).tensors(True)
+            y = eng.dense_from_ids_device(res.targets_ptr if res.n_targets else 0, res.target_offsets_ptr, D, res.n_targets, max_length,
+                                          pad_to_multiple_of, int(ignore_index) & 0xFFFFFFFF, 0, 0, fl, stream).tensors(True)
+            out = {"input_ids": x["ids"], "attention_mask": x["mask"], "labels": y["ids"].to(torch.int64) if i64 else y["ids"],
+                   "lengths": x["lengths"], "label_lengths": y["lengths"], "n_truncated": x["n_truncated"] + y["n_truncated"]}
+        out.update(res._counts())
         if return_tensors == "np":
             out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
         return out

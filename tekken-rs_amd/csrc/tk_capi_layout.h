@@ -1,7 +1,8 @@
 // tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _rowfit / _regroup / _pair.cpp) share, and
 // only they include: ONE description of the outputs of each result struct, from which tk_free_<pass> and the copy-out of the host
 // entries are made, and the three entries around a pass (ids on the device | text on the device | text on the host) written once.
-// (tk_capi_words.cpp, tk_capi_specials.cpp and tk_capi_fim.cpp take the descriptions of tk_words / tk_specials / tk_fim from here
+// (tk_capi_words.cpp, tk_capi_specials.cpp, tk_capi_fim.cpp and tk_capi_noise.cpp take the descriptions of tk_words / tk_specials /
+// tk_fim / tk_noise_replace / tk_noise_spans from here
 // and have entries of their own: they take the text, or stand in front of encode.)
 #ifndef TK_CAPI_LAYOUT_H
 #define TK_CAPI_LAYOUT_H
@@ -90,6 +91,21 @@ template <class F> static inline void layout_outputs(tk_fim& r, uint64_t esz, ui
     f(r.part_src, r.n_parts * 8, r.part_src != nullptr);
     f(r.cuts, r.n_docs * 16, true);
     f(r.mode, r.n_docs, true);
+}
+template <class F> static inline void layout_outputs(tk_noise_replace& r, uint64_t, uint64_t, F&& f) {
+    f(r.input_ids, r.n_ids * 4, true);
+    f(r.labels, r.n_ids * 4, true);
+    f(r.selected, r.n_ids, r.selected != nullptr);
+}
+template <class F> static inline void layout_outputs(tk_noise_spans& r, uint64_t, uint64_t, F&& f) {
+    const uint64_t offs = (r.n_docs + 1) * 8, nj = (r.n_inputs + r.n_targets) * 4;
+    f(r.inputs, r.n_inputs * 4, r.inputs != nullptr);           // (TK_NOISE_SPLIT: the first four)
+    f(r.input_offsets, offs, r.input_offsets != nullptr);
+    f(r.targets, r.n_targets * 4, r.targets != nullptr);
+    f(r.target_offsets, offs, r.target_offsets != nullptr);
+    f(r.joined, nj, r.joined != nullptr);                       // (TK_NOISE_JOINED: the last three)
+    f(r.joined_offsets, offs, r.joined_offsets != nullptr);
+    f(r.joined_labels, nj, r.joined_labels != nullptr);
 }
 template <class F> static inline void layout_outputs(tk_words& r, uint64_t, uint64_t, F&& f) {
     f(r.word_ids, r.n_ids * 4, true);

@@ -31,9 +31,8 @@ static int split_flags(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* d_doc_
 
 // The words pass over ids and text on the device (the caller holds c->mu; checks: TK_WORDS_CHECK_ALIGNED or 0; the flags of o
 // are known).  Two host waits: the error words and n_words behind the scan, the end of the call.
-static int run_words(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const uint8_t* d_bytes,
-                     const uint64_t* d_doc_offs, uint64_t n_bytes, int checks, const tk_words_opts* o, hipStream_t s, tk_words* out,
-                     uint64_t* bad) {
+int run_words(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const uint8_t* d_bytes,
+              const uint64_t* d_doc_offs, uint64_t n_bytes, int checks, const tk_words_opts* o, hipStream_t s, tk_words* out, uint64_t* bad) {
     WordsBufs& b = c->words;
     for (float& m : b.ms) m = 0.f;
     int rc = token_tables(c);

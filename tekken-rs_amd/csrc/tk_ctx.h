@@ -157,6 +157,16 @@ struct FimBufs {
     Event ev[3];                   // the stages of the last FIM call (tk_last_fim_ms), created at the first one
     float ms[2] = {0.f, 0.f};      // cut kernel | permute kernel
 };
+// the noise pass (tk_noise.hip): replace mode's ids, labels and selected bytes (spans mode: its work flags); spans mode's five
+// outputs (the two split offsets are the document scans themselves) and joined_offsets; the statistics words; the work arrays
+// (the tiles' counts and their scans, the documents' counts in front of them, kept ids and lengths, the scan workspace); the host
+// entries' copies of a small batch's text and offsets
+struct NoiseBufs {
+    DevBuf ids, lab, sel, inputs, targets, joined, jlab, joffs, in_off, tg_off, stat;
+    DevBuf tsel, trs, tS, tR, dsel0, drs0, SB, RB, KS, in_len, tg_len, bsum, text, toffs;
+    Event ev[4];                   // the stages of the last noise call (tk_last_noise_ms), created at the first one
+    float ms[3] = {0.f, 0.f, 0.f}; // selection | counts and scans | fill kernel
+};
 
 struct tk_ctx {
     int device = 0;
@@ -192,6 +202,7 @@ struct tk_ctx {
     WordsBufs words;
     SpecialsBufs specials;
     FimBufs fim;
+    NoiseBufs noise;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -309,6 +320,10 @@ int join_check_args(tk_ctx* c, uint64_t n_parts, uint64_t n_convs, const tk_join
 int run_join(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t P, uint64_t n_ids, const uint32_t* d_ctrl,
              const uint32_t* d_pflags, const uint64_t* d_conv, uint64_t C, bool check_parts, const tk_join_opts* o, hipStream_t s,
              tk_join* out);
+// tk_capi_words.cpp: the words pass over ids and text on the device (tk_capi_noise.cpp runs it between encode and the noise pass
+// under one lock); checks: TK_WORDS_CHECK_ALIGNED or 0
+int run_words(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const uint8_t* d_bytes,
+              const uint64_t* d_doc_offs, uint64_t n_bytes, int checks, const tk_words_opts* o, hipStream_t s, tk_words* out, uint64_t* bad);
 // tk_capi_decode.cpp: the decode kernels' tables (also what the spans kernel reads), built at the first call that needs them
 int token_tables(tk_ctx* c);
 template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // ... as the decode and spans kernels take them

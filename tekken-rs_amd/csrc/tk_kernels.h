@@ -493,6 +493,55 @@ struct TkFimArgs {
 hipError_t tk_launch_fim_cut(const TkFimArgs& a, int unit_bytes, hipStream_t s);       // everything but out_units
 hipError_t tk_launch_fim_permute(const TkFimArgs& a, int unit_bytes, hipStream_t s);   // out_units (behind tk_launch_fim_cut); no unit: nothing is launched
 
+// ---- masked-LM and span-corruption rows: a noise pass over encoded ids (tk_noise.hip) ----
+#define TKN_TILE 4096u         /* input ids of a block's tile of the noise kernels: 4 rounds of 4 a thread */
+#define TKN_ROUND 1024u        /* ids of one round of a block: TKY_BLOCK threads, 4 consecutive ids each */
+#define TKN_SEED_BASE 0x4E4F4900u
+#define TKN_SLOTS 64u          /* copies of every counter of a call: a block adds to copy blockIdx % TKN_SLOTS, the host adds them up */
+#define TKN_STATS 4u           /* counters of a copy */
+#define TKN_STAT_DROP (TKN_SLOTS * TKN_STATS)   /* the word behind the copies: a document drops a run */
+struct TkNoiseArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const uint64_t* offs;      // [n_docs + 1]
+    const uint32_t* word_ids;  // [n_ids] or NULL (needed by TK_NOISE_UNIT_WORD)
+    const uint8_t* sel;        // [n_ids] the caller's choice, or NULL: drawn
+    uint64_t n_docs, n_ids;
+    uint32_t s[4];             // s_k = h(seed, TKN_SEED_BASE + k)
+    uint64_t start_q32, mask_q32, mask_random_q32;   // (the third: mask_q32 + random_q32)
+    uint32_t unit, span_min, span_max;
+    uint32_t mask_id, num_special, n_ordinary;   // S0; V - S0
+    int32_t ignore;            // ignore_index
+    // replace mode
+    uint32_t* out_ids;         // [n_ids]
+    int32_t* labels;           // [n_ids]
+    uint8_t* selected;         // [n_ids]: replace mode: the output or NULL; spans mode: selected(i) in front of the drop (a work array)
+    // spans mode
+    uint32_t n_sentinels, sentinel_first, desc, final_id, split, joined;
+    uint64_t n_tiles;          // ceil(n_ids / TKN_TILE)
+    uint32_t *tile_sel, *tile_rs;          // [n_tiles] selected ids | run starts of the tile
+    const uint64_t *tile_S, *tile_R;       // [n_tiles + 1] their exclusive scans
+    uint32_t *doc_sel0, *doc_rs0;          // [n_docs] of a document that starts inside a tile: the tile's selected ids | run starts in front of it (else 0: zeroed by the caller)
+    uint64_t *SB, *RB;         // [n_docs + 1] selected ids | run starts in front of the document
+    uint32_t* KS;              // [n_docs] the document's selected ids behind the drop
+    uint32_t *in_len, *tg_len; // [n_docs] the ids of inputs_d | targets_d
+    const uint64_t *in_off, *tg_off;       // [n_docs + 1] their exclusive scans: input_offsets | target_offsets
+    uint64_t n_inputs, n_targets;          // known behind the host read: nothing is written at or beyond them
+    uint32_t *inputs, *targets, *joined_ids;
+    uint64_t* joined_offs;     // [n_docs + 1]
+    int32_t* joined_labels;
+    // TKN_SLOTS copies of TKN_STATS counters -- replace: [0] n_selected, [1] n_masked, [2] n_random; spans: [0] n_selected behind
+    // the drop, [1] n_runs, [2] n_runs_dropped -- and [TKN_STAT_DROP]: not 0 where a document drops a run (tk_launch_noise_docs;
+    // tk_launch_noise_drop returns at once where it is 0).  Zeroed by the caller
+    unsigned long long* stat;
+};
+hipError_t tk_launch_noise_replace(const TkNoiseArgs& a, hipStream_t s);   // out_ids, labels, selected, stat[0..2]; no id: nothing is launched
+hipError_t tk_launch_noise_select(const TkNoiseArgs& a, hipStream_t s);    // spans mode: selected
+hipError_t tk_launch_noise_count(const TkNoiseArgs& a, hipStream_t s);     // tile_sel, tile_rs, doc_sel0, doc_rs0
+hipError_t tk_launch_noise_docs(const TkNoiseArgs& a, hipStream_t s);      // SB, RB, KS without a drop, stat[TKN_STAT_DROP] (behind the two tile scans)
+hipError_t tk_launch_noise_drop(const TkNoiseArgs& a, hipStream_t s);      // KS of the documents with a dropped run
+hipError_t tk_launch_noise_lens(const TkNoiseArgs& a, hipStream_t s);      // in_len, tg_len, stat[0..2]
+hipError_t tk_launch_noise_fill(const TkNoiseArgs& a, hipStream_t s);      // the outputs (behind the two document scans and the host read)
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
