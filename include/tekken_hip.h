@@ -427,6 +427,102 @@ int tk_encode_batch_window(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* do
                            int validate_utf8, const tk_window_opts* opts, tk_window* out);
 void tk_free_window(tk_window* out);
 
+/* ---- boundary-aware token-budget chunks: long documents cut at breaks of the text (no reference equivalent: pad_id(),
+ * src/tekkenizer.rs:304, is all the reference has; the definition is this project's own -- what LangChain's
+ * RecursiveCharacterTextSplitter.from_tiktoken_encoder, LlamaIndex's SentenceSplitter and semchunk do by calling a tokenizer over
+ * and over on the host) ----
+ * The window pass cuts every `step` ids wherever that falls; this pass cuts a document of more than max_length ids at the strongest
+ * break of the text that a chunk of at least min_length body ids can end at.  Input: the ragged ids R_d = ids[oo[d] : oo[d+1]],
+ * n_d = len(R_d), d < D; one LEVEL byte per id; optionally the spans buffer of tk_token_spans_device (2 * n_ids uint32); options
+ * max_length T (required, > 0), min_length m, overlap o, multiple_of (0 = none), pad_id, keep_head h, keep_tail t, levels (a bit
+ * mask, for tk_chunk_levels_device and the entries that encode first) and the flags below.  Let c = T - h - t; c >= 1 and
+ * 0 <= o < m <= c are required.
+ *   Levels.  lev[i] (uint8) is the strength of the break in front of id i: 0 NONE (inside a character), 1 TOKEN, 2 WORD, 3 SENTENCE,
+ *   4 LINE, 5 PARAGRAPH (a byte above 5 reads as 5).  Either the caller gives the bytes (how a syntax-aware choice comes in, as with
+ *   the FIM cuts), or tk_chunk_levels_device makes them from text and spans, a total function of bytes only: with text the bytes of
+ *   document d, len their number, p the span start of id i and WS the six ASCII bytes 0x09 .. 0x0D and 0x20, first match wins:
+ *     1. p >= len or p == 0: TOKEN.
+ *     2. (text[p] & 0xC0) == 0x80: NONE.
+ *     3. Walk back from p over WS bytes to q: the walk ends in front of the first byte that is not WS, at byte 0, or after 16 bytes
+ *        -- then it was stopped by the bound, whatever lies further in front.  nl = the 0x0A among text[q : p]: nl >= 2 PARAGRAPH,
+ *        nl == 1 LINE.
+ *     4. gap = (q < p) or text[p] in WS.  If the walk was not stopped by the bound and q > 0: SENTENCE if gap and text[q - 1] is one
+ *        of . ! ?; SENTENCE also if q >= 3 and text[q - 3 : q] is one of E3 80 82, EF BC 81, EF BC 9F (the ideographic full stop,
+ *        the fullwidth ! and ?; no white space needed).
+ *     5. Otherwise WORD if gap, else TOKEN.
+ *   Then the mask: a level in 2 .. 5 whose bit 1 << level is not in `levels` is demoted to the highest enabled level below it, or
+ *   to TOKEN; NONE and TOKEN cannot be disabled.  No read leaves text[0 : len].
+ *   Walk, per document.
+ *     1. n_d <= T gives ONE chunk: R_d as it lies (empty documents too, as rule 2 of the window pass).
+ *     2. Otherwise the body is B = R_d[h : n_d - t], b = n_d - h - t, and L(j) = lev[oo[d] + h + j].  Start at a = 0.
+ *     3. b - a <= c: the last chunk is [a, b).  Otherwise the candidates are the j in [a + m, a + c], best = max L(j) over them, the
+ *        cut e is the LARGEST candidate with L(e) == best, and the chunk is [a, e) with cut_level = best.
+ *     4. The next start is the smallest j in [max(a + 1, e - o), e) with L(j) >= WORD; if there is none, the smallest there with
+ *        L(j) >= TOKEN; if there is none, e.  Go to 3.
+ *     5. Row k of the document is R_d[:h] + B[a_k : e_k] + R_d[n_d - t :].
+ *   It follows that a_k < a_{k+1} <= e_k < e_{k+1}, e_k - a_{k+1} <= o, m <= e_k - a_k <= c for all but the last chunk, a_0 = 0,
+ *   e_last = b and w_d <= 1 + ceil((b - c) / (m - o)); with every level equal the chunks are the window pass's windows at
+ *   stride = o, for any valid m.
+ *   Outputs.  input_ids[W, L], mask, lengths, window_doc, window_start = min(h + a_k, n_d), doc_windows and spans[W, L, 2] (with
+ *   TK_CHUNK_SPANS) mean exactly what they mean in tk_window, and so do the row-length rules (TK_CHUNK_FIXED, multiple_of, int32 or
+ *   int64 with TK_CHUNK_I64, TK_CHUNK_MASK).  cut_level[W] (uint8): the level of the cut that ended the chunk, TK_CHUNK_CUT_LAST
+ *   (255) for a document's last chunk.  chunk_bytes[W, 2] (uint32, with TK_CHUNK_BYTES, which needs spans): the span start of the
+ *   chunk's first body id and the span end of its last; for an unsplit document from its first id's start to its last id's end,
+ *   (0, 0) for one without ids.  level_counts (uint64[6]): the cuts made at every level -- the quality figure: a high count at
+ *   NONE or TOKEN says min_length is too close to max_length.  Counts: n_docs, n_windows = W, row_len = L, n_split.
+ *   TK_ERR_INVALID_ARG, nothing written, an earlier chunk result stays readable: the window pass's list with stride read as
+ *   overlap; m == 0, m > c or o >= m; a levels bit outside 2 .. 5; TK_CHUNK_BYTES or TK_CHUNK_SPANS without a spans buffer; ids
+ *   without a level buffer in the from-ids entry.  A failed allocation is TK_ERR_RUNTIME.  D == 0 is valid and gives W == 0.
+ * A separate pass behind the unchanged encode pipeline (csrc/tk_chunk.hip): the levels kernel; the walk, run twice (the counts, then
+ * -- behind their scan and ONE small read that sizes the tensors -- the windows' records); the fill kernel, the window pass's with
+ * one more load a row.  One wait ends the call. */
+#define TK_CHUNK_FIXED 1
+#define TK_CHUNK_I64 2
+#define TK_CHUNK_MASK 4
+#define TK_CHUNK_SPANS 8
+#define TK_CHUNK_BYTES 16
+#define TK_CHUNK_LEVEL_NONE 0
+#define TK_CHUNK_LEVEL_TOKEN 1
+#define TK_CHUNK_LEVEL_WORD 2
+#define TK_CHUNK_LEVEL_SENTENCE 3
+#define TK_CHUNK_LEVEL_LINE 4
+#define TK_CHUNK_LEVEL_PARAGRAPH 5
+#define TK_CHUNK_LEVELS_ALL 60
+#define TK_CHUNK_CUT_LAST 255
+typedef struct tk_chunk_opts { uint32_t max_length, min_length, overlap, multiple_of, pad_id, keep_head, keep_tail, levels, flags; } tk_chunk_opts;
+typedef struct tk_chunk { void* input_ids; uint8_t* mask; uint32_t *lengths, *window_doc, *window_start; uint64_t* doc_windows;
+                          uint32_t* spans; uint8_t* cut_level; uint32_t* chunk_bytes; uint64_t* level_counts;
+                          uint64_t n_docs, n_windows, row_len, n_split; } tk_chunk;
+/* The level bytes of ids whose spans are on the device (d_spans: 2 * n_ids uint32 as tk_token_spans_device returns them;
+ * d_id_offsets as below; d_bytes / d_doc_offsets: the text the ids were encoded from) under the mask `levels` (bits 1 << 2 ..
+ * 1 << 5; another bit: TK_ERR_INVALID_ARG) -> *d_levels, n_ids uint8 in a device buffer owned by the context, valid until the next
+ * call that makes levels on it. */
+int tk_chunk_levels_device(tk_ctx* ctx, const void* d_spans, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                           const void* d_bytes, const void* d_doc_offsets, uint64_t n_bytes, uint32_t levels, void* hip_stream,
+                           void** d_levels);
+/* ids and their level bytes already on the device (d_id_offsets: n_docs + 1 uint64, [0] = 0, non-decreasing, [n_docs] = n_ids -- NOT
+ * checked, as in tk_window_from_ids_device: anything else is out-of-bounds indexing on the device) -> chunks.  d_levels: n_ids
+ * uint8, the caller's or tk_chunk_levels_device's; d_spans: NULL without TK_CHUNK_SPANS and TK_CHUNK_BYTES; opts->levels is checked
+ * and not used.  out's buffers are device buffers owned by the context, valid until the next chunk call on it, and SEPARATE from
+ * every other pass's outputs.  The work is enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_chunk_from_ids_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                             const void* d_levels, const void* d_spans, const tk_chunk_opts* opts, void* hip_stream, tk_chunk* out);
+/* tk_encode_batch_device_ex + the spans pass (into a buffer of the chunk pass: tk_token_spans_device's result stays as it is) + the
+ * levels + the chunk pass on the same stream.  keep_head / keep_tail of opts are ignored and set from add_bos / add_eos; checks:
+ * TK_CHECK_OFFSETS / TK_CHECK_UTF8 as in tk_encode_batch_device_dense; the ragged outputs (*d_ids / *d_out_offsets / *n_ids as
+ * tk_encode_batch_device) are returned as well. */
+int tk_encode_batch_device_chunk(tk_ctx* ctx, const void* d_bytes, const void* d_doc_offsets, uint64_t n_docs, uint64_t n_bytes,
+                                 int add_bos, int add_eos, int checks, const tk_chunk_opts* opts, void* hip_stream,
+                                 void** d_ids, void** d_out_offsets, uint64_t* n_ids, tk_chunk* out);
+/* Host in / host out: tk_encode_batch + the same passes (batches of the one-launch small path included).  out's buffers are pinned
+ * host memory, released with tk_free_chunk (an unselected output is NULL). */
+int tk_encode_batch_chunk(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs, int add_bos, int add_eos,
+                          int validate_utf8, const tk_chunk_opts* opts, tk_chunk* out);
+void tk_free_chunk(tk_chunk* out);
+/* Milliseconds of the stages of the last chunk call on the context: [0] the levels kernel (of the last call that made levels),
+ * [1] the two walks and the scan, [2] the fill kernel. */
+void tk_last_chunk_ms(const tk_ctx* ctx, float ms[3]);
+
 /* ---- chat batches: text parts joined with control ids, plus labels (no reference equivalent: the reference never makes a
  * control token out of text -- "[INST]" in the input stays plain text -- and get_control_token, src/tekkenizer.rs:331-341, only
  * hands out the id) ----

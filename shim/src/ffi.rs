@@ -170,6 +170,50 @@ pub struct TkWindow {
     pub row_len: u64,
     pub n_split: u64,
 }
+// boundary-aware token-budget chunks (tk_chunk_opts.flags, the level bytes, tk_chunk_opts.levels; include/tekken_hip.h has the
+// definition)
+pub const TK_CHUNK_FIXED: u32 = 1;
+pub const TK_CHUNK_I64: u32 = 2;
+pub const TK_CHUNK_MASK: u32 = 4;
+pub const TK_CHUNK_SPANS: u32 = 8;
+pub const TK_CHUNK_BYTES: u32 = 16;
+pub const TK_CHUNK_LEVEL_NONE: u8 = 0;
+pub const TK_CHUNK_LEVEL_TOKEN: u8 = 1;
+pub const TK_CHUNK_LEVEL_WORD: u8 = 2;
+pub const TK_CHUNK_LEVEL_SENTENCE: u8 = 3;
+pub const TK_CHUNK_LEVEL_LINE: u8 = 4;
+pub const TK_CHUNK_LEVEL_PARAGRAPH: u8 = 5;
+pub const TK_CHUNK_LEVELS_ALL: u32 = 60;
+pub const TK_CHUNK_CUT_LAST: u8 = 255;
+#[repr(C)]
+pub struct TkChunkOpts {
+    pub max_length: u32,
+    pub min_length: u32,
+    pub overlap: u32,
+    pub multiple_of: u32,
+    pub pad_id: u32,
+    pub keep_head: u32,
+    pub keep_tail: u32,
+    pub levels: u32,
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkChunk {
+    pub input_ids: *mut c_void,
+    pub mask: *mut u8,
+    pub lengths: *mut u32,
+    pub window_doc: *mut u32,
+    pub window_start: *mut u32,
+    pub doc_windows: *mut u64,
+    pub spans: *mut u32,
+    pub cut_level: *mut u8,
+    pub chunk_bytes: *mut u32,
+    pub level_counts: *mut u64,
+    pub n_docs: u64,
+    pub n_windows: u64,
+    pub row_len: u64,
+    pub n_split: u64,
+}
 // chat batches: parts joined with control ids, plus labels (include/tekken_hip.h has the definition)
 pub const TK_CHECK_PARTS: c_int = 16;
 pub const TK_JOIN_NONE: u32 = 0xFFFF_FFFF;
@@ -472,6 +516,21 @@ extern "C" {
     pub fn tk_encode_batch_window(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
                                   validate_utf8: c_int, opts: *const TkWindowOpts, out: *mut TkWindow) -> c_int;
     pub fn tk_free_window(out: *mut TkWindow);
+    // boundary-aware chunks: the level byte of every id from text and spans; long documents cut at the strongest break a chunk can
+    // end at (+ cut_level, chunk_bytes, level_counts), fused with encode, host form; the stage times of the last call
+    pub fn tk_chunk_levels_device(ctx: *mut TkCtx, d_spans: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                  d_bytes: *const c_void, d_doc_offsets: *const c_void, n_bytes: u64, levels: u32, hip_stream: *mut c_void,
+                                  d_levels: *mut *mut c_void) -> c_int;
+    pub fn tk_chunk_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                    d_levels: *const c_void, d_spans: *const c_void, opts: *const TkChunkOpts, hip_stream: *mut c_void,
+                                    out: *mut TkChunk) -> c_int;
+    pub fn tk_encode_batch_device_chunk(ctx: *mut TkCtx, d_bytes: *const c_void, d_doc_offsets: *const c_void, n_docs: u64, n_bytes: u64,
+                                        add_bos: c_int, add_eos: c_int, checks: c_int, opts: *const TkChunkOpts, hip_stream: *mut c_void,
+                                        d_ids: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_ids: *mut u64, out: *mut TkChunk) -> c_int;
+    pub fn tk_encode_batch_chunk(ctx: *mut TkCtx, bytes: *const u8, doc_offsets: *const u64, n_docs: u64, add_bos: c_int, add_eos: c_int,
+                                 validate_utf8: c_int, opts: *const TkChunkOpts, out: *mut TkChunk) -> c_int;
+    pub fn tk_free_chunk(out: *mut TkChunk);
+    pub fn tk_last_chunk_ms(ctx: *const TkCtx, ms: *mut f32);
     // sentence-pair rows: the ids of 2P parts (first text, second text) as rows head + A + sep + B + tail, cut or split into
     // overlapping windows (+ mask, type ids, sequence ids, spans, the mapping back to the pairs), fused with encode, host form
     pub fn tk_pair_from_ids_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_parts: u64, n_ids: u64,

@@ -34,6 +34,11 @@ _UNITS = {"byte": UNIT_BYTE, "char": UNIT_CHAR, "utf16": UNIT_UTF16}   # the off
 DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
 SEQPACK_I64, SEQPACK_POSITIONS, SEQPACK_SEGMENTS, SEQPACK_CU_SEQLENS, SEQPACK_DROP_LAST = 1, 2, 4, 8, 16   # tk_seqpack_opts.flags (the packed entries)
 WINDOW_FIXED, WINDOW_I64, WINDOW_MASK, WINDOW_SPANS = 1, 2, 4, 8   # tk_window_opts.flags (the window entries)
+CHUNK_FIXED, CHUNK_I64, CHUNK_MASK, CHUNK_SPANS, CHUNK_BYTES = 1, 2, 4, 8, 16   # tk_chunk_opts.flags (the chunk entries)
+CHUNK_LEVEL_NONE, CHUNK_LEVEL_TOKEN, CHUNK_LEVEL_WORD, CHUNK_LEVEL_SENTENCE, CHUNK_LEVEL_LINE, CHUNK_LEVEL_PARAGRAPH = 0, 1, 2, 3, 4, 5   # the level bytes
+CHUNK_LEVELS_ALL = 60   # tk_chunk_opts.levels: bit 1 << level of every level that can be disabled
+CHUNK_CUT_LAST = 255   # cut_level: a document's last chunk
+_LEVELS = {"word": CHUNK_LEVEL_WORD, "sentence": CHUNK_LEVEL_SENTENCE, "line": CHUNK_LEVEL_LINE, "paragraph": CHUNK_LEVEL_PARAGRAPH}   # the levels keyword of encode_batch_chunks
 PAIR_LONGEST_FIRST, PAIR_ONLY_FIRST, PAIR_ONLY_SECOND = 0, 1, 2   # tk_pair_opts.strategy
 PAIR_FIXED, PAIR_I64, PAIR_MASK, PAIR_SPANS, PAIR_TYPE_IDS, PAIR_SEQUENCE_IDS, PAIR_OVERFLOW = 1, 2, 4, 8, 16, 32, 64   # tk_pair_opts.flags (the pair entries)
 PAIR_SEQ_NONE = 255   # sequence_ids: a fixed id or a pad (HF's None)
@@ -128,6 +133,19 @@ class _WindowOpts(ctypes.Structure):
 class _Window(ctypes.Structure):
     _fields_ = [("input_ids", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("window_doc", ctypes.c_void_p),
                 ("window_start", ctypes.c_void_p), ("doc_windows", ctypes.c_void_p), ("spans", ctypes.c_void_p),
+                ("n_docs", ctypes.c_uint64), ("n_windows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_split", ctypes.c_uint64)]
+
+
+class _ChunkOpts(ctypes.Structure):
+    _fields_ = [("max_length", ctypes.c_uint32), ("min_length", ctypes.c_uint32), ("overlap", ctypes.c_uint32), ("multiple_of", ctypes.c_uint32),
+                ("pad_id", ctypes.c_uint32), ("keep_head", ctypes.c_uint32), ("keep_tail", ctypes.c_uint32), ("levels", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
+class _Chunk(ctypes.Structure):
+    _fields_ = [("input_ids", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("window_doc", ctypes.c_void_p),
+                ("window_start", ctypes.c_void_p), ("doc_windows", ctypes.c_void_p), ("spans", ctypes.c_void_p),
+                ("cut_level", ctypes.c_void_p), ("chunk_bytes", ctypes.c_void_p), ("level_counts", ctypes.c_void_p),
                 ("n_docs", ctypes.c_uint64), ("n_windows", ctypes.c_uint64), ("row_len", ctypes.c_uint64), ("n_split", ctypes.c_uint64)]
 
 
@@ -424,7 +442,7 @@ def lib():
     # library built before a pass still loads through TK_HIP_LIB
     u64, ci, vpp = ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(vp)
     for R, opts, extra in ((DenseResult, _DenseOpts, []), (SeqpackResult, _SeqpackOpts, []), (WindowResult, _WindowOpts, [vp]),
-                           (RowfitResult, _RowfitOpts, [vp]), (RegroupResult, _RegroupOpts, [vp, vp])):
+                           (RowfitResult, _RowfitOpts, [vp]), (RegroupResult, _RegroupOpts, [vp, vp]), (ChunkResult, _ChunkOpts, [vp, vp])):
         if not hasattr(L, "tk_%s_from_ids_device" % R.PASS):
             continue
         op, rp = ctypes.POINTER(opts), ctypes.POINTER(R.STRUCT)
@@ -433,6 +451,11 @@ def lib():
                            ("tk_encode_batch_%s", [vp, u8p, u64p, u64, ci, ci, ci, op, rp]), ("tk_free_%s", [rp])):
             fn = getattr(L, name % R.PASS)
             fn.restype, fn.argtypes = (None if name == "tk_free_%s" else ci), args
+    if hasattr(L, "tk_chunk_levels_device"):   # (boundary-aware chunks: libraries built before them still load through TK_HIP_LIB)
+        L.tk_chunk_levels_device.restype = ci
+        L.tk_chunk_levels_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, u64, ctypes.c_uint32, vp, vpp]
+        L.tk_last_chunk_ms.restype = None
+        L.tk_last_chunk_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 3)]
     if hasattr(L, "tk_pair_from_ids_device"):   # (sentence-pair rows: libraries built before them still load through TK_HIP_LIB)
         pop, pp = ctypes.POINTER(_PairOpts), ctypes.POINTER(_Pair)
         L.tk_pair_from_ids_device.restype = ci
@@ -709,6 +732,26 @@ class WindowResult(_LayoutResult):
                ("window_start", "<i4", lambda r: (r.n_windows,), np.uint32, False),
                ("doc_windows", "<i8", lambda r: (r.n_docs + 1,), np.uint64, False),
                ("spans", "<i4", lambda r: (r.n_windows, r.row_len, 2), np.uint32, True))
+    COUNTS = ("n_docs", "n_windows", "row_len", "n_split")
+    DICT_COUNTS = ("n_windows", "n_split")
+
+
+def _chunk_opts(max_length, min_length, overlap=0, multiple_of=0, pad_id=0, keep_head=0, keep_tail=0, levels=CHUNK_LEVELS_ALL, flags=0):
+    return _ChunkOpts(int(max_length or 0), int(min_length or 0), int(overlap or 0), int(multiple_of or 0), int(pad_id), int(keep_head),
+                      int(keep_tail), int(levels), int(flags))
+
+
+class ChunkResult(_LayoutResult):
+    """What the device chunk entries return (tk_chunk): raw device pointers of context-owned buffers, valid until the next chunk
+    call on the context.  The first seven outputs are WindowResult's; cut_level_ptr: uint8 [n_windows] (CHUNK_CUT_LAST for a
+    document's last chunk); chunk_bytes_ptr: uint32 [n_windows, 2] or None (with CHUNK_BYTES); level_counts_ptr: uint64 [6], the cuts
+    made at every level.
+    views(): WindowResult's seven, then cut_level as uint8 [n_windows], chunk_bytes as int32 [n_windows, 2] or None, level_counts as
+    int64 [6]."""
+    STRUCT, PASS, I64 = _Chunk, "chunk", CHUNK_I64
+    OUTPUTS = WindowResult.OUTPUTS + (("cut_level", "|u1", lambda r: (r.n_windows,), np.uint8, False),
+                                      ("chunk_bytes", "<i4", lambda r: (r.n_windows, 2), np.uint32, True),
+                                      ("level_counts", "<i8", lambda r: (6,), np.uint64, False))
     COUNTS = ("n_docs", "n_windows", "row_len", "n_split")
     DICT_COUNTS = ("n_windows", "n_split")
 
@@ -1599,6 +1642,46 @@ class Engine:
         o = _window_opts(max_length, stride, multiple_of, pad_id, 0, 0, flags)
         return self._encode_host(WindowResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
 
+    def chunk_levels_device(self, d_spans_ptr, d_id_offs_ptr, n_docs, n_ids, d_bytes_ptr, d_offs_ptr, n_bytes, levels=CHUNK_LEVELS_ALL, stream=0):
+        """tk_chunk_levels_device: the level byte of every id (the strength of the break of the text in front of it, CHUNK_LEVEL_*)
+        from its span and the text, under the mask `levels`; the rules are in include/tekken_hip.h.  Returns the device pointer of
+        n_ids uint8 (context-owned, valid until the next call that makes levels)."""
+        d_lev = ctypes.c_void_p()
+        self._call("tk_chunk_levels_device", ctypes.c_void_p(d_spans_ptr or None), ctypes.c_void_p(d_id_offs_ptr), n_docs, n_ids,
+                   ctypes.c_void_p(d_bytes_ptr or None), ctypes.c_void_p(d_offs_ptr), n_bytes, int(levels), ctypes.c_void_p(stream), ctypes.byref(d_lev))
+        return d_lev.value
+
+    def chunk_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, d_levels_ptr, max_length, min_length, overlap=0, multiple_of=0,
+                              pad_id=0, keep_head=0, keep_tail=0, flags=0, d_spans_ptr=0, stream=0):
+        """tk_chunk_from_ids_device: ragged ids and their level bytes resident in HBM -> chunks [n_windows, row_len] cut at the
+        strongest break a chunk of min_length .. max_length - keep_head - keep_tail body ids can end at (+ mask with CHUNK_MASK,
+        spans with CHUNK_SPANS and chunk_bytes with CHUNK_BYTES from d_spans_ptr, lengths, window_doc, window_start, doc_windows,
+        cut_level, level_counts); the definition is in include/tekken_hip.h.  Returns a ChunkResult (context-owned device buffers,
+        apart from every other output)."""
+        o = _chunk_opts(max_length, min_length, overlap, multiple_of, pad_id, keep_head, keep_tail, CHUNK_LEVELS_ALL, flags)
+        return self._from_ids_device(ChunkResult, o, flags, d_ids_ptr, d_id_offs_ptr, n_docs, n_ids, (d_levels_ptr, d_spans_ptr), stream)
+
+    def encode_batch_device_chunk(self, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, max_length, min_length, overlap=0, add_bos=True, add_eos=True,
+                                  multiple_of=0, pad_id=0, levels=CHUNK_LEVELS_ALL, flags=0, checks=0, stream=0):
+        """tk_encode_batch_device_chunk: encode_batch_device + the spans pass (into a buffer of the chunk pass) + the levels + the
+        chunk pass on the same stream; every chunk repeats BOS / EOS.  Returns (d_ids_ptr, d_out_offs_ptr, n_ids, ChunkResult), all
+        context-owned."""
+        o = _chunk_opts(max_length, min_length, overlap, multiple_of, pad_id, 0, 0, levels, flags)
+        return self._encode_device(ChunkResult, o, flags, d_bytes_ptr, d_offs_ptr, n_docs, n_bytes, add_bos, add_eos, checks, stream)
+
+    def encode_batch_chunk(self, data, offs, max_length, min_length, overlap=0, add_bos=True, add_eos=True, validate_utf8=False, multiple_of=0,
+                           pad_id=0, levels=CHUNK_LEVELS_ALL, flags=0):
+        """tk_encode_batch_chunk, host in / host out: a dict of numpy arrays (encode_batch_window's, cut_level uint8 [n_windows],
+        chunk_bytes uint32 [n_windows, 2] or None, level_counts uint64 [6]) and the counts n_windows, n_split."""
+        o = _chunk_opts(max_length, min_length, overlap, multiple_of, pad_id, 0, 0, levels, flags)
+        return self._encode_host(ChunkResult, o, flags, data, offs, add_bos, add_eos, validate_utf8)[1]
+
+    def last_chunk_ms(self):
+        """tk_last_chunk_ms: GPU milliseconds of the last chunk pass -- (levels kernel, the two walks and the scan, fill kernel)."""
+        ms = (ctypes.c_float * 3)()
+        _need("tk_last_chunk_ms")(self._h, ctypes.byref(ms))
+        return tuple(float(x) for x in ms)
+
     def pair_from_ids_device(self, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, max_length, strategy=PAIR_LONGEST_FIRST, stride=0, max_fixed=0,
                              multiple_of=0, pad_id=0, head=(), sep=(), tail=(), flags=0, d_spans_ptr=0, stream=0):
         """tk_pair_from_ids_device: the ragged ids of 2P parts resident in HBM (part 2p the first text, part 2p + 1 the second) ->
@@ -2344,6 +2427,55 @@ class Tekkenizer:
                "n_windows": t["n_windows"], "n_split": t["n_split"]}
         if return_tensors == "np":
             out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
+        return out
+
+    def encode_batch_chunks(self, docs, max_length, overlap=0, min_length=None, levels=("word", "sentence", "line", "paragraph"),
+                            add_bos=False, add_eos=False, padding="max_length", pad_to_multiple_of=None, pad_id=None, dtype="int64",
+                            return_attention_mask=True, return_offsets_mapping=False, return_tensors="pt", copy=True, return_text=False):
+        """Token-budget chunks that respect the text's structure (tk_encode_batch_device_chunk / tk_encode_batch_chunk; the
+        definition is in include/tekken_hip.h): a document of more than max_length ids is cut into chunks of at most max_length
+        ids, each with its own BOS / EOS, and every cut is made at the strongest break -- paragraph, line, sentence, word, token --
+        that a chunk of at least min_length text ids can end at; the next chunk starts up to `overlap` ids earlier, at a word.  A
+        shorter document is one chunk.  min_length None: max(c // 2, overlap + 1) with c = max_length - BOS - EOS.  levels: the
+        kinds of break that count (one left out is demoted to the next one below, at last to a token break).
+        The keys of encode_batch_windows, and "cut_level": uint8 [W] the CHUNK_LEVEL_* of the cut behind every chunk
+        (CHUNK_CUT_LAST for a document's last), "chunk_bytes": int32 [W, 2] the byte range of the document that the chunk's text
+        ids cover, "level_counts": int64 [6] the cuts made at every level (many at NONE or TOKEN: min_length is too close to
+        max_length); with return_text, "texts": the document's bytes under chunk_bytes, decoded with errors="replace".
+        padding, pad_to_multiple_of, pad_id, dtype, return_tensors and copy as in encode_batch_windows."""
+        eng = self._device_engine()
+        body = int(max_length or 0) - int(bool(add_bos)) - int(bool(add_eos))
+        m = max(body // 2, int(overlap or 0) + 1) if min_length is None else min_length
+        pad, data, offs, d_bytes, d_offs, stream = self._batch_prelude(
+            "encode_batch_chunks", docs, add_bos, add_eos, pad_id,
+            padding in ("longest", "max_length") and dtype in ("int64", "int32") and return_tensors in ("pt", "np")
+            and all(x in _LEVELS for x in levels), "padding / dtype / return_tensors / levels",
+            {"max_length": max_length, "min_length": m, "overlap": overlap}, upload=return_tensors != "np")
+        mask = sum(1 << _LEVELS[x] for x in set(levels))
+        flags = (CHUNK_FIXED if padding == "max_length" else 0) | (CHUNK_I64 if dtype == "int64" else 0) | CHUNK_BYTES \
+            | (CHUNK_MASK if return_attention_mask else 0) | (CHUNK_SPANS if return_offsets_mapping else 0)
+        if return_tensors == "np":
+            r = eng.encode_batch_chunk(data, offs, max_length, m, overlap, add_bos, add_eos, False, pad_to_multiple_of, pad, mask, flags)
+            out = {"input_ids": r["input_ids"], "attention_mask": r["mask"], "lengths": r["lengths"].astype(np.int32),
+                   "overflow_to_sample_mapping": r["window_doc"].astype(np.int32), "window_start": r["window_start"].astype(np.int32),
+                   "doc_windows": r["doc_windows"].astype(np.int64),
+                   "offset_mapping": r["spans"].astype(np.int32) if r["spans"] is not None else None,
+                   "cut_level": r["cut_level"], "chunk_bytes": r["chunk_bytes"].astype(np.int32),
+                   "level_counts": r["level_counts"].astype(np.int64), "n_windows": r["n_windows"], "n_split": r["n_split"]}
+            where, wdoc = out["chunk_bytes"], out["overflow_to_sample_mapping"]
+        else:
+            _, _, _, res = eng.encode_batch_device_chunk(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), max_length, m, overlap,
+                                                         add_bos, add_eos, pad_to_multiple_of or 0, pad, mask, flags, CHECK_OFFSETS, stream)
+            t = res.tensors(copy)
+            out = {"input_ids": t["input_ids"], "attention_mask": t["mask"], "lengths": t["lengths"], "overflow_to_sample_mapping": t["window_doc"],
+                   "window_start": t["window_start"], "doc_windows": t["doc_windows"], "offset_mapping": t["spans"], "cut_level": t["cut_level"],
+                   "chunk_bytes": t["chunk_bytes"], "level_counts": t["level_counts"], "n_windows": t["n_windows"], "n_split": t["n_split"]}
+            if return_text:
+                where, wdoc = out["chunk_bytes"].cpu().numpy(), out["overflow_to_sample_mapping"].cpu().numpy()
+        if return_text:
+            raw = data.tobytes()
+            out["texts"] = [raw[int(offs[d]) + int(s):int(offs[d]) + int(e)].decode("utf-8", errors="replace")
+                            for d, (s, e) in zip(wdoc.tolist(), where.tolist())]
         return out
 
     def _fixed_ids(self, ids, default):

@@ -1,4 +1,4 @@
-// tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _rowfit / _regroup / _pair.cpp) share, and
+// tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _chunk / _rowfit / _regroup / _pair.cpp) share, and
 // only they include: ONE description of the outputs of each result struct, from which tk_free_<pass> and the copy-out of the host
 // entries are made, and the three entries around a pass (ids on the device | text on the device | text on the host) written once.
 // (tk_capi_words.cpp, tk_capi_specials.cpp, tk_capi_fim.cpp and tk_capi_noise.cpp take the descriptions of tk_words / tk_specials /
@@ -43,6 +43,19 @@ template <class F> static inline void layout_outputs(tk_window& r, uint64_t esz,
     f(r.window_start, r.n_windows * 4, true);
     f(r.doc_windows, (r.n_docs + 1) * 8, true);
     f(r.spans, elems * 8, r.spans != nullptr);
+}
+template <class F> static inline void layout_outputs(tk_chunk& r, uint64_t esz, uint64_t, F&& f) {
+    const uint64_t elems = r.n_windows * r.row_len;
+    f(r.input_ids, elems * esz, true);
+    f(r.mask, elems, r.mask != nullptr);
+    f(r.lengths, r.n_windows * 4, true);
+    f(r.window_doc, r.n_windows * 4, true);
+    f(r.window_start, r.n_windows * 4, true);
+    f(r.doc_windows, (r.n_docs + 1) * 8, true);
+    f(r.spans, elems * 8, r.spans != nullptr);
+    f(r.cut_level, r.n_windows, true);
+    f(r.chunk_bytes, r.n_windows * 8, r.chunk_bytes != nullptr);
+    f(r.level_counts, 6 * 8, true);
 }
 template <class F> static inline void layout_outputs(tk_pair& r, uint64_t esz, uint64_t, F&& f) {
     const uint64_t elems = r.n_windows * r.row_len;

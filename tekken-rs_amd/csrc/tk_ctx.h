@@ -105,6 +105,14 @@ struct JoinBufs { DevBuf ids, offs, labels, pidx, stat, has, cb, start, plocal, 
 // the overlapping windows (tk_window.hip): the tensor, its mask and spans, the per-window arrays, doc_windows; the work arrays
 // (dw_next: the scan that becomes doc_windows once the call is accepted, the counts, the scan workspace, the statistics words)
 struct WindowBufs { DevBuf ids, mask, spans, len, doc, start, dw, dw_next, cnt, bsum, stat; };
+// the boundary-aware chunks (tk_chunk.hip): the window pass's outputs, cut_level, chunk_bytes and level_counts; the work arrays (as
+// the window pass's, and the windows' records); the level bytes of tk_chunk_levels_device and the spans of the entries that encode
+// first
+struct ChunkBufs {
+    DevBuf ids, mask, spans, len, doc, start, dw, cut, cbytes, lcounts, dw_next, cnt, bsum, stat, rec, lev, in_spans;
+    Event ev[7];                   // the stages of the last chunk call (tk_last_chunk_ms), created at the first one
+    float ms[3] = {0.f, 0.f, 0.f}; // levels | walks and scan | fill
+};
 // the sentence-pair rows (tk_pair.hip): the tensor, its mask, type ids, sequence ids and spans, the per-row arrays, pair_windows;
 // the work arrays (pw_next: the scan that becomes pair_windows once the call is accepted, the counts, the scan workspace, the
 // statistics words)
@@ -196,6 +204,7 @@ struct tk_ctx {
     SeqpackBufs seqpack;
     JoinBufs join;
     WindowBufs window;
+    ChunkBufs chunk;
     PairBufs pair;
     RowfitBufs rowfit;
     RegroupBufs regroup;

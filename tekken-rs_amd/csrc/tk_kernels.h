@@ -249,6 +249,44 @@ struct TkWindowArgs {
 hipError_t tk_launch_window_counts(const TkWindowArgs& a, hipStream_t s);   // counts, stat
 hipError_t tk_launch_window(const TkWindowArgs& a, int i64, hipStream_t s); // the outputs; n_rows == 0: nothing is launched
 
+// ---- boundary-aware token-budget chunks (tk_chunk.hip) ----
+struct TkChunkRec { uint32_t start, len, level, pad; };   // a chunk's body run B[start : start + len] and the level of the cut behind it
+struct TkChunkArgs {
+    const uint32_t* ids;       // [n_ids] packed token ids of all documents
+    const uint64_t* id_offs;   // [n_docs + 1]
+    const uint32_t* in_spans;  // [2 * n_ids] (start, end) per id, or NULL (the levels kernel: its input)
+    const uint8_t* lev;        // [n_ids] the level of the break in front of every id (a byte above 5 reads as 5)
+    uint64_t n_docs;
+    uint32_t max_len, min_len, overlap;   // T; m; o (0 <= o < m <= c = T - h - t)
+    uint32_t keep_head, keep_tail, pad_id;
+    uint32_t group;            // documents a wave of the walk takes (a power of two <= 64; set by the launcher)
+    uint32_t row_len;          // L (< 2^31; 0: only the per-row outputs are written)
+    uint64_t n_rows;           // W (< 2^32)
+    uint32_t* counts;          // [n_docs] w_d
+    const uint64_t* doc_windows;   // [n_docs + 1] exclusive scan of counts, strictly increasing
+    TkChunkRec* rec;           // [W] out of the second walk, in of the fill kernel
+    void* out;                 // [W * L] int32 or int64
+    uint8_t* mask;             // [W * L] or NULL
+    uint32_t* out_spans;       // [W * L * 2] or NULL
+    uint32_t* lengths;         // [W]
+    uint32_t* window_doc;      // [W]
+    uint32_t* window_start;    // [W]
+    uint8_t* cut_level;        // [W]
+    uint32_t* chunk_bytes;     // [W * 2] or NULL
+    // zeroed by the caller: [0] longest document, clamped to 2^32 - 1 (atomicMax), [1] += documents with w_d > 1, [2 .. 8) += the
+    // cuts made at level 0 .. 5
+    unsigned long long* stat;
+    TkyRows rows;              // the launch shape (tk_rows.h; set by the launcher)
+    // the levels kernel alone
+    const uint8_t* bytes;      // the text
+    const uint64_t* doc_offs;  // [n_docs + 1]
+    uint32_t demote;           // 4 bits a level: what level L becomes under the caller's mask
+    uint8_t* lev_out;          // [n_ids]
+};
+hipError_t tk_launch_chunk_levels(const TkChunkArgs& a, hipStream_t s);         // lev_out
+hipError_t tk_launch_chunk_walk(const TkChunkArgs& a, int records, hipStream_t s);   // 0: counts, stat; 1: rec (behind the scan)
+hipError_t tk_launch_chunk(const TkChunkArgs& a, int i64, hipStream_t s);       // the outputs; n_rows == 0: nothing is launched
+
 // ---- sentence-pair rows (tk_pair.hip) ----
 struct TkPairArgs {
     const uint32_t* ids;       // [n_ids] packed token ids of the 2P parts, encoded without BOS / EOS
