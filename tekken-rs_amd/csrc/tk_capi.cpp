@@ -144,6 +144,10 @@ static void read_knobs(TkKnobs& k) {
     if (const char* lf = getenv("TK_LONG_FORCE")) k.long_force = (uint32_t)atoi(lf);
     if (const char* ml = getenv("TK_MEMO_LOG2")) { const int v = atoi(ml); k.memo_log2 = v <= 0 ? 0u : (uint32_t)(v < 10 ? 10 : v > 26 ? 26 : v); }
     if (const char* mp = getenv("TK_MEMO_POLICY")) k.memo_policy = strcmp(mp, "always") == 0 ? 1 : 0;
+    if (const char* tf = getenv("TK_TAIL_FOLD")) k.tail_fold = atoi(tf) != 0 ? 1 : 0;
+    if (const char* fg = getenv("TK_TAIL_FOLD_MERGE")) k.fold_merge = atoi(fg) != 0;
+    if (const char* fm = getenv("TK_TAIL_FOLD_MISS_MAX")) k.fold_miss_max = (uint32_t)atoll(fm);
+    if (const char* fd = getenv("TK_TAIL_FOLD_DOC_MAX")) k.fold_doc_max = (uint32_t)atoll(fd);
     if (const char* pl = getenv("TK_PIPELINE"))  // "doc": per-document kernels only, "flat": chunk-per-wave kernel always
         k.pipeline_forced = strcmp(pl, "doc") == 0 ? 2 : strcmp(pl, "flat") == 0 ? 1 : 0;
 }

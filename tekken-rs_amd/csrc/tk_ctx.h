@@ -74,6 +74,12 @@ struct TkKnobs {
     uint32_t memo_log2 = 24;       // entries = 2^memo_log2 (32 bytes each: 512 MB of a 288 GB part), 0 = off; TK_MEMO_LOG2
     int memo_policy = 0;           // 0 adaptive (pause while the hit rate is low), 1 always on; TK_MEMO_POLICY=always
     int pipeline_forced = 0;       // TK_PIPELINE: 0 / 1 flat (default), 2 per-document kernels only
+    int tail_fold = -1;            // TK_TAIL_FOLD: the folded scans of the flat tail: -1 by the two bounds below, 0 never, 1 wherever they can run (A / B, tests)
+    // the folded forms cost (partial sums)^2 loads: the largest counts of partial sums at which they were not slower than the
+    // three-kernel scans (profiles/tail_fold_time.json); TK_TAIL_FOLD_MISS_MAX / TK_TAIL_FOLD_DOC_MAX
+    bool fold_merge = true;        // TK_TAIL_FOLD_MERGE=0: two merge kernels instead of tk_merge_all_kernel (the A / B that isolates it)
+    uint32_t fold_miss_max = 1300; // miss side: block sums of 2048 entries (5 n_chunks entries)
+    uint32_t fold_doc_max = 512;   // document side: blocks of 4096 documents
 };
 // ... and the ones read on EVERY call of the batch pipeline (call_knobs, tk_pipeline.cpp): tools set them between calls
 struct TkCallKnobs {
@@ -219,7 +225,7 @@ struct tk_ctx {
     DevBuf long_jobs;              // tk_long.hip: the long pieces of the long-list documents
     DevBuf long_list;              // pass 2 -> tk_long.hip: documents with a long piece that is not a vocabulary key
     // flat path (tk_flat.hip)
-    DevBuf f_first, f_tmp, f_lstart, f_flags, f_todo, f_miss, f_mcnt, f_mpfx, f_wfirst, f_info;
+    DevBuf f_first, f_tmp, f_lstart, f_flags, f_todo, f_miss, f_mcnt, f_mpfx, f_wfirst, f_info, f_gsum;
     DevBuf f_long;                 // records of the pieces of 65..TKF_LONGCAP bytes
     DevBuf f_cut;                  // chunks left to the CUT instantiation (tk_flat_cut_kernel)
     DevBuf f_late;                 // documents a long-piece record flagged after the list of handed-back documents was made

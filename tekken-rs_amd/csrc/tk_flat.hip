@@ -199,6 +199,47 @@ __global__ __launch_bounds__(TKM_WIDE_BLOCK) void tk_merge_wide_kernel(TkFlatArg
     }
 }
 
+// Both of the above in ONE launch (the folded tail): a block runs tk_merge_kernel's narrow loop, and then -- only if the wide
+// classes hold anything, which on ordinary text they do not -- passes a barrier and runs tk_merge_wide_kernel's loops on the same
+// 160 KB of LDS (the filter and the narrow columns are dead by then).  Same wave numbering, same memo log.  A block starts on its
+// wide items as soon as ITS narrow ones are done.  The two memo cases are two loops, so that the log record stays in registers
+// (a pointer that is either the record's address or null forces it into scratch memory: tk_merge_kernel's 24 bytes per lane).
+#define TKM_ALL_LDS_BYTES (TKM_LDS_BYTES > TKM_WIDE_LDS_BYTES ? TKM_LDS_BYTES : TKM_WIDE_LDS_BYTES)
+__global__ __launch_bounds__(TKM_BLOCK) void tk_merge_all_kernel(TkFlatArgs a) {
+    static_assert(TKM_BLOCK == TKM_WIDE_BLOCK && !TKM_WIDE_FILTER, "one block shape for both halves; the wide half reuses the filter's LDS");
+    extern __shared__ __attribute__((aligned(16))) uint32_t wlds[];
+    if (TKM_FILTER) tk_merge_load_filter<TKM_BLOCK, TK_PAIRF_WORDS>(a, wlds);
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t wave = (uint64_t)blockIdx.x * (TKM_BLOCK / 64) + wv;
+    const uint64_t n_waves = (uint64_t)gridDim.x * (TKM_BLOCK / 64);
+    const uint64_t p2 = a.miss_prefix[2 * a.n_chunks], p3 = a.miss_prefix[3 * a.n_chunks], p4 = a.miss_prefix[4 * a.n_chunks];
+    {
+        uint32_t* mlds = wlds + TKM_FWORDS + wv * TKM_LDS_WORDS(16);
+        if (a.memo_log) {                                    // (grid-uniform)
+            TkMemoLog ml;
+            ml.base = a.memo_log + wave * a.memo_log_per_wave;
+            ml.n = 0u;
+            ml.cap = wave < a.memo_log_waves ? a.memo_log_per_wave : 0u;
+            for (uint64_t w = wave; w * 64 < p2; w += n_waves) tk_merge_wave<false>(a, w, wv_lane(), mlds, TKM_FILTER ? wlds : nullptr, &ml);
+            if (wave < a.memo_log_waves && wv_lane() == 0) a.memo_log_counts[wave] = ml.n;
+        } else {
+            for (uint64_t w = wave; w * 64 < p2; w += n_waves) tk_merge_wave<false>(a, w, wv_lane(), mlds, TKM_FILTER ? wlds : nullptr, nullptr);
+        }
+    }
+    if (p4 == p2) return;                                    // (grid-uniform: every thread of a block passes the barrier or none does)
+    __syncthreads();
+    const uint64_t w2 = (p3 - p2 + 63) / 64, w3 = (p4 - p3 + 63) / 64;   // pieces of 17..32 / 33..64 bytes: 64 per wave
+    uint32_t* mlds = wlds + wv * TKM_LDS_WORDS(32);
+    for (uint64_t w = wave; w < w2; w += n_waves) tk_merge_wave<true>(a, w, wv_lane(), mlds, nullptr);
+    if (w3 == 0) return;                                     // (grid-uniform)
+    // the class 33..64 bytes needs 64-entry columns: every second wave takes it, with its neighbour's LDS
+    __syncthreads();
+    if ((wv & 1u) == 0u) {                                   // (scalar: wv is)
+        const uint64_t ew = wave >> 1, n_ew = n_waves >> 1;
+        for (uint64_t w = ew; w < w3; w += n_ew) tk_merge_wave_long3(a, w, wv_lane(), mlds, nullptr);
+    }
+}
+
 // flagged documents -> list; the longest of them (it sizes the scratch of the piece-by-piece pass) -> *maxlen
 __global__ __launch_bounds__(TKF_BLOCK) void tk_flat_todo_kernel(const uint32_t* __restrict__ flags, const uint64_t* __restrict__ doc_offs,
                                                                   uint64_t n_docs, uint32_t* __restrict__ todo,
@@ -223,6 +264,51 @@ __global__ __launch_bounds__(TKF_BLOCK) void tk_flat_counts_kernel(const uint64_
 // one wave per 64 consecutive documents, strided over the grid (tkf_assemble_waves)
 __global__ __launch_bounds__(TKF_BLOCK) void tk_flat_assemble_kernel(TkFlatAssembleArgs a) {
     tkf_assemble_waves(a, (uint64_t)blockIdx.x * (TKF_BLOCK / 64) + (threadIdx.x >> 6), (uint64_t)gridDim.x * (TKF_BLOCK / 64), wv_lane());
+}
+
+// ---- the folded tail (tk_flat_tail_impl.h: every consumer adds up the few partial sums below it itself) ----
+// miss side: raw block sums -> miss_prefix, wave_first, wave_first_wide, TKC_NARROW_LEFT; one wave per 512 entries
+__global__ __launch_bounds__(TKF_BLOCK) void tk_fold_apply_kernel(const uint32_t* __restrict__ counts, uint64_t n, uint64_t n_chunks,
+                                                                   const uint64_t* __restrict__ block_sums, uint64_t* __restrict__ prefix,
+                                                                   uint32_t* __restrict__ wave_first, uint32_t* __restrict__ wave_first_wide,
+                                                                   uint32_t* __restrict__ narrow_left_out) {
+    tkf_fold_apply_wave((uint64_t)blockIdx.x * (TKF_BLOCK / 64) + (threadIdx.x >> 6), wv_lane(), counts, n, n_chunks, block_sums, prefix,
+                        wave_first, wave_first_wide, narrow_left_out);
+}
+
+// document side: tkf_counts_body, the sums of every group of 64 documents and of the block's 4096
+#define TKF_FOLD_COUNTS_BLOCK (64u * (TKF_FOLD_DOC_BLOCK / (64u * TKF_FOLD_GROUPS)))   /* 16 waves */
+__global__ __launch_bounds__(TKF_FOLD_COUNTS_BLOCK) void tk_flat_counts_sums_kernel(const uint64_t* __restrict__ doc_offs, uint64_t n_docs,
+                                                                                     uint64_t n_bytes, uint64_t n_chunks,
+                                                                                     const uint64_t* __restrict__ P,
+                                                                                     const uint32_t* __restrict__ lstart,
+                                                                                     const uint32_t* __restrict__ flags,
+                                                                                     const uint32_t* __restrict__ holes, uint32_t extra,
+                                                                                     uint32_t* __restrict__ counts,
+                                                                                     TkFlatDocInfo* __restrict__ info, int final_pass,
+                                                                                     uint32_t* __restrict__ n_flagged,
+                                                                                     uint64_t* __restrict__ group_sums,
+                                                                                     uint64_t* __restrict__ doc_block_sums) {
+    __shared__ uint64_t wsum[TKF_FOLD_COUNTS_BLOCK / 64];
+    const uint32_t wv = threadIdx.x >> 6;
+    const uint64_t s = tkf_counts_sums_wave((uint64_t)blockIdx.x * (TKF_FOLD_COUNTS_BLOCK / 64) + wv, wv_lane(), doc_offs, n_docs, n_bytes,
+                                            n_chunks, P, lstart, flags, holes, extra, counts, info, final_pass, n_flagged, group_sums);
+    if (wv_lane() == 0) wsum[wv] = s;
+    __syncthreads();                                         // (every thread of the block gets here)
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (uint32_t w = 0; w < TKF_FOLD_COUNTS_BLOCK / 64; ++w) t += wsum[w];
+        doc_block_sums[blockIdx.x] = t;
+    }
+}
+
+// document side: one wave per 64 consecutive documents, output offsets made on the way (tkf_assemble_fold_waves)
+__global__ __launch_bounds__(TKF_BLOCK) void tk_flat_assemble_fold_kernel(TkFlatAssembleArgs a, const uint32_t* __restrict__ counts,
+                                                                           const uint64_t* __restrict__ group_sums,
+                                                                           const uint64_t* __restrict__ doc_block_sums,
+                                                                           uint64_t* __restrict__ out_offs) {
+    tkf_assemble_fold_waves(a, counts, group_sums, doc_block_sums, out_offs, (uint64_t)blockIdx.x * (TKF_BLOCK / 64) + (threadIdx.x >> 6),
+                            (uint64_t)gridDim.x * (TKF_BLOCK / 64), wv_lane());
 }
 
 // ------------------------------------------------------------------------------------------
@@ -282,7 +368,8 @@ hipError_t tk_launch_merge_wavefirst(const uint64_t* prefix, uint64_t n_chunks, 
     return hipGetLastError();
 }
 
-hipError_t tk_launch_merge(const TkFlatArgs& a, uint32_t* narrow_left_out, hipStream_t s) {
+// the two merge kernels: wave_first / wave_first_wide / TKC_NARROW_LEFT are there already (tk_launch_merge_wavefirst, or the folded apply)
+hipError_t tk_launch_merge_kernels(const TkFlatArgs& a, hipStream_t s) {
     if (a.n_chunks == 0) return hipSuccess;
     // persistent grids (the number of queued pieces stays on the device): the blocks that are resident at once -- each
     // one copies the PAIR filter into its LDS first -- and never more than the sub-queues could fill
@@ -309,11 +396,35 @@ hipError_t tk_launch_merge(const TkFlatArgs& a, uint32_t* narrow_left_out, hipSt
     uint64_t b1 = (a.n_chunks * 4 + TKM_BLOCK / 64 - 1) / (TKM_BLOCK / 64), b2 = (a.n_chunks + TKM_WIDE_BLOCK / 64 - 1) / (TKM_WIDE_BLOCK / 64);
     if (b1 > res1) b1 = res1;
     if (b2 > res2) b2 = res2;
-    (void)tk_launch_merge_wavefirst(a.miss_prefix, a.n_chunks, a.wave_first, a.wave_first_wide, narrow_left_out, s);
     // (the memo log is cut into one stretch per wave of THIS grid; a grid with more waves than the log was sized for logs nothing
     // from the surplus waves)
     hipLaunchKernelGGL(tk_merge_kernel, dim3((uint32_t)b1), dim3(TKM_BLOCK), TKM_LDS_BYTES, s, a);
     hipLaunchKernelGGL(tk_merge_wide_kernel, dim3((uint32_t)b2), dim3(TKM_WIDE_BLOCK), TKM_WIDE_LDS_BYTES, s, a);
+    if (a.memo_tab && a.memo_log) {
+        hipLaunchKernelGGL(tk_memo_commit_kernel, dim3(1024), dim3(TKF_BLOCK), 0, s, a.memo_tab, a.memo_log, a.memo_log_counts, a.memo_log_per_wave, a.memo_log_waves, a.t.key_hash_mode, a.memo_mask);
+    }
+    return hipGetLastError();
+}
+
+// tk_launch_merge_kernels with the two merge kernels in one launch (tk_merge_all_kernel); the memo's commit kernel behind it
+hipError_t tk_launch_merge_all(const TkFlatArgs& a, hipStream_t s) {
+    if (a.n_chunks == 0) return hipSuccess;
+    static uint64_t res_dev[64] = {0};   // (per device, like tk_launch_merge_kernels)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    uint64_t& res = res_dev[dev & 63];
+    if (res == 0) {
+        int cus = 256, p = 0;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(tk_merge_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                TKM_ALL_LDS_BYTES) != hipSuccess)
+            return hipErrorInvalidValue;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, tk_merge_all_kernel, TKM_BLOCK, TKM_ALL_LDS_BYTES) != hipSuccess || p <= 0) p = 1;
+        res = (uint64_t)cus * (uint64_t)p;
+    }
+    uint64_t b = (a.n_chunks * 4 + TKM_BLOCK / 64 - 1) / (TKM_BLOCK / 64);
+    if (b > res) b = res;
+    hipLaunchKernelGGL(tk_merge_all_kernel, dim3((uint32_t)b), dim3(TKM_BLOCK), TKM_ALL_LDS_BYTES, s, a);
     if (a.memo_tab && a.memo_log) {
         hipLaunchKernelGGL(tk_memo_commit_kernel, dim3(1024), dim3(TKF_BLOCK), 0, s, a.memo_tab, a.memo_log, a.memo_log_counts, a.memo_log_per_wave, a.memo_log_waves, a.t.key_hash_mode, a.memo_mask);
     }
@@ -414,5 +525,47 @@ hipError_t tk_launch_flat_assemble(uint64_t n_docs, const void* doc_info, const 
     uint64_t blocks = ((n_docs + 63) / 64 + (TKF_BLOCK / 64) - 1) / (TKF_BLOCK / 64);   // 64 documents per wave
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(tk_flat_assemble_kernel, dim3((uint32_t)blocks), dim3(TKF_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---- the folded tail: two launches for tk_launch_scan + tk_launch_merge_wavefirst, two for counts + scan + assembly ----
+hipError_t tk_launch_fold_apply(const uint32_t* counts, uint64_t n, uint64_t n_chunks, uint64_t* prefix, uint64_t* block_sums,
+                                uint32_t* wave_first, uint32_t* wave_first_wide, uint32_t* narrow_left_out, hipStream_t s) {
+    if (n_chunks == 0 || n < 4 * n_chunks) return hipErrorInvalidValue;
+    hipError_t e = tk_launch_scan_block_sums(counts, n, block_sums, s);
+    if (e != hipSuccess) return e;
+    const uint64_t waves = (n + TKF_FOLD_WAVE - 1) / TKF_FOLD_WAVE;
+    hipLaunchKernelGGL(tk_fold_apply_kernel, dim3(tkf_blocks(waves * 64)), dim3(TKF_BLOCK), 0, s, counts, n, n_chunks, block_sums, prefix,
+                       wave_first, wave_first_wide, narrow_left_out);
+    return hipGetLastError();
+}
+
+hipError_t tk_launch_flat_counts_sums(const uint64_t* doc_offs, uint64_t n_docs, uint64_t n_bytes, uint64_t n_chunks, const uint64_t* P,
+                                      const uint32_t* lstart, const uint32_t* flags, const uint32_t* holes, uint32_t extra,
+                                      uint32_t* counts, void* doc_info, int final_pass, uint32_t* n_flagged, uint64_t* group_sums,
+                                      uint64_t* doc_block_sums, hipStream_t s) {
+    if (n_docs == 0) return hipErrorInvalidValue;
+    const uint64_t blocks = (n_docs + TKF_FOLD_DOC_BLOCK - 1) / TKF_FOLD_DOC_BLOCK;
+    hipLaunchKernelGGL(tk_flat_counts_sums_kernel, dim3((uint32_t)blocks), dim3(TKF_FOLD_COUNTS_BLOCK), 0, s, doc_offs, n_docs, n_bytes,
+                       n_chunks, P, lstart, flags, holes, extra, counts, (TkFlatDocInfo*)doc_info, final_pass, n_flagged, group_sums,
+                       doc_block_sums);
+    return hipGetLastError();
+}
+
+hipError_t tk_launch_flat_assemble_fold(uint64_t n_docs, const void* doc_info, const uint32_t* kcount, const uint32_t* counts,
+                                        const uint64_t* group_sums, const uint64_t* doc_block_sums, uint64_t* out_offs,
+                                        const uint32_t* tmp, const uint32_t* staging, uint32_t* out_ids, uint32_t bos_id, uint32_t eos_id,
+                                        int add_bos, int add_eos, uint64_t* total_out, const uint32_t* skip_if, hipStream_t s) {
+    if (n_docs == 0) return hipErrorInvalidValue;
+    TkFlatAssembleArgs a;
+    a.total_out = total_out;
+    a.skip_if = skip_if;
+    a.n_docs = n_docs; a.info = (const TkFlatDocInfo*)doc_info; a.kcount = kcount; a.out_offs = out_offs;
+    a.tmp = tmp; a.staging = staging; a.out_ids = out_ids;
+    a.bos_id = bos_id; a.eos_id = eos_id; a.add_bos = add_bos; a.add_eos = add_eos;
+    uint64_t blocks = ((n_docs + 63) / 64 + (TKF_BLOCK / 64) - 1) / (TKF_BLOCK / 64);   // 64 documents per wave
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(tk_flat_assemble_fold_kernel, dim3((uint32_t)blocks), dim3(TKF_BLOCK), 0, s, a, counts, group_sums, doc_block_sums,
+                       out_offs);
     return hipGetLastError();
 }

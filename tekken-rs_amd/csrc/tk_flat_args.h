@@ -95,4 +95,12 @@ struct TkFlatArgs {
     TkTablesView t;
 };
 
+// ---- the folded tail (tk_flat_tail_impl.h) ----
+#define TKF_FOLD_TILE 2048u        /* counts per raw block sum of the miss side: the tile of tk_scan_block_sums */
+#define TKF_FOLD_WAVE 512u         /* entries of the miss side per wave of the apply: 8 per lane */
+#ifndef TKF_FOLD_GROUPS
+#define TKF_FOLD_GROUPS 4u         /* groups of 64 documents per wave of the counts kernel */
+#endif
+#define TKF_FOLD_DOC_BLOCK (1024u * TKF_FOLD_GROUPS)   /* documents per block sum of the document side: 16 waves of the counts kernel */
+
 #endif

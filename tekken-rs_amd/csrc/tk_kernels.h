@@ -62,7 +62,25 @@ hipError_t tk_launch_flat_assemble(uint64_t n_docs, const void* doc_info, const 
 // the first launch of tk_launch_merge on its own: which sub-queue holds the first item of every merge wave
 hipError_t tk_launch_merge_wavefirst(const uint64_t* prefix, uint64_t n_chunks, uint32_t* wave_first, uint32_t* wave_first_wide,
                                      uint32_t* narrow_left_out, hipStream_t s);
-hipError_t tk_launch_merge(const TkFlatArgs& a, uint32_t* narrow_left_out, hipStream_t s);  // both merge kernels, persistent grids (narrow_left_out: TKC_NARROW_LEFT)
+hipError_t tk_launch_merge_kernels(const TkFlatArgs& a, hipStream_t s);   // both merge kernels, persistent grids (behind the wave-first launch or the folded apply)
+hipError_t tk_launch_merge_all(const TkFlatArgs& a, hipStream_t s);       // ... as one launch: narrow loop, then the wide loops on the same LDS
+
+// ---- the folded tail of the flat path (tk_flat_tail_impl.h): the same arrays from fewer launches; for n_chunks, n_docs >= 1 ----
+// the first kernel of tk_launch_scan alone: raw (not scanned) sums of 2048 counts each
+hipError_t tk_launch_scan_block_sums(const uint32_t* counts, uint64_t n, uint64_t* block_sums, hipStream_t s);
+// tk_launch_scan(counts, n, prefix, ...) + tk_launch_merge_wavefirst in two launches; n >= 4 n_chunks (the sub-queue counts first)
+hipError_t tk_launch_fold_apply(const uint32_t* counts, uint64_t n, uint64_t n_chunks, uint64_t* prefix, uint64_t* block_sums,
+                                uint32_t* wave_first, uint32_t* wave_first_wide, uint32_t* narrow_left_out, hipStream_t s);
+// tk_launch_flat_counts, and the counts' sums per 64 documents (group_sums[ceil(n_docs / 64)]) and per 4096 (doc_block_sums)
+hipError_t tk_launch_flat_counts_sums(const uint64_t* doc_offs, uint64_t n_docs, uint64_t n_bytes, uint64_t n_chunks, const uint64_t* P,
+                                      const uint32_t* lstart, const uint32_t* flags, const uint32_t* holes, uint32_t extra,
+                                      uint32_t* counts, void* doc_info, int final_pass, uint32_t* n_flagged, uint64_t* group_sums,
+                                      uint64_t* doc_block_sums, hipStream_t s);
+// tk_launch_scan of the counts + tk_launch_flat_assemble in one launch: out_offs[0 .. n_docs] is WRITTEN here
+hipError_t tk_launch_flat_assemble_fold(uint64_t n_docs, const void* doc_info, const uint32_t* kcount, const uint32_t* counts,
+                                        const uint64_t* group_sums, const uint64_t* doc_block_sums, uint64_t* out_offs,
+                                        const uint32_t* tmp, const uint32_t* staging, uint32_t* out_ids, uint32_t bos_id, uint32_t eos_id,
+                                        int add_bos, int add_eos, uint64_t* total_out, const uint32_t* skip_if, hipStream_t s);
 
 hipError_t tk_launch_iota(uint32_t* out, uint64_t n, hipStream_t s);   // out[i] = i
 hipError_t tk_launch_add_u64(uint64_t* p, uint64_t n, uint64_t add, hipStream_t s);   // p[i] += add

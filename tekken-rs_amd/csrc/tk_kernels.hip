@@ -183,6 +183,16 @@ hipError_t tk_launch_scan(const uint32_t* counts, uint64_t n, uint64_t* offs, ui
     return hipGetLastError();
 }
 
+// the first kernel of the scan alone: block_sums[b] = sum of counts[2048 b .. 2048 b + 2048), not scanned.  The folded tail of
+// the flat path (tk_flat.hip: tk_fold_apply_kernel) adds up the sums below a tile itself instead of launching the other two.
+hipError_t tk_launch_scan_block_sums(const uint32_t* counts, uint64_t n, uint64_t* block_sums, hipStream_t s) {
+    static_assert(TK_SCAN_TILE == 2048, "TKF_FOLD_TILE of tk_flat_args.h is this tile");
+    const uint64_t n_blocks = (n + TK_SCAN_TILE - 1) / TK_SCAN_TILE;
+    if (n_blocks == 0) return hipSuccess;
+    hipLaunchKernelGGL(tk_scan_block_sums, dim3((uint32_t)n_blocks), dim3(TK_BLOCK), 0, s, counts, n, block_sums);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 // compaction: one wave per document, grid-stride over documents
 // ------------------------------------------------------------------------------------------

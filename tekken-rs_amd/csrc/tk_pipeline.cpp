@@ -309,7 +309,19 @@ struct FlatRun {
     uint64_t wf_narrow;            // entries of f_wfirst for the narrow classes (the wide ones lie behind them)
     uint64_t total;                // ids of the batch, once a finish() has been waited for
     TkFlatArgs fa;
+    bool fold_miss, fold_doc;      // the folded forms of the two scans (flat_fold_choice)
+    bool merge_one;                // both merge kernels in one launch (tk_merge_all_kernel)
 };
+
+// The folded forms (tk_flat_tail_impl.h) run where there is something to scan and the partial sums are few: every consumer adds
+// them up itself, (partial sums)^2 loads in all.  TK_TAIL_FOLD=0 / 1 forces either form (1: wherever it can run).
+static void flat_fold_choice(FlatRun& r) {
+    const TkKnobs& k = r.c->knobs;
+    const uint64_t miss_sums = (5 * r.n_chunks + TKF_FOLD_TILE - 1) / TKF_FOLD_TILE, doc_blocks = (r.n_docs + TKF_FOLD_DOC_BLOCK - 1) / TKF_FOLD_DOC_BLOCK;
+    r.fold_miss = r.n_chunks != 0 && k.tail_fold != 0 && (k.tail_fold == 1 || miss_sums <= k.fold_miss_max);
+    r.fold_doc = r.n_docs != 0 && k.tail_fold != 0 && (k.tail_fold == 1 || doc_blocks <= k.fold_doc_max);
+    r.merge_one = k.tail_fold != 0 && k.fold_merge;
+}
 
 static int flat_reserve(FlatRun& r) {
     tk_ctx* c = r.c;
@@ -331,6 +343,7 @@ static int flat_reserve(FlatRun& r) {
     TK_HIP(c, c->out_offs.reserve((n_docs + 1) * 8));
     const uint64_t scan_n = n_docs > 5 * n_chunks ? n_docs : 5 * n_chunks;
     TK_HIP(c, c->block_sums.reserve((scan_n / 2048 + 4) * 8));
+    if (r.fold_doc) TK_HIP(c, c->f_gsum.reserve(((n_docs + 63) / 64 + (n_docs + TKF_FOLD_DOC_BLOCK - 1) / TKF_FOLD_DOC_BLOCK + 2) * 8));   // group sums | block sums
     return TK_OK;
 }
 
@@ -424,13 +437,24 @@ static int flat_finish(FlatRun& r, int final_pass, bool wait) {
     const uint32_t extra = (uint32_t)((r.add_bos ? 1 : 0) + (r.add_eos ? 1 : 0));
     // chunk slot prefix sums: behind those of the 4 C miss counts (offset by the miss total: only differences are used)
     const uint64_t* d_P = (const uint64_t*)c->f_mpfx.p + 4 * r.n_chunks;
-    TK_HIP(c, tk_launch_flat_counts(r.d_offs, r.n_docs, r.n_bytes, r.n_chunks, d_P, fa.lstart, fa.flags, fa.holes, extra,
-                                    (uint32_t*)c->counts.p, c->f_info.p, final_pass, c->ctr(TKC_HANDED_BACK), r.s));
-    TK_HIP(c, tk_launch_scan((const uint32_t*)c->counts.p, r.n_docs, (uint64_t*)c->out_offs.p, (uint64_t*)c->block_sums.p, r.s));
-    TK_HIP(c, tk_launch_flat_assemble(r.n_docs, c->f_info.p, fa.kcount, (const uint64_t*)c->out_offs.p, fa.tmp,
-                                      (const uint32_t*)c->staging.p, (uint32_t*)c->out_ids.p, c->host.bos_id,
-                                      c->host.eos_id, r.add_bos, r.add_eos, (uint64_t*)c->ctr(TKC_TOTAL),
-                                      final_pass ? nullptr : c->ctr(TKC_HANDED_BACK), r.s));
+    if (r.fold_doc) {   // two launches: the counts kernel leaves sums, the assembly makes its own offsets
+        uint64_t* gsum = (uint64_t*)c->f_gsum.p;
+        uint64_t* bsum = gsum + (r.n_docs + 63) / 64;
+        TK_HIP(c, tk_launch_flat_counts_sums(r.d_offs, r.n_docs, r.n_bytes, r.n_chunks, d_P, fa.lstart, fa.flags, fa.holes, extra,
+                                             (uint32_t*)c->counts.p, c->f_info.p, final_pass, c->ctr(TKC_HANDED_BACK), gsum, bsum, r.s));
+        TK_HIP(c, tk_launch_flat_assemble_fold(r.n_docs, c->f_info.p, fa.kcount, (const uint32_t*)c->counts.p, gsum, bsum,
+                                               (uint64_t*)c->out_offs.p, fa.tmp, (const uint32_t*)c->staging.p, (uint32_t*)c->out_ids.p,
+                                               c->host.bos_id, c->host.eos_id, r.add_bos, r.add_eos, (uint64_t*)c->ctr(TKC_TOTAL),
+                                               final_pass ? nullptr : c->ctr(TKC_HANDED_BACK), r.s));
+    } else {
+        TK_HIP(c, tk_launch_flat_counts(r.d_offs, r.n_docs, r.n_bytes, r.n_chunks, d_P, fa.lstart, fa.flags, fa.holes, extra,
+                                        (uint32_t*)c->counts.p, c->f_info.p, final_pass, c->ctr(TKC_HANDED_BACK), r.s));
+        TK_HIP(c, tk_launch_scan((const uint32_t*)c->counts.p, r.n_docs, (uint64_t*)c->out_offs.p, (uint64_t*)c->block_sums.p, r.s));
+        TK_HIP(c, tk_launch_flat_assemble(r.n_docs, c->f_info.p, fa.kcount, (const uint64_t*)c->out_offs.p, fa.tmp,
+                                          (const uint32_t*)c->staging.p, (uint32_t*)c->out_ids.p, c->host.bos_id,
+                                          c->host.eos_id, r.add_bos, r.add_eos, (uint64_t*)c->ctr(TKC_TOTAL),
+                                          final_pass ? nullptr : c->ctr(TKC_HANDED_BACK), r.s));
+    }
     TK_HIP(c, hipEventRecord(c->ev[2], r.s));
     TK_HIP(c, hipMemcpyAsync(c->h_pin, c->ctr(TKC_WORK), TKC_FINAL_WORDS * 4, hipMemcpyDeviceToHost, r.s));
     if (wait) {
@@ -552,7 +576,8 @@ static int run_pipeline_flat(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* 
                              int add_bos, int add_eos, hipStream_t s, uint64_t* n_ids) {
     const bool serial = c->knobs.serial_tail;
     FlatRun r = {c, d_bytes, d_offs, n_docs, n_bytes, (n_bytes + TKF_COMMIT - 1) / TKF_COMMIT, add_bos, add_eos,
-                 s, serial ? s : (hipStream_t)c->stream_b, serial, 0, 0, {}};
+                 s, serial ? s : (hipStream_t)c->stream_b, serial, 0, 0, {}, false, false, false};
+    flat_fold_choice(r);
     int rc = flat_reserve(r);
     if (rc != TK_OK) return rc;
     flat_args(r);
@@ -584,8 +609,15 @@ static int run_pipeline_flat(tk_ctx* c, const uint8_t* d_bytes, const uint64_t* 
         ~JoinStreams() { if (armed) { (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(a); } }
     } join_guard{s, r.sb, true};
     if ((rc = flat_fork_todo(r)) != TK_OK) return rc;
-    TK_HIP(c, tk_launch_scan(r.fa.miss_count, 5 * r.n_chunks, (uint64_t*)c->f_mpfx.p, (uint64_t*)c->block_sums.p, s));
-    TK_HIP(c, tk_launch_merge(r.fa, c->ctr(TKC_NARROW_LEFT), s));
+    if (r.fold_miss) {  // block sums -> apply (prefix sums, wave_first*, TKC_NARROW_LEFT in one pass)
+        TK_HIP(c, tk_launch_fold_apply(r.fa.miss_count, 5 * r.n_chunks, r.n_chunks, (uint64_t*)c->f_mpfx.p, (uint64_t*)c->block_sums.p,
+                                       r.fa.wave_first, r.fa.wave_first_wide, c->ctr(TKC_NARROW_LEFT), s));
+    } else {
+        TK_HIP(c, tk_launch_scan(r.fa.miss_count, 5 * r.n_chunks, (uint64_t*)c->f_mpfx.p, (uint64_t*)c->block_sums.p, s));
+        TK_HIP(c, tk_launch_merge_wavefirst(r.fa.miss_prefix, r.n_chunks, r.fa.wave_first, r.fa.wave_first_wide, c->ctr(TKC_NARROW_LEFT), s));
+    }
+    // the single merge launch has nothing to do with the fold's bound: it is taken behind either scan form (TK_TAIL_FOLD=0: the two kernels)
+    TK_HIP(c, r.merge_one ? tk_launch_merge_all(r.fa, s) : tk_launch_merge_kernels(r.fa, s));
     TK_HIP(c, hipEventRecord(c->ev[4], s));
     if ((rc = flat_finish(r, 0, r.serial)) != TK_OK) return rc;
     const uint32_t* early = c->h_pin;

@@ -51,6 +51,10 @@ extern "C" {
 #endif
 // 0, or an error code with the reason in c->err.  The development build only.
 int tk_test_flat_tail(int device, struct TkTestTailCase* c);
+// the same with the folded forms of the two scans (tk_flat_tail_impl.h) where tk_pipeline.cpp would take them: fold = 0 never,
+// 1 wherever they can run, -1 while the miss side has at most miss_max block sums / the documents at most doc_max blocks of 4096
+// miss_prefix_out: NULL, or [4 n_chunks + 1] words for the prefix sums of the sub-queue counts as the merge kernels would read them
+int tk_test_flat_tail_fold(int device, struct TkTestTailCase* c, int fold, uint32_t miss_max, uint32_t doc_max, uint64_t* miss_prefix_out);
 // offs[0 .. n] = exclusive prefix sums of counts[0 .. n) through tk_launch_scan; offs must hold n + 2 words: the last one comes
 // back as it went in
 int tk_test_scan(int device, const uint32_t* counts, uint64_t n, uint64_t* offs_out);
