@@ -93,12 +93,12 @@ uint64_t tk_small_path_calls(const tk_ctx* ctx);
 /* Documents so far whose long piece (>= 1 KiB, not a vocabulary key) was merged in rounds by a whole workgroup
  * (csrc/tk_long.hip) instead of step by step by one wave (diagnostics / tests; TK_LONG_MIN overrides the threshold). */
 uint64_t tk_round_path_docs(const tk_ctx* ctx);
-/* Pieces of 65..256 bytes of the LAST batch that stayed on the flat path as records (csrc/tk_flat_impl.h step 6) instead of
+/* Pieces of 65..256 bytes of the LAST batch that stayed on the flat path as records (csrc/tk_flat_chunk_impl.h step 6) instead of
  * handing their documents to the per-document kernels (diagnostics / tests; TK_FLAT_LONG=0 at context creation switches
  * the path off, TK_FLAT_LONG128=0 its one-lane-per-piece merge). */
 uint64_t tk_long_piece_records(const tk_ctx* ctx);
 /* 2048-byte regions of the LAST batch that held a piece of more than 64 bytes and went through the CUT instantiation of the
- * flat kernel (csrc/tk_flat_impl.h step 4b: such a piece is cut into fragments wherever no vocabulary token can span the
+ * flat kernel (csrc/tk_flat_chunk_impl.h step 4b: such a piece is cut into fragments wherever no vocabulary token can span the
  * boundary, and the fragments merge independently -- exact; diagnostics / tests; TK_FLAT_CUT=0 switches the cuts off). */
 uint64_t tk_cut_chunks(const tk_ctx* ctx);
 /* Host waits of the LAST batch on the flat pipeline: 2 -- the list of the documents the flat kernel handed back (made on a

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(TKF_BLOCK) TKF_OCC void tk_flat_split_kernel(TkFlat
 
 // The chunks tk_flat_kernel left alone because they hold a piece of more than 64 bytes (a.cut_list): the same chunk work
 // with the CUT step -- such pieces are cut into fragments wherever no vocabulary token can span the boundary
-// (tk_flat_impl.h step 4b), so that a 32 KiB letter run becomes thousands of independent short merges instead of one chain
+// (tk_flat_chunk_impl.h step 4b), so that a 32 KiB letter run becomes thousands of independent short merges instead of one chain
 // and its document stays on the flat path.  Persistent waves over the list; the count never leaves the device.
 template <int DBG>
 __device__ __forceinline__ void tk_flat_cut_body(const TkFlatArgs& a, uint32_t* lds_all) {
@@ -155,19 +155,45 @@ TK_DEV void tk_merge_load_filter(const TkFlatArgs& a, uint32_t* filt) {
 #endif
 #define TKM_WIDE_FWORDS (TKM_WIDE_FILTER ? TK_PAIRF_WORDS : 0u)
 #define TKM_WIDE_LDS_BYTES ((TKM_WIDE_FWORDS + (TKM_WIDE_BLOCK / 64) * TKM_LDS_WORDS(32)) * 4)
+// The narrow classes (2..16 bytes): groups of 64 of the first `total` queued pieces, strided over the grid's waves.  LOG: what they merge into goes to
+// this wave's stretch of the memo log -- two loops, so that the log record stays in registers (a pointer that is its address or null: 24 bytes of scratch).
+template <bool LOG>
+__device__ __forceinline__ void tk_merge_narrow_loop(const TkFlatArgs& a, uint64_t wave, uint64_t n_waves, uint64_t total, uint32_t* mlds,
+                                                     const uint32_t* filt) {
+    if (LOG) {
+        TkMemoLog ml;
+        ml.base = a.memo_log + wave * a.memo_log_per_wave;
+        ml.n = 0u;
+        ml.cap = wave < a.memo_log_waves ? a.memo_log_per_wave : 0u;
+        for (uint64_t w = wave; w * 64 < total; w += n_waves) tk_merge_wave<false>(a, w, wv_lane(), mlds, filt, &ml);
+        if (wave < a.memo_log_waves && wv_lane() == 0) a.memo_log_counts[wave] = ml.n;
+    } else {
+        for (uint64_t w = wave; w * 64 < total; w += n_waves) tk_merge_wave<false>(a, w, wv_lane(), mlds, filt, nullptr);
+    }
+}
+// The wide classes: w2 groups of 64 pieces of 17..32 bytes, then w3 of 33..64 bytes (wv: the wave's number in its block, scalar in every caller)
+__device__ __forceinline__ void tk_merge_wide_loops(const TkFlatArgs& a, uint32_t wv, uint64_t wave, uint64_t n_waves, uint64_t w2, uint64_t w3,
+                                                    uint32_t* mlds, const uint32_t* filt) {
+    for (uint64_t w = wave; w < w2; w += n_waves) tk_merge_wave<true>(a, w, wv_lane(), mlds, filt);
+    if (w3 == 0) return;                                     // (grid-uniform)
+    // the class 33..64 bytes needs 64-entry columns: every second wave takes it, with its neighbour's LDS
+    __syncthreads();
+    if ((wv & 1u) == 0u) {
+        const uint64_t ew = wave >> 1, n_ew = n_waves >> 1;
+        for (uint64_t w = ew; w < w3; w += n_ew) tk_merge_wave_long3(a, w, wv_lane(), mlds, filt);
+    }
+}
+
 __global__ __launch_bounds__(TKM_BLOCK) void tk_merge_kernel(TkFlatArgs a) {   // pieces of 2..16 bytes
     extern __shared__ __attribute__((aligned(16))) uint32_t wlds[];
     if (TKM_FILTER) tk_merge_load_filter<TKM_BLOCK, TK_PAIRF_WORDS>(a, wlds);
-    const uint64_t wave = (uint64_t)blockIdx.x * (TKM_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform: say so, as in tk_merge_all_kernel)
+    const uint64_t wave = (uint64_t)blockIdx.x * (TKM_BLOCK / 64) + wv;
     const uint64_t n_waves = (uint64_t)gridDim.x * (TKM_BLOCK / 64);
     const uint64_t total = a.miss_prefix[2 * a.n_chunks];
-    uint32_t* mlds = wlds + TKM_FWORDS + (threadIdx.x >> 6) * TKM_LDS_WORDS(16);
-    TkMemoLog ml;
-    ml.base = a.memo_log ? a.memo_log + wave * a.memo_log_per_wave : nullptr;
-    ml.n = 0u;
-    ml.cap = a.memo_log && wave < a.memo_log_waves ? a.memo_log_per_wave : 0u;
-    for (uint64_t w = wave; w * 64 < total; w += n_waves) tk_merge_wave<false>(a, w, wv_lane(), mlds, TKM_FILTER ? wlds : nullptr, a.memo_log ? &ml : nullptr);
-    if (a.memo_log && wave < a.memo_log_waves && wv_lane() == 0) a.memo_log_counts[wave] = ml.n;
+    uint32_t* mlds = wlds + TKM_FWORDS + wv * TKM_LDS_WORDS(16);
+    if (a.memo_log) tk_merge_narrow_loop<true>(a, wave, n_waves, total, mlds, TKM_FILTER ? wlds : nullptr);   // (grid-uniform)
+    else tk_merge_narrow_loop<false>(a, wave, n_waves, total, mlds, TKM_FILTER ? wlds : nullptr);
 }
 
 // the log of the merge kernel's new memo entries into the table (tk_memo_commit_one; the slots were claimed where the records were written)
@@ -183,27 +209,19 @@ __global__ __launch_bounds__(TKM_WIDE_BLOCK) void tk_merge_wide_kernel(TkFlatArg
     extern __shared__ __attribute__((aligned(16))) uint32_t wlds[];
     if (TKM_WIDE_FILTER) tk_merge_load_filter<TKM_WIDE_BLOCK, TKM_WIDE_FWORDS>(a, wlds);
     const uint32_t* wfilt = TKM_WIDE_FILTER ? wlds : nullptr;
-    const uint64_t wave = (uint64_t)blockIdx.x * (TKM_WIDE_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform: say so, as in the other two)
+    const uint64_t wave = (uint64_t)blockIdx.x * (TKM_WIDE_BLOCK / 64) + wv;
     const uint64_t n_waves = (uint64_t)gridDim.x * (TKM_WIDE_BLOCK / 64);
     const uint64_t n2 = a.miss_prefix[3 * a.n_chunks] - a.miss_prefix[2 * a.n_chunks];   // pieces of 17..32 bytes: 64 per wave
     const uint64_t n3 = a.miss_prefix[4 * a.n_chunks] - a.miss_prefix[3 * a.n_chunks];   // pieces of 33..64 bytes: 64 per wave
     const uint64_t w2 = (n2 + 63) / 64, w3 = (n3 + 63) / 64;
-    uint32_t* mlds = wlds + TKM_WIDE_FWORDS + (threadIdx.x >> 6) * TKM_LDS_WORDS(32);
-    for (uint64_t w = wave; w < w2; w += n_waves) tk_merge_wave<true>(a, w, wv_lane(), mlds, wfilt);
-    if (w3 == 0) return;                                     // (grid-uniform)
-    // the class 33..64 bytes needs 64-entry columns: every second wave takes it, with its neighbour's LDS
-    __syncthreads();
-    if (((threadIdx.x >> 6) & 1u) == 0u) {
-        const uint64_t ew = wave >> 1, n_ew = n_waves >> 1;
-        for (uint64_t w = ew; w < w3; w += n_ew) tk_merge_wave_long3(a, w, wv_lane(), mlds, wfilt);
-    }
+    tk_merge_wide_loops(a, wv, wave, n_waves, w2, w3, wlds + TKM_WIDE_FWORDS + wv * TKM_LDS_WORDS(32), wfilt);
 }
 
 // Both of the above in ONE launch (the folded tail): a block runs tk_merge_kernel's narrow loop, and then -- only if the wide
 // classes hold anything, which on ordinary text they do not -- passes a barrier and runs tk_merge_wide_kernel's loops on the same
 // 160 KB of LDS (the filter and the narrow columns are dead by then).  Same wave numbering, same memo log.  A block starts on its
-// wide items as soon as ITS narrow ones are done.  The two memo cases are two loops, so that the log record stays in registers
-// (a pointer that is either the record's address or null forces it into scratch memory: tk_merge_kernel's 24 bytes per lane).
+// wide items as soon as ITS narrow ones are done.  (The two memo cases: tk_merge_narrow_loop.)
 #define TKM_ALL_LDS_BYTES (TKM_LDS_BYTES > TKM_WIDE_LDS_BYTES ? TKM_LDS_BYTES : TKM_WIDE_LDS_BYTES)
 __global__ __launch_bounds__(TKM_BLOCK) void tk_merge_all_kernel(TkFlatArgs a) {
     static_assert(TKM_BLOCK == TKM_WIDE_BLOCK && !TKM_WIDE_FILTER, "one block shape for both halves; the wide half reuses the filter's LDS");
@@ -215,29 +233,13 @@ __global__ __launch_bounds__(TKM_BLOCK) void tk_merge_all_kernel(TkFlatArgs a) {
     const uint64_t p2 = a.miss_prefix[2 * a.n_chunks], p3 = a.miss_prefix[3 * a.n_chunks], p4 = a.miss_prefix[4 * a.n_chunks];
     {
         uint32_t* mlds = wlds + TKM_FWORDS + wv * TKM_LDS_WORDS(16);
-        if (a.memo_log) {                                    // (grid-uniform)
-            TkMemoLog ml;
-            ml.base = a.memo_log + wave * a.memo_log_per_wave;
-            ml.n = 0u;
-            ml.cap = wave < a.memo_log_waves ? a.memo_log_per_wave : 0u;
-            for (uint64_t w = wave; w * 64 < p2; w += n_waves) tk_merge_wave<false>(a, w, wv_lane(), mlds, TKM_FILTER ? wlds : nullptr, &ml);
-            if (wave < a.memo_log_waves && wv_lane() == 0) a.memo_log_counts[wave] = ml.n;
-        } else {
-            for (uint64_t w = wave; w * 64 < p2; w += n_waves) tk_merge_wave<false>(a, w, wv_lane(), mlds, TKM_FILTER ? wlds : nullptr, nullptr);
-        }
+        if (a.memo_log) tk_merge_narrow_loop<true>(a, wave, n_waves, p2, mlds, TKM_FILTER ? wlds : nullptr);   // (grid-uniform)
+        else tk_merge_narrow_loop<false>(a, wave, n_waves, p2, mlds, TKM_FILTER ? wlds : nullptr);
     }
     if (p4 == p2) return;                                    // (grid-uniform: every thread of a block passes the barrier or none does)
     __syncthreads();
     const uint64_t w2 = (p3 - p2 + 63) / 64, w3 = (p4 - p3 + 63) / 64;   // pieces of 17..32 / 33..64 bytes: 64 per wave
-    uint32_t* mlds = wlds + wv * TKM_LDS_WORDS(32);
-    for (uint64_t w = wave; w < w2; w += n_waves) tk_merge_wave<true>(a, w, wv_lane(), mlds, nullptr);
-    if (w3 == 0) return;                                     // (grid-uniform)
-    // the class 33..64 bytes needs 64-entry columns: every second wave takes it, with its neighbour's LDS
-    __syncthreads();
-    if ((wv & 1u) == 0u) {                                   // (scalar: wv is)
-        const uint64_t ew = wave >> 1, n_ew = n_waves >> 1;
-        for (uint64_t w = ew; w < w3; w += n_ew) tk_merge_wave_long3(a, w, wv_lane(), mlds, nullptr);
-    }
+    tk_merge_wide_loops(a, wv, wave, n_waves, w2, w3, wlds + wv * TKM_LDS_WORDS(32), nullptr);
 }
 
 // flagged documents -> list; the longest of them (it sizes the scratch of the piece-by-piece pass) -> *maxlen
@@ -431,7 +433,7 @@ hipError_t tk_launch_merge_all(const TkFlatArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Pieces of 65..TKF_LONGCAP bytes (tk_flat_impl.h step 6): one wave per record -- the end of the piece where the chunk did
+// Pieces of 65..TKF_LONGCAP bytes (tk_flat_chunk_impl.h step 6): one wave per record -- the end of the piece where the chunk did
 // not see it (sequential matcher), whole-piece lookup, the single-wave merge; ids + holes into the slots the chunk
 // reserved, the document's hole count like the merge kernels.  Launched only when the flat kernel wrote records.
 __global__ __launch_bounds__(256) void tk_flat_long_kernel(TkFlatArgs a, uint32_t* work_counter, uint32_t* scratch, uint32_t scratch_words) {

@@ -16,7 +16,7 @@
                                                         chunk's last piece, when its end is not in the region, reserves LONGCAP slots */
 /* queue records per chunk, one sub-queue per length class (2..8, 9..16, 17..32, 33..64 bytes).  A chunk owns the pieces that
    start in its commit range and, where a long piece that it cuts into fragments ends in its right halo, the fragments up to
-   that end (tk_flat_impl.h, CUT instantiation): TKF_OWN bytes at most */
+   that end (tk_flat_chunk_impl.h, CUT instantiation): TKF_OWN bytes at most */
 #define TKF_OWN (TKF_COMMIT + TKF_HR)
 #define TKF_MISSOFF0 0u
 #define TKF_MISSOFF1 (TKF_OWN / 2u)                                 /* at most OWN / 2 pieces of >= 2 bytes */

@@ -37,7 +37,7 @@ void TkHostTables::make_pair_filter() {
     }
 }
 
-// The cut rule (tk_flat_impl.h, CUT instantiation; model: tools/cut_model.py): a part of the merge loop that spans the
+// The cut rule (tk_flat_chunk_impl.h, CUT instantiation; model: tools/cut_model.py): a part of the merge loop that spans the
 // boundary between bytes i-1 and i is a vocabulary key -- of two bytes (then it is the bigram itself: cut_k2) or of more
 // (then it contains b[i-2..i] or b[i-1..i+1]: cut_g3 holds every trigram that occurs inside a token).
 void TkHostTables::make_cut_tables() {

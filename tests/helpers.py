@@ -50,6 +50,22 @@ def random_unicode_docs(n, seed=7, max_len=120):
     return ["".join(rng.choice(alpha) for _ in range(rng.randint(0, max_len))).encode("utf-8") for _ in range(n)]
 
 
+def walked_lead_byte_docs():
+    """Both sides of TKF_WALKCAP (672 lead bytes per region that the multi-byte walk of tk_flat_chunk_impl.h deals out over the lanes; more
+    are walked lane by lane).  Two-byte chars that the range rules of tkf_classify do not cover -- Armenian letters (lead bytes D4 /
+    D5), section and pilcrow signs, U+00A0 and U+0085 (lead C2), an NKo digit (lead DF) -- in a fixed mixed order, 600 .. 1024 of them
+    per 2048-byte stretch, padded with "x "; every stretch three times over as one document, and twice over behind 31 ASCII letters."""
+    chars = ["\u0531", "\u00a7", "\u0561", "\u00a0", "\u0540", "\u00b6", "\u0575", "\u0085", "\u07c1"]
+    assert all(len(c.encode("utf-8")) == 2 for c in chars)
+    docs = []
+    for k in (600, 640, 671, 672, 673, 704, 900, 1024):
+        s = "".join(chars[i % len(chars)] for i in range(k)).encode("utf-8")
+        s += (b"x " * 1024)[:2048 - len(s)]
+        assert len(s) == 2048
+        docs += [s * 3, (b"abcdefghijklmnopqrstuvwxyzabcde" + s) * 2]
+    return docs
+
+
 def oracle_for(v):
     import tk_oracle
     return tk_oracle.Oracle(v["tokens"], v["num_special"], v["bos"], v["eos"])

@@ -147,7 +147,7 @@ def test_every_kind_of_run_behind_a_char_the_region_cuts(test_vocab):
 
 def test_emu_flat_sparse_miss_queues(test_vocab):
     """A few queued pieces in ~300 chunks: the later items of a merge wave lie more than three 64-entry windows of
-    sub-queues behind the first, so the wave finds them by bisection (csrc/tk_flat_impl.h tk_merge_wave), narrow and wide."""
+    sub-queues behind the first, so the wave finds them by bisection (csrc/tk_merge_impl.h tk_merge_wave), narrow and wide."""
     filler = b"a\nb\nc\nd\ne\nf\ng\nh\ni\nj\nk\nl\nm\nn\no\np\nq\nr\ns\nt\nu\nv\nw\nx\ny\nz\n" * 40      # one-byte pieces: never queued
     docs = [filler] * 290
     for d, w in ((0, b"qzxjv"), (140, b"kqjxzvwpyfbg"), (280, b"zqxjkvbwpfgmhdcylrtn"), (3, b"xzqjvkwbpfmgyhdclrtnxzqjvkwbpfmgyhdclrtn"),
@@ -157,7 +157,7 @@ def test_emu_flat_sparse_miss_queues(test_vocab):
 
 
 def test_emu_flat_long_pieces_stay_on_the_flat_path(test_vocab, monkeypatch):
-    """Pieces of 65..256 bytes (tk_flat_impl.h step 6, tk_flat_long_wave): their documents are NOT handed back -- the piece
+    """Pieces of 65..256 bytes (tk_flat_chunk_impl.h step 6, tk_merge_impl.h tk_flat_long_wave): their documents are NOT handed back -- the piece
     becomes a record, its ids come from one wave's lookup / merge into the reserved slots; where the chunk does not see the
     end of its last piece (the piece crosses the region end) the sequential matcher finds it; beyond 256 bytes the document
     is handed back after all unless the piece can be cut (step 4b; TK_FLAT_CUT=0 shows the hand-back).  Letter runs, CJK runs, punctuation runs, at every offset around a chunk boundary."""
@@ -353,6 +353,17 @@ def test_emu_flat_every_bmp_code_point(small_vocab):
             assert starts[i] == tk_oracle.split(d), (i, d[:60])
         assert ids[i] == o.encode(d, False, False), i
     assert len(flagged) < len(docs) // 10
+
+
+def test_emu_flat_walk_both_sides_of_walkcap(test_vocab):
+    """The multi-byte walk (tk_flat_chunk_impl.h tkf_walk_chars) has one decoder, one class look-up and one marker for its two forms:
+    the lead bytes dealt out over all lanes (up to TKF_WALKCAP = 672 of them in a region) and every lane walking its own (beyond;
+    always under the JSON pattern).  600 .. 1024 walked lead bytes per 2048 bytes (helpers.walked_lead_byte_docs), ids and split
+    against the oracle under both patterns; such text stays on the flat path."""
+    docs = helpers.walked_lead_byte_docs()
+    assert len(docs) == 16
+    assert len(_emu_check(test_vocab, docs)) <= len(docs) // 4
+    _emu_check_json(test_vocab, docs)
 
 
 def test_key_hash_fallback_mode(test_vocab):

@@ -633,9 +633,25 @@ def test_json_pattern_opt_in(tk, test_vocab, bench_vocab):
     t.close()
 
 
+def test_walk_both_sides_of_walkcap(tk, eng_small, test_vocab):
+    """GPU twin of test_flat_path.py test_emu_flat_walk_both_sides_of_walkcap: 600 .. 1024 walked lead bytes per 2048 bytes, the
+    dealt walk and the lane-by-lane walk of tk_flat_chunk_impl.h tkf_walk_chars, ids against the oracle under both patterns."""
+    docs = helpers.walked_lead_byte_docs()
+    plain = helpers.oracle_for(test_vocab)
+    assert eng_small.encode_docs(docs, True, True) == [plain.encode(d, True, True) for d in docs]
+    orc = helpers.oracle_for(test_vocab)
+    orc.set_pattern(1)
+    e = tk.Engine(test_vocab["tokens"], test_vocab["num_special"], test_vocab["bos"], test_vocab["eos"], device=0)
+    try:
+        e.set_pattern(1)
+        assert e.encode_docs(docs, True, True) == [orc.encode(d, True, True) for d in docs]
+    finally:
+        e.close()
+
+
 @pytest.mark.gpu
 def test_merge_kernels_every_piece_length(tk, eng_small, eng_bench, test_vocab, bench_vocab):
-    """The merge kernels (csrc/tk_flat_impl.h tk_merge_lds<8|16|32>, the one-lane-per-byte loop for 33..64 bytes, pass 2
+    """The merge kernels (csrc/tk_merge_impl.h tk_merge_lds<8|16|32>, the one-lane-per-byte loop for 33..64 bytes, pass 2
     beyond): words of every length 2..80 that miss the vocabulary -- random letters, runs of one letter, UTF-8 words --
     many per document, so that a wave's 64 queued pieces span several documents (the hole counts of a run of lanes
     are combined into one atomic) and the 16-byte id stores meet every alignment and every tail length."""
@@ -664,7 +680,7 @@ def test_merge_kernels_every_piece_length(tk, eng_small, eng_bench, test_vocab, 
 
 def test_sparse_miss_queues(tk, eng_bench, bench_vocab):
     """Few queued pieces in many chunks: the 64 items of a merge wave then span thousands of per-chunk sub-queues (the wave
-    finds them by a window over the prefix sums, then by bisection: csrc/tk_flat_impl.h tk_merge_wave); every length class,
+    finds them by a window over the prefix sums, then by bisection: csrc/tk_merge_impl.h tk_merge_wave); every length class,
     also with one single queued piece in the whole batch."""
     import random
     rng = random.Random(99)
@@ -689,7 +705,7 @@ def test_sparse_miss_queues(tk, eng_bench, bench_vocab):
 
 
 def test_long_pieces_stay_on_the_flat_path(tk, eng_small, eng_bench, test_vocab, bench_vocab, monkeypatch):
-    """Pieces of 65..256 bytes (csrc/tk_flat_impl.h step 6, tk_flat_long_kernel): their documents are not handed back; beyond 256
+    """Pieces of 65..256 bytes (csrc/tk_flat_chunk_impl.h step 6, tk_flat_long_kernel): their documents are not handed back; beyond 256
     bytes they are unless the piece can be cut (step 4b; TK_FLAT_CUT=0 shows the hand-back).  Letter runs, CJK paragraphs, rulers, the first byte of the piece walking over a chunk boundary, many
     such pieces per document; the same batch with the path switched off (TK_FLAT_LONG=0) gives the same ids."""
     import random

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Model of the EXACT CUT DECOMPOSITION of a missed piece (csrc/tk_flat_impl.h, CUT instantiation of the flat kernel).
+"""Model of the EXACT CUT DECOMPOSITION of a missed piece (csrc/tk_flat_chunk_impl.h, CUT instantiation of the flat kernel).
 
 tiktoken's merge loop (the engine behind reference src/tekkenizer.rs:384-386) joins two adjacent parts
 only if their concatenated BYTES are a vocabulary key.  A part that spans the boundary i | i+1 of a piece therefore is a

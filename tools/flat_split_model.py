@@ -1,7 +1,7 @@
 """Executable model of the FLAT split: the piece-start rules of tools/split_rules_model.py restated as
 pure mask algebra over the packed byte stream of ALL documents (bit i = byte i of the packed buffer).
 
-This is what tk_flat_kernel (tekken-rs_amd/csrc/tk_flat_impl.h) evaluates, one chunk of the stream per
+This is what tk_flat_kernel (tekken-rs_amd/csrc/tk_flat_lane.h rules, tk_flat_chunk_impl.h) evaluates, one chunk of the stream per
 wave with the masks held "lane layout" (lane l owns bits [W*l, W*l+W) of the chunk).  Document
 boundaries are just another mask: every look-behind shift is cut at a document start (DS), every
 look-ahead shift at a document end (DE), runs are broken at DS.  ASCII only: a document with a byte
