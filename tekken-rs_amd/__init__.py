@@ -767,6 +767,19 @@ def _windows(r):
     return (r.n_windows, r.row_len)
 
 
+def _window_dict(r, **own):
+    """What encode_batch_windows returns, from the engine's numpy result (uint32 / uint64 arrays: shown as int32 / int64) or from
+    the tensors of a device result; own: the keys a pass adds in front of the counts (encode_batch_chunks)."""
+    as_ = (lambda v, dt: v.astype(dt)) if isinstance(r["lengths"], np.ndarray) else (lambda v, dt: v)
+    out = {"input_ids": r["input_ids"], "attention_mask": r["mask"], "lengths": as_(r["lengths"], np.int32),
+           "overflow_to_sample_mapping": as_(r["window_doc"], np.int32), "window_start": as_(r["window_start"], np.int32),
+           "doc_windows": as_(r["doc_windows"], np.int64),
+           "offset_mapping": as_(r["spans"], np.int32) if r["spans"] is not None else None}
+    out.update(own)
+    out["n_windows"], out["n_split"] = r["n_windows"], r["n_split"]
+    return out
+
+
 class PairResult(_LayoutResult):
     """What the device pair entries return (tk_pair): raw device pointers of context-owned buffers, valid until the next pair call
     on the context.  input_ids_ptr: int32 or int64 [n_windows, row_len]; mask_ptr / type_ids_ptr / sequence_ids_ptr: uint8
@@ -2406,11 +2419,7 @@ class Tekkenizer:
             | (WINDOW_MASK if return_attention_mask else 0) | (WINDOW_SPANS if return_offsets_mapping else 0)
         if return_tensors == "np" and not in_units:
             r = eng.encode_batch_window(data, offs, max_length, stride, add_bos, add_eos, False, pad_to_multiple_of, pad, flags)
-            return {"input_ids": r["input_ids"], "attention_mask": r["mask"], "lengths": r["lengths"].astype(np.int32),
-                    "overflow_to_sample_mapping": r["window_doc"].astype(np.int32), "window_start": r["window_start"].astype(np.int32),
-                    "doc_windows": r["doc_windows"].astype(np.int64),
-                    "offset_mapping": r["spans"].astype(np.int32) if r["spans"] is not None else None,
-                    "n_windows": r["n_windows"], "n_split": r["n_split"]}
+            return _window_dict(r)
         import torch
         if in_units:
             # three calls on the stream: encode, the units pass, the window pass over the unit spans (every window repeats BOS / EOS)
@@ -2421,10 +2430,7 @@ class Tekkenizer:
         else:
             _, _, _, res = eng.encode_batch_device_window(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), max_length, stride,
                                                           add_bos, add_eos, pad_to_multiple_of, pad, flags, CHECK_OFFSETS, stream)
-        t = res.tensors(copy)
-        out = {"input_ids": t["input_ids"], "attention_mask": t["mask"], "lengths": t["lengths"], "overflow_to_sample_mapping": t["window_doc"],
-               "window_start": t["window_start"], "doc_windows": t["doc_windows"], "offset_mapping": t["spans"],
-               "n_windows": t["n_windows"], "n_split": t["n_split"]}
+        out = _window_dict(res.tensors(copy))
         if return_tensors == "np":
             out = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in out.items()}
         return out
@@ -2456,20 +2462,14 @@ class Tekkenizer:
             | (CHUNK_MASK if return_attention_mask else 0) | (CHUNK_SPANS if return_offsets_mapping else 0)
         if return_tensors == "np":
             r = eng.encode_batch_chunk(data, offs, max_length, m, overlap, add_bos, add_eos, False, pad_to_multiple_of, pad, mask, flags)
-            out = {"input_ids": r["input_ids"], "attention_mask": r["mask"], "lengths": r["lengths"].astype(np.int32),
-                   "overflow_to_sample_mapping": r["window_doc"].astype(np.int32), "window_start": r["window_start"].astype(np.int32),
-                   "doc_windows": r["doc_windows"].astype(np.int64),
-                   "offset_mapping": r["spans"].astype(np.int32) if r["spans"] is not None else None,
-                   "cut_level": r["cut_level"], "chunk_bytes": r["chunk_bytes"].astype(np.int32),
-                   "level_counts": r["level_counts"].astype(np.int64), "n_windows": r["n_windows"], "n_split": r["n_split"]}
+            out = _window_dict(r, cut_level=r["cut_level"], chunk_bytes=r["chunk_bytes"].astype(np.int32),
+                               level_counts=r["level_counts"].astype(np.int64))
             where, wdoc = out["chunk_bytes"], out["overflow_to_sample_mapping"]
         else:
             _, _, _, res = eng.encode_batch_device_chunk(d_bytes.data_ptr(), d_offs.data_ptr(), len(docs), len(data), max_length, m, overlap,
                                                          add_bos, add_eos, pad_to_multiple_of or 0, pad, mask, flags, CHECK_OFFSETS, stream)
             t = res.tensors(copy)
-            out = {"input_ids": t["input_ids"], "attention_mask": t["mask"], "lengths": t["lengths"], "overflow_to_sample_mapping": t["window_doc"],
-                   "window_start": t["window_start"], "doc_windows": t["doc_windows"], "offset_mapping": t["spans"], "cut_level": t["cut_level"],
-                   "chunk_bytes": t["chunk_bytes"], "level_counts": t["level_counts"], "n_windows": t["n_windows"], "n_split": t["n_split"]}
+            out = _window_dict(t, cut_level=t["cut_level"], chunk_bytes=t["chunk_bytes"], level_counts=t["level_counts"])
             if return_text:
                 where, wdoc = out["chunk_bytes"].cpu().numpy(), out["overflow_to_sample_mapping"].cpu().numpy()
         if return_text:

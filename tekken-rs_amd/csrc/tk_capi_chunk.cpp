@@ -14,12 +14,8 @@ static int chunk_check_levels(tk_ctx* c, uint32_t levels) {
 static int chunk_check_opts(tk_ctx* c, const tk_chunk_opts* o) {
     if (!o) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
     if (o->flags & ~(uint32_t)TK_CHUNK_ALL_FLAGS) { c->err = "unknown chunk flag"; return TK_ERR_INVALID_ARG; }
-    if (o->max_length == 0) { c->err = "chunks need a max_length"; return TK_ERR_INVALID_ARG; }
-    if (o->max_length > TK_LAYOUT_MAX_ROW) { c->err = "max_length " + std::to_string(o->max_length) + " is beyond 2^31 - 1"; return TK_ERR_INVALID_ARG; }
-    if ((uint64_t)o->keep_head + o->keep_tail >= o->max_length) {
-        c->err = "keep_head + keep_tail leave no room for text in max_length " + std::to_string(o->max_length);
-        return TK_ERR_INVALID_ARG;
-    }
+    const int rc = rowfill_check_opts(c, "chunks", o);
+    if (rc != TK_OK) return rc;
     const uint32_t cap = o->max_length - o->keep_head - o->keep_tail;
     if (o->min_length == 0 || o->min_length > cap) {
         c->err = "min_length " + std::to_string(o->min_length) + " is not in 1 .. " + std::to_string(cap) + ", the body ids of a chunk";
@@ -31,19 +27,14 @@ static int chunk_check_opts(tk_ctx* c, const tk_chunk_opts* o) {
     }
     return chunk_check_levels(c, o->levels);
 }
-// the options of an entry that encodes first: BOS / EOS are what every chunk repeats
-static int chunk_encode_opts(tk_ctx* c, const tk_chunk_opts* opts, int add_bos, int add_eos, tk_chunk_opts* o) {
-    *o = *opts;
-    o->keep_head = add_bos ? 1u : 0u;
-    o->keep_tail = add_eos ? 1u : 0u;
-    return chunk_check_opts(c, o);
-}
-static uint64_t round_up(uint64_t L, uint64_t m) { return m ? (L + m - 1) / m * m : L; }
+static constexpr auto chunk_encode_opts = rowfill_encode_opts<tk_chunk_opts, chunk_check_opts>;
 
-static int chunk_events(tk_ctx* c) {
-    for (Event& ev : c->chunk.ev)
-        if (!ev.h) TK_HIP(c, hipEventCreate(&ev.h));
-    return TK_OK;
+static hipError_t chunk_events(tk_ctx* c) {
+    for (Event& ev : c->chunk.ev) {
+        const hipError_t e = ev.h ? hipSuccess : hipEventCreate(&ev.h);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // The level bytes of ids on the device into c->chunk.lev, on s (one wait).  The caller holds c->mu; the mask is known.
@@ -55,7 +46,7 @@ static int run_levels(tk_ctx* c, const uint32_t* d_spans, const uint64_t* d_id_o
     if (rc != TK_OK) return rc;
     if (n_docs == 0 && n_ids) { c->err = "chunks: ids without a document"; return TK_ERR_INVALID_ARG; }
     TK_HIP(c, b.lev.reserve(n_ids + 16));
-    if ((rc = chunk_events(c)) != TK_OK) return rc;
+    TK_HIP(c, chunk_events(c));
     if (n_docs == 0 || n_ids == 0) return TK_OK;
     TkChunkArgs a;
     memset(&a, 0, sizeof(a));
@@ -81,9 +72,9 @@ static int run_levels(tk_ctx* c, const uint32_t* d_spans, const uint64_t* d_id_o
 }
 
 // The chunk pass over ids and level bytes on the device into the context's c->chunk buffers; *out gets the device pointers.  The
-// first walk's counts and their scan go to work buffers; ONE read (W, the longest document, n_split, the level counts) sizes the
-// tensors, and only once the sizes are accepted is anything of an earlier result touched (the scan becomes doc_windows by a swap of
-// the two buffers).  One wait ends the call.  The caller holds c->mu.
+// tensors are sized by the three steps of tk_capi_layout.h, the first walk being the counts kernel (ONE read: W, the longest document,
+// n_split, the level counts), and only once the sizes are accepted is anything of an earlier result touched (rowfill_outputs).  One
+// wait ends the call.  The caller holds c->mu.
 static int run_chunk(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, const uint8_t* d_lev,
                      const uint32_t* d_spans, const tk_chunk_opts* o, hipStream_t s, tk_chunk* out) {
     ChunkBufs& b = c->chunk;
@@ -96,72 +87,32 @@ static int run_chunk(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
                spans = (o->flags & TK_CHUNK_SPANS) != 0, bytes = (o->flags & TK_CHUNK_BYTES) != 0;
     if ((spans || bytes) && !d_spans) { c->err = "TK_CHUNK_SPANS and TK_CHUNK_BYTES need a spans buffer"; return TK_ERR_INVALID_ARG; }
     if (n_ids && !d_lev) { c->err = "chunks: ids without a level buffer"; return TK_ERR_INVALID_ARG; }
-    if (fixed && round_up(o->max_length, o->multiple_of) > TK_LAYOUT_MAX_ROW) {
-        c->err = "chunks: max_length rounded up to a multiple of " + std::to_string(o->multiple_of) + " is beyond 2^31 - 1";
-        return TK_ERR_INVALID_ARG;
-    }
-    TK_HIP(c, b.stat.reserve(64));
-    TK_HIP(c, b.cnt.reserve(n_docs * 4 + 16));
-    TK_HIP(c, b.dw_next.reserve((n_docs + 1) * 8));
-    TK_HIP(c, b.bsum.reserve(scan_workspace_bytes(n_docs)));
-    if ((rc = chunk_events(c)) != TK_OK) return rc;
+    if ((rc = layout_check_fixed_len(c, "chunks", fixed, o->max_length, o->multiple_of)) != TK_OK) return rc;
     TkChunkArgs a;
     memset(&a, 0, sizeof(a));
-    a.ids = d_ids;
-    a.id_offs = d_id_offs;
-    a.in_spans = d_spans;
+    rowfill_inputs(a, d_ids, d_id_offs, d_spans, n_docs, o);
     a.lev = d_lev;
-    a.n_docs = n_docs;
-    a.max_len = o->max_length;
     a.min_len = o->min_length;
     a.overlap = o->overlap;
-    a.keep_head = o->keep_head;
-    a.keep_tail = o->keep_tail;
-    a.pad_id = o->pad_id;
-    a.counts = (uint32_t*)b.cnt.p;
-    a.stat = (unsigned long long*)b.stat.p;
-    unsigned long long stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // the longest document | the split ones | the cuts at levels 0 .. 5
-    uint64_t W = 0;
-    if (n_docs == 0) {
-        TK_HIP(c, hipMemsetAsync(b.dw_next.p, 0, 8, s));
-    } else {
-        TK_HIP(c, hipMemsetAsync(a.stat, 0, 64, s));
-        TK_HIP(c, hipEventRecord(b.ev[2], s));
-        TK_HIP(c, tk_launch_chunk_walk(a, 0, s));
-        if ((rc = scan_u32(c, b.bsum, a.counts, n_docs, (uint64_t*)b.dw_next.p, s)) != TK_OK) return rc;
-        TK_HIP(c, hipEventRecord(b.ev[3], s));
-        TK_HIP(c, hipMemcpyAsync(&W, (const uint64_t*)b.dw_next.p + n_docs, 8, hipMemcpyDeviceToHost, s));
-        TK_HIP(c, hipMemcpyAsync(stat, a.stat, 64, hipMemcpyDeviceToHost, s));
-    }
-    TK_HIP(c, hipStreamSynchronize(s));
+    unsigned long long stat[8];                     // the longest document | the split ones | the cuts at levels 0 .. 5
+    uint64_t W, L;
+    rc = layout_count_rows(c, n_docs, b.stat, b.cnt, b.dw_next, b.bsum, stat, 8, s, [&](uint32_t* counts, unsigned long long* d_stat) {
+        a.counts = counts;
+        a.stat = d_stat;
+        hipError_t e = chunk_events(c);             // (behind the work buffers, as every resource of the call)
+        if (e == hipSuccess) e = hipEventRecord(b.ev[2], s);
+        return e != hipSuccess ? e : tk_launch_chunk_walk(a, 0, s);
+    }, &W, &b.ev[3].h);
+    if (rc != TK_OK) return rc;
     if (stat[0] >= 0xFFFFFFFFull) { c->err = "chunks: a document reaches 2^32 - 1 ids (window_start is uint32)"; return TK_ERR_INVALID_ARG; }
-    const uint64_t L = round_up(fixed || stat[0] > o->max_length ? o->max_length : stat[0], o->multiple_of);
-    if (L > TK_LAYOUT_MAX_ROW || W >= (1ull << 32) || (W && L > TK_LAYOUT_MAX_ELEMS / W)) {
-        c->err = "chunks: " + std::to_string(W) + " rows of " + std::to_string(L) + " elements are beyond what one tensor can hold";
-        return TK_ERR_INVALID_ARG;
-    }
-    const uint64_t elems = W * L;
-    TK_HIP(c, b.ids.reserve(elems * (i64 ? 8 : 4) + 16));
-    if (mask) TK_HIP(c, b.mask.reserve(elems + 16));
-    if (spans) TK_HIP(c, b.spans.reserve(elems * 8 + 16));
-    TK_HIP(c, b.len.reserve(W * 4 + 16));
-    TK_HIP(c, b.doc.reserve(W * 4 + 16));
-    TK_HIP(c, b.start.reserve(W * 4 + 16));
+    rc = layout_row_len(c, "chunks", fixed, stat[0] < o->max_length ? stat[0] : o->max_length, o->max_length, o->multiple_of, W, &L);
+    if (rc != TK_OK) return rc;
     TK_HIP(c, b.cut.reserve(W + 16));
     if (bytes) TK_HIP(c, b.cbytes.reserve(W * 8 + 16));
     TK_HIP(c, b.lcounts.reserve(64));
     TK_HIP(c, b.rec.reserve(W * sizeof(TkChunkRec) + 16));
-    std::swap(b.dw, b.dw_next);
-    a.row_len = (uint32_t)L;
-    a.n_rows = W;
-    a.doc_windows = (const uint64_t*)b.dw.p;
+    if ((rc = rowfill_outputs(c, b, a, W, L, i64, mask, spans)) != TK_OK) return rc;
     a.rec = (TkChunkRec*)b.rec.p;
-    a.out = b.ids.p;
-    a.mask = mask ? (uint8_t*)b.mask.p : nullptr;
-    a.out_spans = spans ? (uint32_t*)b.spans.p : nullptr;
-    a.lengths = (uint32_t*)b.len.p;
-    a.window_doc = (uint32_t*)b.doc.p;
-    a.window_start = (uint32_t*)b.start.p;
     a.cut_level = (uint8_t*)b.cut.p;
     a.chunk_bytes = bytes ? (uint32_t*)b.cbytes.p : nullptr;
     if (n_docs == 0) {
@@ -182,20 +133,10 @@ static int run_chunk(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
         (void)hipEventElapsedTime(&b.ms[2], b.ev[5], b.ev[6]);
         b.ms[1] = first + second;
     }
-    out->input_ids = b.ids.p;
-    out->mask = a.mask;
-    out->lengths = a.lengths;
-    out->window_doc = a.window_doc;
-    out->window_start = a.window_start;
-    out->doc_windows = (uint64_t*)b.dw.p;
-    out->spans = a.out_spans;
+    rowfill_result(a, stat[1], out);
     out->cut_level = a.cut_level;
     out->chunk_bytes = a.chunk_bytes;
     out->level_counts = (uint64_t*)b.lcounts.p;
-    out->n_docs = n_docs;
-    out->n_windows = W;
-    out->row_len = L;
-    out->n_split = stat[1];
     return TK_OK;
 }
 

@@ -31,10 +31,6 @@ static int dense_encode_opts(tk_ctx* c, const tk_dense_opts* opts, int add_bos, 
     }
     return TK_OK;
 }
-static int dense_too_large(tk_ctx* c, uint64_t n_docs, uint64_t row_len) {
-    c->err = "dense: " + std::to_string(n_docs) + " rows of " + std::to_string(row_len) + " elements are beyond what one tensor can hold";
-    return TK_ERR_INVALID_ARG;
-}
 
 // The dense pass over ids on the device into the context's c->dense buffers; *out gets the device pointers.  Longest-row mode: one
 // reduction over the id offsets and one 8-byte read size the tensor; FIXED: no read before the launch.  One wait at the end
@@ -56,8 +52,8 @@ static int run_dense(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs
         TK_HIP(c, hipStreamSynchronize(s));
         L = o->max_length && longest > o->max_length ? o->max_length : longest;
     }
-    if (o->multiple_of) L = (L + o->multiple_of - 1) / o->multiple_of * o->multiple_of;
-    if (L > TK_LAYOUT_MAX_ROW || (n_docs && L > TK_LAYOUT_MAX_ELEMS / n_docs)) return dense_too_large(c, n_docs, L);
+    L = round_up(L, o->multiple_of);
+    if (L > TK_LAYOUT_MAX_ROW || (n_docs && L > TK_LAYOUT_MAX_ELEMS / n_docs)) return layout_too_large(c, "dense", n_docs, L);
     const uint64_t elems = n_docs * L;
     TK_HIP(c, c->dense.ids.reserve(elems * (i64 ? 8 : 4) + 16));
     if (mask) TK_HIP(c, c->dense.mask.reserve(elems + 16));
@@ -127,7 +123,7 @@ extern "C" int tk_ragged_from_dense_device(tk_ctx* c, const void* d_dense, uint6
     TK_ENTRY(c);
     if (flags & ~(TK_DENSE_I64 | TK_DENSE_PAD_LEFT)) { c->err = "unknown dense flag"; return TK_ERR_INVALID_ARG; }
     if ((!d_dense && n_docs && row_len) || !d_ids || !d_id_offsets || !n_ids) { c->err = "null argument"; return TK_ERR_INVALID_ARG; }
-    if (n_docs >= 0xFFFFFFF0ull || row_len > TK_LAYOUT_MAX_ROW || (n_docs && row_len > TK_LAYOUT_MAX_ELEMS / n_docs)) return dense_too_large(c, n_docs, row_len);
+    if (n_docs >= 0xFFFFFFF0ull || row_len > TK_LAYOUT_MAX_ROW || (n_docs && row_len > TK_LAYOUT_MAX_ELEMS / n_docs)) return layout_too_large(c, "dense", n_docs, row_len);
     TK_HIP(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)hip_stream;
     const int i64 = (flags & TK_DENSE_I64) != 0;

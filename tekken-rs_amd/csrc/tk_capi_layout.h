@@ -1,6 +1,8 @@
 // tk_capi_layout.h -- what the host files of the layout passes (tk_capi_dense / _seqpack / _join / _window / _chunk / _rowfit / _regroup / _pair.cpp) share, and
 // only they include: ONE description of the outputs of each result struct, from which tk_free_<pass> and the copy-out of the host
-// entries are made, and the three entries around a pass (ids on the device | text on the device | text on the host) written once.
+// entries are made, the sizing of a tensor of rows (the refusals, and the counts / scan / one read of the window, chunk and pair
+// passes), what the window and chunk passes share beyond that, and the three entries around a pass (ids on the device | text on the
+// device | text on the host) written once.
 // (tk_capi_words.cpp, tk_capi_specials.cpp, tk_capi_fim.cpp and tk_capi_noise.cpp take the descriptions of tk_words / tk_specials /
 // tk_fim / tk_noise_replace / tk_noise_spans from here
 // and have entries of their own: they take the text, or stand in front of encode.)
@@ -145,6 +147,124 @@ template <class R> static inline int layout_copy_out(tk_ctx* c, const R& dev, ui
     layout_outputs(r, esz, n_docs, [&](auto*& p, uint64_t, bool) { p = (std::remove_reference_t<decltype(p)>)h[n++].host; });
     *out = r;
     return TK_OK;
+}
+
+// ---- the sizing of a tensor of rows ----
+static inline uint64_t round_up(uint64_t L, uint64_t m) { return m ? (L + m - 1) / m * m : L; }
+// what every pass says of a tensor it cannot make; noun: "dense", "windows", ...
+static inline int layout_too_large(tk_ctx* c, const char* noun, uint64_t n_rows, uint64_t row_len) {
+    c->err = std::string(noun) + ": " + std::to_string(n_rows) + " rows of " + std::to_string(row_len) + " elements are beyond what one tensor can hold";
+    return TK_ERR_INVALID_ARG;
+}
+// The passes in which an owner (a document, a pair) gives w rows -- window, chunk, pair -- size their tensors in three steps, and
+// touch nothing of an earlier result before the third has gone through (the pass then swaps `next` in as its doc_windows):
+// 1. before anything is enqueued: a fixed row length that cannot be
+static inline int layout_check_fixed_len(tk_ctx* c, const char* noun, bool fixed, uint64_t max_length, uint64_t multiple_of) {
+    if (!fixed || round_up(max_length, multiple_of) <= TK_LAYOUT_MAX_ROW) return TK_OK;
+    c->err = std::string(noun) + ": max_length rounded up to a multiple of " + std::to_string(multiple_of) + " is beyond 2^31 - 1";
+    return TK_ERR_INVALID_ARG;
+}
+// 2. the work buffers, the pass's counts kernel -- counts_kernel(counts, d_stat) enqueues it on s: counts[n] and n_stat statistics
+// words, zeroed here --, the scan of the counts into `next`, and ONE read with one wait: *W = next[n], the rows, and stat[0 .. n_stat).
+// No owner: nothing is launched, next[0] = 0 and everything read is 0.  scanned: an event recorded behind the scan (one that
+// counts_kernel may have created), or null
+template <class K>
+static inline int layout_count_rows(tk_ctx* c, uint64_t n, DevBuf& d_stat, DevBuf& cnt, DevBuf& next, DevBuf& bsum, unsigned long long* stat,
+                                    size_t n_stat, hipStream_t s, K counts_kernel, uint64_t* W, const hipEvent_t* scanned = nullptr) {
+    TK_HIP(c, d_stat.reserve(64));
+    TK_HIP(c, cnt.reserve(n * 4 + 16));
+    TK_HIP(c, next.reserve((n + 1) * 8));
+    TK_HIP(c, bsum.reserve(scan_workspace_bytes(n)));
+    *W = 0;
+    memset(stat, 0, n_stat * 8);
+    if (n == 0) {
+        TK_HIP(c, hipMemsetAsync(next.p, 0, 8, s));
+    } else {
+        TK_HIP(c, hipMemsetAsync(d_stat.p, 0, n_stat * 8, s));
+        TK_HIP(c, counts_kernel((uint32_t*)cnt.p, (unsigned long long*)d_stat.p));
+        const int rc = scan_u32(c, bsum, (const uint32_t*)cnt.p, n, (uint64_t*)next.p, s);
+        if (rc != TK_OK) return rc;
+        if (scanned) TK_HIP(c, hipEventRecord(*scanned, s));
+        TK_HIP(c, hipMemcpyAsync(W, (const uint64_t*)next.p + n, 8, hipMemcpyDeviceToHost, s));
+        TK_HIP(c, hipMemcpyAsync(stat, d_stat.p, n_stat * 8, hipMemcpyDeviceToHost, s));
+    }
+    TK_HIP(c, hipStreamSynchronize(s));
+    return TK_OK;
+}
+// 3. the row length: max_length where `fixed`, else the longest row (window and chunk pass the longest document, clamped to
+// max_length; a pair's row never exceeds it), rounded up to multiple_of; refused where W rows of it are more than a tensor holds
+static inline int layout_row_len(tk_ctx* c, const char* noun, bool fixed, uint64_t longest, uint64_t max_length, uint64_t multiple_of, uint64_t W,
+                                 uint64_t* L) {
+    *L = round_up(fixed ? max_length : longest, multiple_of);
+    if (*L > TK_LAYOUT_MAX_ROW || W >= (1ull << 32) || (W && *L > TK_LAYOUT_MAX_ELEMS / W)) return layout_too_large(c, noun, W, *L);
+    return TK_OK;
+}
+
+// ---- what the window and chunk passes share beyond that (their rows are head | a run of the body | tail of a document:
+// TkRowFillArgs, WindowBufs; O: tk_window_opts / tk_chunk_opts, R: tk_window / tk_chunk) ----
+// the option tests both have, behind the null and flag tests of each; noun: "windows" / "chunks"
+template <class O> static inline int rowfill_check_opts(tk_ctx* c, const char* noun, const O* o) {
+    if (o->max_length == 0) { c->err = std::string(noun) + " need a max_length"; return TK_ERR_INVALID_ARG; }
+    if (o->max_length > TK_LAYOUT_MAX_ROW) { c->err = "max_length " + std::to_string(o->max_length) + " is beyond 2^31 - 1"; return TK_ERR_INVALID_ARG; }
+    if ((uint64_t)o->keep_head + o->keep_tail >= o->max_length) {
+        c->err = "keep_head + keep_tail leave no room for text in max_length " + std::to_string(o->max_length);
+        return TK_ERR_INVALID_ARG;
+    }
+    return TK_OK;
+}
+// the options of an entry that encodes first: BOS / EOS are what every row repeats
+template <class O, int (*check_opts)(tk_ctx*, const O*)>
+static int rowfill_encode_opts(tk_ctx* c, const O* opts, int add_bos, int add_eos, O* o) {
+    *o = *opts;
+    o->keep_head = add_bos ? 1u : 0u;
+    o->keep_tail = add_eos ? 1u : 0u;
+    return check_opts(c, o);
+}
+template <class O>
+static inline void rowfill_inputs(TkRowFillArgs& a, const uint32_t* d_ids, const uint64_t* d_id_offs, const uint32_t* d_spans, uint64_t n_docs, const O* o) {
+    a.ids = d_ids;
+    a.id_offs = d_id_offs;
+    a.in_spans = d_spans;
+    a.n_docs = n_docs;
+    a.max_len = o->max_length;
+    a.keep_head = o->keep_head;
+    a.keep_tail = o->keep_tail;
+    a.pad_id = o->pad_id;
+}
+// The seven outputs both have, for W rows of L elements: reserved, then -- the last thing that can fail is behind -- the scan
+// swapped in as doc_windows, and the fill's arguments point at them.  (The chunk pass reserves its own outputs in front.)
+static inline int rowfill_outputs(tk_ctx* c, WindowBufs& b, TkRowFillArgs& a, uint64_t W, uint64_t L, bool i64, bool mask, bool spans) {
+    const uint64_t elems = W * L;
+    TK_HIP(c, b.ids.reserve(elems * (i64 ? 8 : 4) + 16));
+    if (mask) TK_HIP(c, b.mask.reserve(elems + 16));
+    if (spans) TK_HIP(c, b.spans.reserve(elems * 8 + 16));
+    TK_HIP(c, b.len.reserve(W * 4 + 16));
+    TK_HIP(c, b.doc.reserve(W * 4 + 16));
+    TK_HIP(c, b.start.reserve(W * 4 + 16));
+    std::swap(b.dw, b.dw_next);
+    a.row_len = (uint32_t)L;
+    a.n_rows = W;
+    a.doc_windows = (const uint64_t*)b.dw.p;
+    a.out = b.ids.p;
+    a.mask = mask ? (uint8_t*)b.mask.p : nullptr;
+    a.out_spans = spans ? (uint32_t*)b.spans.p : nullptr;
+    a.lengths = (uint32_t*)b.len.p;
+    a.window_doc = (uint32_t*)b.doc.p;
+    a.window_start = (uint32_t*)b.start.p;
+    return TK_OK;
+}
+template <class R> static inline void rowfill_result(const TkRowFillArgs& a, uint64_t n_split, R* out) {
+    out->input_ids = a.out;
+    out->mask = a.mask;
+    out->lengths = a.lengths;
+    out->window_doc = a.window_doc;
+    out->window_start = a.window_start;
+    out->doc_windows = (uint64_t*)a.doc_windows;
+    out->spans = a.out_spans;
+    out->n_docs = a.n_docs;
+    out->n_windows = a.n_rows;
+    out->row_len = a.row_len;
+    out->n_split = n_split;
 }
 
 // ---- the three entries around a pass, for the passes whose entries take the same arguments (dense, seqpack, window, rowfit, regroup;

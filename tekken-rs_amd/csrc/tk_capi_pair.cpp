@@ -40,12 +40,11 @@ static int pair_encode_opts(tk_ctx* c, const tk_pair_opts* opts, int, int, tk_pa
     if (rc == TK_OK) *o = *opts;
     return rc;
 }
-static uint64_t round_up(uint64_t L, uint64_t m) { return m ? (L + m - 1) / m * m : L; }
 
-// The pair pass over ids on the device into the context's c->pair buffers; *out gets the device pointers.  The per-pair counts and
-// their scan go to work buffers; ONE read (W and the statistics words) sizes the tensors, and only once the sizes are accepted is
-// anything of an earlier result touched (the scan becomes pair_windows by a swap of the two buffers).  One wait ends the call.
-// The caller holds c->mu.
+// The pair pass over ids on the device into the context's c->pair buffers; *out gets the device pointers.  The tensors are sized by
+// the three steps of tk_capi_layout.h (ONE read: W and the statistics words), and only once the sizes are accepted is anything of an
+// earlier result touched (the scan becomes pair_windows by a swap of the two buffers).  One wait ends the call.  The caller holds
+// c->mu.
 static int run_pair(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_parts, uint64_t n_ids, const uint32_t* d_spans,
                     const tk_pair_opts* o, hipStream_t s, tk_pair* out) {
     int rc = pair_check_opts(c, o);
@@ -56,15 +55,8 @@ static int run_pair(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs,
     const uint32_t fl = o->flags;
     const bool fixed = (fl & TK_PAIR_FIXED) != 0, i64 = (fl & TK_PAIR_I64) != 0, spans = (fl & TK_PAIR_SPANS) != 0;
     if (spans && !d_spans) { c->err = "TK_PAIR_SPANS needs a spans buffer"; return TK_ERR_INVALID_ARG; }
-    if (fixed && round_up(o->max_length, o->multiple_of) > TK_LAYOUT_MAX_ROW) {
-        c->err = "pairs: max_length rounded up to a multiple of " + std::to_string(o->multiple_of) + " is beyond 2^31 - 1";
-        return TK_ERR_INVALID_ARG;
-    }
+    if ((rc = layout_check_fixed_len(c, "pairs", fixed, o->max_length, o->multiple_of)) != TK_OK) return rc;
     const uint64_t P = n_parts / 2;
-    TK_HIP(c, c->pair.stat.reserve(64));
-    TK_HIP(c, c->pair.cnt.reserve(P * 4 + 16));
-    TK_HIP(c, c->pair.pw_next.reserve((P + 1) * 8));
-    TK_HIP(c, c->pair.bsum.reserve(scan_workspace_bytes(P)));
     TkPairArgs a;
     memset(&a, 0, sizeof(a));
     a.ids = d_ids;
@@ -82,26 +74,16 @@ static int run_pair(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs,
     a.stride = o->stride;
     a.max_fixed = o->max_fixed ? o->max_fixed : a.cap - 1u;
     a.pad_id = o->pad_id;
-    a.counts = (uint32_t*)c->pair.cnt.p;
-    a.stat = (unsigned long long*)c->pair.stat.p;
-    unsigned long long stat[5] = {0, 0, 0, 0, 0};   // the longest row | truncated | split | fixed side cut | the longest part
-    uint64_t W = 0;
-    if (P == 0) {
-        TK_HIP(c, hipMemsetAsync(c->pair.pw_next.p, 0, 8, s));
-    } else {
-        TK_HIP(c, hipMemsetAsync(a.stat, 0, sizeof(stat), s));
-        TK_HIP(c, tk_launch_pair_counts(a, s));
-        if ((rc = scan_u32(c, c->pair.bsum, a.counts, P, (uint64_t*)c->pair.pw_next.p, s)) != TK_OK) return rc;
-        TK_HIP(c, hipMemcpyAsync(&W, (const uint64_t*)c->pair.pw_next.p + P, 8, hipMemcpyDeviceToHost, s));
-        TK_HIP(c, hipMemcpyAsync(stat, a.stat, sizeof(stat), hipMemcpyDeviceToHost, s));
-    }
-    TK_HIP(c, hipStreamSynchronize(s));
+    unsigned long long stat[5];                     // the longest row | truncated | split | fixed side cut | the longest part
+    uint64_t W, L;
+    rc = layout_count_rows(c, P, c->pair.stat, c->pair.cnt, c->pair.pw_next, c->pair.bsum, stat, 5, s, [&](uint32_t* counts, unsigned long long* d_stat) {
+        a.counts = counts;
+        a.stat = d_stat;
+        return tk_launch_pair_counts(a, s);
+    }, &W);
+    if (rc != TK_OK) return rc;
     if (stat[4] >= 0xFFFFFFFFull) { c->err = "pairs: a part reaches 2^32 - 1 ids (window_start is uint32)"; return TK_ERR_INVALID_ARG; }
-    const uint64_t L = round_up(fixed ? o->max_length : stat[0], o->multiple_of);      // (a row never exceeds max_length)
-    if (L > TK_LAYOUT_MAX_ROW || W >= (1ull << 32) || (W && L > TK_LAYOUT_MAX_ELEMS / W)) {
-        c->err = "pairs: " + std::to_string(W) + " rows of " + std::to_string(L) + " elements are beyond what one tensor can hold";
-        return TK_ERR_INVALID_ARG;
-    }
+    if ((rc = layout_row_len(c, "pairs", fixed, stat[0], o->max_length, o->multiple_of, W, &L)) != TK_OK) return rc;
     const uint64_t elems = W * L;
     TK_HIP(c, c->pair.ids.reserve(elems * (i64 ? 8 : 4) + 16));
     if (fl & TK_PAIR_MASK) TK_HIP(c, c->pair.mask.reserve(elems + 16));

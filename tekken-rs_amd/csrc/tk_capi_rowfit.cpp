@@ -111,10 +111,7 @@ static int run_rowfit(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
             return TK_ERR_INVALID_ARG;
         }
         n_rows = stat[3];
-        if (n_rows > TK_LAYOUT_MAX_ELEMS / L) {
-            c->err = "rowfit: " + std::to_string(n_rows) + " rows of " + std::to_string(L) + " elements are beyond what one tensor can hold";
-            return TK_ERR_INVALID_ARG;
-        }
+        if (n_rows > TK_LAYOUT_MAX_ELEMS / L) return layout_too_large(c, "rowfit", n_rows, L);
         if (want_cu && n_rows * L >= (1ull << 31)) {
             c->err = "rowfit: cu_seqlens is int32 and " + std::to_string(n_rows) + " rows of " + std::to_string(L) + " elements do not fit";
             return TK_ERR_INVALID_ARG;

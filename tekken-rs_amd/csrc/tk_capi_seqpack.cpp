@@ -27,10 +27,7 @@ static int run_seqpack(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_of
                want_seg = (o->flags & TK_SEQPACK_SEGMENTS) != 0, want_cu = (o->flags & TK_SEQPACK_CU_SEQLENS) != 0;
     const uint64_t n_rows = (o->flags & TK_SEQPACK_DROP_LAST) ? n_ids / L : n_ids / L + (n_ids % L != 0);
     const uint64_t n_used = n_ids < n_rows * L ? n_ids : n_rows * L;
-    if (n_rows > TK_LAYOUT_MAX_ELEMS / L) {
-        c->err = "seqpack: " + std::to_string(n_rows) + " rows of " + std::to_string(L) + " elements are beyond what one tensor can hold";
-        return TK_ERR_INVALID_ARG;
-    }
+    if (n_rows > TK_LAYOUT_MAX_ELEMS / L) return layout_too_large(c, "seqpack", n_rows, L);
     if (want_cu && n_used >= (1ull << 31)) {
         c->err = "seqpack: cu_seqlens is int32 and " + std::to_string(n_used) + " ids do not fit";
         return TK_ERR_INVALID_ARG;

@@ -310,21 +310,10 @@ hipError_t tk_launch_chunk_walk(const TkChunkArgs& args, int records, hipStream_
     return hipGetLastError();
 }
 
-template <int I64, int MASK>
-static void tkc_launch2(const TkChunkArgs& a, bool vec, dim3 grid, hipStream_t s) {
-    if (vec) hipLaunchKernelGGL((tk_chunk_kernel<I64, MASK, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((tk_chunk_kernel<I64, MASK, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
-}
-
 hipError_t tk_launch_chunk(const TkChunkArgs& args, int i64, hipStream_t s) {
     TkChunkArgs a = args;
     const TkyRowsGrid rg = tky_rows_shape(a.n_rows, a.row_len, true, a.rows);   // (L == 0: one unit a row, which writes the per-row outputs)
     if (rg.x == 0u) return hipSuccess;
-    const bool vec = a.row_len != 0u && a.row_len % 4u == 0u;
-    const dim3 grid(rg.x, rg.y);
-    if (i64 && a.mask) tkc_launch2<1, 1>(a, vec, grid, s);
-    else if (i64) tkc_launch2<1, 0>(a, vec, grid, s);
-    else if (a.mask) tkc_launch2<0, 1>(a, vec, grid, s);
-    else tkc_launch2<0, 0>(a, vec, grid, s);
+    TKY_LAUNCH_I64_MASK_VEC(tk_chunk_kernel, i64, a.mask, a.row_len != 0u && a.row_len % 4u == 0u, dim3(rg.x, rg.y), s, a);
     return hipGetLastError();
 }

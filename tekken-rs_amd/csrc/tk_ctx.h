@@ -111,11 +111,10 @@ struct JoinBufs { DevBuf ids, offs, labels, pidx, stat, has, cb, start, plocal, 
 // the overlapping windows (tk_window.hip): the tensor, its mask and spans, the per-window arrays, doc_windows; the work arrays
 // (dw_next: the scan that becomes doc_windows once the call is accepted, the counts, the scan workspace, the statistics words)
 struct WindowBufs { DevBuf ids, mask, spans, len, doc, start, dw, dw_next, cnt, bsum, stat; };
-// the boundary-aware chunks (tk_chunk.hip): the window pass's outputs, cut_level, chunk_bytes and level_counts; the work arrays (as
-// the window pass's, and the windows' records); the level bytes of tk_chunk_levels_device and the spans of the entries that encode
-// first
-struct ChunkBufs {
-    DevBuf ids, mask, spans, len, doc, start, dw, cut, cbytes, lcounts, dw_next, cnt, bsum, stat, rec, lev, in_spans;
+// the boundary-aware chunks (tk_chunk.hip): the window pass's outputs and work arrays, and its own: cut_level, chunk_bytes and
+// level_counts; the windows' records; the level bytes of tk_chunk_levels_device and the spans of the entries that encode first
+struct ChunkBufs : WindowBufs {
+    DevBuf cut, cbytes, lcounts, rec, lev, in_spans;
     Event ev[7];                   // the stages of the last chunk call (tk_last_chunk_ms), created at the first one
     float ms[3] = {0.f, 0.f, 0.f}; // levels | walks and scan | fill
 };
@@ -293,7 +292,7 @@ int enter_device(tk_ctx* c, uint64_t n_docs);
 struct CopyOut { const void* dev; size_t bytes; void* host; bool selected = true; };
 int pinned_blocks(tk_ctx* c, CopyOut* a, int n);
 int copy_out(tk_ctx* c, CopyOut* a, int n, const char* what);
-// ---- what the layout passes share (tk_capi_dense / _seqpack / _join / _window / _rowfit / _regroup.cpp; tk_capi_layout.h is theirs alone) ----
+// ---- what the layout passes share (tk_capi_dense / _seqpack / _join / _window / _chunk / _pair / _rowfit / _regroup.cpp; tk_capi_layout.h is theirs alone) ----
 #define TK_LAYOUT_MAX_ROW 0x7FFFFFFFull         /* a row of a tensor stays below 2^31 elements */
 #define TK_LAYOUT_MAX_ELEMS (1ull << 36)        /* rows * row length: 256 GiB of int32, more than the part holds */
 // how an entry with check flags opens: an unknown flag is refused first, then a null argument

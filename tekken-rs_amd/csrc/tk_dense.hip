@@ -129,21 +129,11 @@ __global__ __launch_bounds__(TKY_BLOCK) void tk_ragged_kernel(TkRaggedArgs a, Tk
     }
 }
 
-template <int I64, int MASK>
-static void tkn_launch2(const TkDenseArgs& a, dim3 grid, hipStream_t s) {
-    if (a.row_len % 4u == 0u) hipLaunchKernelGGL((tk_dense_kernel<I64, MASK, 1>), grid, dim3(TKY_BLOCK), 0, s, a);
-    else hipLaunchKernelGGL((tk_dense_kernel<I64, MASK, 0>), grid, dim3(TKY_BLOCK), 0, s, a);
-}
-
 hipError_t tk_launch_dense(const TkDenseArgs& args, int i64, hipStream_t s) {
     TkDenseArgs a = args;
     const TkyRowsGrid rg = tky_rows_shape(a.n_docs, a.row_len, false, a.rows);
     if (rg.x == 0u) return hipSuccess;
-    const dim3 grid(rg.x, rg.y);
-    if (i64 && a.mask) tkn_launch2<1, 1>(a, grid, s);
-    else if (i64) tkn_launch2<1, 0>(a, grid, s);
-    else if (a.mask) tkn_launch2<0, 1>(a, grid, s);
-    else tkn_launch2<0, 0>(a, grid, s);
+    TKY_LAUNCH_I64_MASK_VEC(tk_dense_kernel, i64, a.mask, a.row_len % 4u == 0u, dim3(rg.x, rg.y), s, a);
     return hipGetLastError();
 }
 

@@ -243,13 +243,13 @@ hipError_t tk_launch_seqpack_starts(const TkSeqpackArgs& a, hipStream_t s);   //
 hipError_t tk_launch_seqpack(const TkSeqpackArgs& a, int i64, hipStream_t s); // the tensors; n_rows == 0: nothing is launched
 hipError_t tk_launch_seqpack_cu(const TkSeqpackArgs& a, hipStream_t s);       // cu_seqlens (a.cu != NULL), n_segments, max_seqlen
 
-// ---- overlapping windows for long documents (tk_window.hip) ----
-struct TkWindowArgs {
+// ---- what the arguments of the window and chunk passes share: their rows are head | a run of the body | tail of a document ----
+struct TkRowFillArgs {
     const uint32_t* ids;       // [n_ids] packed token ids of all documents
     const uint64_t* id_offs;   // [n_docs + 1]
-    const uint32_t* in_spans;  // [2 * n_ids] (start, end) per id, or NULL
+    const uint32_t* in_spans;  // [2 * n_ids] (start, end) per id, or NULL (the chunk pass's levels kernel: its input)
     uint64_t n_docs;
-    uint32_t max_len, step;    // T; c - s
+    uint32_t max_len;          // T
     uint32_t keep_head, keep_tail, pad_id;
     uint32_t row_len;          // L (< 2^31; 0: only the per-row outputs are written)
     uint64_t n_rows;           // W (< 2^32)
@@ -261,40 +261,28 @@ struct TkWindowArgs {
     uint32_t* lengths;         // [W]
     uint32_t* window_doc;      // [W]
     uint32_t* window_start;    // [W]
-    unsigned long long* stat;  // [0] longest document, clamped to 2^32 - 1 (atomicMax), [1] += documents with w_d > 1: zeroed by the caller
+    // zeroed by the caller: [0] longest document, clamped to 2^32 - 1 (atomicMax), [1] += documents with w_d > 1; the chunk pass:
+    // [2 .. 8) += the cuts made at level 0 .. 5
+    unsigned long long* stat;
     TkyRows rows;              // the launch shape (tk_rows.h; set by the launcher)
+};
+
+// ---- overlapping windows for long documents (tk_window.hip) ----
+struct TkWindowArgs : TkRowFillArgs {
+    uint32_t step;             // c - s
 };
 hipError_t tk_launch_window_counts(const TkWindowArgs& a, hipStream_t s);   // counts, stat
 hipError_t tk_launch_window(const TkWindowArgs& a, int i64, hipStream_t s); // the outputs; n_rows == 0: nothing is launched
 
 // ---- boundary-aware token-budget chunks (tk_chunk.hip) ----
 struct TkChunkRec { uint32_t start, len, level, pad; };   // a chunk's body run B[start : start + len] and the level of the cut behind it
-struct TkChunkArgs {
-    const uint32_t* ids;       // [n_ids] packed token ids of all documents
-    const uint64_t* id_offs;   // [n_docs + 1]
-    const uint32_t* in_spans;  // [2 * n_ids] (start, end) per id, or NULL (the levels kernel: its input)
+struct TkChunkArgs : TkRowFillArgs {
     const uint8_t* lev;        // [n_ids] the level of the break in front of every id (a byte above 5 reads as 5)
-    uint64_t n_docs;
-    uint32_t max_len, min_len, overlap;   // T; m; o (0 <= o < m <= c = T - h - t)
-    uint32_t keep_head, keep_tail, pad_id;
+    uint32_t min_len, overlap; // m; o (0 <= o < m <= c = T - h - t)
     uint32_t group;            // documents a wave of the walk takes (a power of two <= 64; set by the launcher)
-    uint32_t row_len;          // L (< 2^31; 0: only the per-row outputs are written)
-    uint64_t n_rows;           // W (< 2^32)
-    uint32_t* counts;          // [n_docs] w_d
-    const uint64_t* doc_windows;   // [n_docs + 1] exclusive scan of counts, strictly increasing
     TkChunkRec* rec;           // [W] out of the second walk, in of the fill kernel
-    void* out;                 // [W * L] int32 or int64
-    uint8_t* mask;             // [W * L] or NULL
-    uint32_t* out_spans;       // [W * L * 2] or NULL
-    uint32_t* lengths;         // [W]
-    uint32_t* window_doc;      // [W]
-    uint32_t* window_start;    // [W]
     uint8_t* cut_level;        // [W]
     uint32_t* chunk_bytes;     // [W * 2] or NULL
-    // zeroed by the caller: [0] longest document, clamped to 2^32 - 1 (atomicMax), [1] += documents with w_d > 1, [2 .. 8) += the
-    // cuts made at level 0 .. 5
-    unsigned long long* stat;
-    TkyRows rows;              // the launch shape (tk_rows.h; set by the launcher)
     // the levels kernel alone
     const uint8_t* bytes;      // the text
     const uint64_t* doc_offs;  // [n_docs + 1]

@@ -1,9 +1,10 @@
-// tk_layout.h -- what the layout kernels share (tk_dense.hip, tk_seqpack.hip, tk_join.hip, tk_window.hip, tk_pair.hip,
-// tk_rowfit.hip, tk_regroup.hip: ragged ids into what a model consumes):
+// tk_layout.h -- what the layout kernels share (tk_dense.hip, tk_seqpack.hip, tk_join.hip, tk_window.hip, tk_chunk.hip,
+// tk_pair.hip, tk_rowfit.hip, tk_regroup.hip: ragged ids into what a model consumes; tk_fim.hip, tk_noise.hip and
+// tk_specials.hip, which cut and reorder text or ids in front of them):
 // the 4-wide element access of an int32 / int64 tensor and the 4-wide gather of ids and spans at any dword, the stores of a uint8
 // plane and of span pairs, the clamped length, the searches for "which document / part holds stream position g", the staging of a
 // tile's starts, the block's row group of the row-group launch shape (tk_rows.h) and the owner of a row, the grid size, the
-// I64 x VEC launch and the one-atomic-a-wave tails.  (Names: tky_ -- tkl_ is tk_long_impl.h's.)
+// I64 x VEC and I64 x MASK x VEC launches and the one-atomic-a-wave tails.  (Names: tky_ -- tkl_ is tk_long_impl.h's.)
 #ifndef TK_LAYOUT_H
 #define TK_LAYOUT_H
 #include <hip/hip_runtime.h>
@@ -32,6 +33,20 @@ static inline uint32_t tky_blocks(uint64_t n, uint64_t cap, uint64_t per = TKY_B
         else if (i64) hipLaunchKernelGGL((kernel<1, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__);       \
         else if (vec) hipLaunchKernelGGL((kernel<0, 1>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__);       \
         else hipLaunchKernelGGL((kernel<0, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__);                \
+    } while (0)
+// kernel<I64, MASK, VEC> by three
+#define TKY_LAUNCH_I64_MASK_VEC(kernel, i64, mask, vec, grid, s, ...)                                       \
+    do {                                                                                                    \
+        switch (((i64) ? 4 : 0) | ((mask) ? 2 : 0) | ((vec) ? 1 : 0)) {                                     \
+        case 7: hipLaunchKernelGGL((kernel<1, 1, 1>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); break;     \
+        case 6: hipLaunchKernelGGL((kernel<1, 1, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); break;     \
+        case 5: hipLaunchKernelGGL((kernel<1, 0, 1>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); break;     \
+        case 4: hipLaunchKernelGGL((kernel<1, 0, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); break;     \
+        case 3: hipLaunchKernelGGL((kernel<0, 1, 1>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); break;     \
+        case 2: hipLaunchKernelGGL((kernel<0, 1, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); break;     \
+        case 1: hipLaunchKernelGGL((kernel<0, 0, 1>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__); break;     \
+        default: hipLaunchKernelGGL((kernel<0, 0, 0>), grid, dim3(TKY_BLOCK), 0, s, __VA_ARGS__);           \
+        }                                                                                                   \
     } while (0)
 
 // a length as the kernels carry it: clamped to 2^32 - 1 (the host refuses a clamped one before anything derived from it is used)

@@ -11,7 +11,8 @@ from helpers import dev, on_device, to_host
 from test_chunk_cpu import (ALL_LEVELS, BYTES, CUT_LAST, FIXED, I64, LINE, MASK, PARAGRAPH, SENTENCE, SPANS, TOKEN, WORD, expected_chunks,
                             expected_levels_batch, refused_cases)
 from test_gpu_spans import pack, sweep_docs
-from test_gpu_window import made_up
+from test_gpu_window import fetch as window_fetch
+from test_gpu_window import long_row_docs, made_up
 
 pytestmark = pytest.mark.gpu
 
@@ -134,8 +135,45 @@ def case(shape):
     return _cases[shape]
 
 
+ROWS_TILE = 2048                   # csrc/tk_rows.h TKY_ROWS_TILE: units of a block's row group
+OWNERS_CAP = 1024                  # csrc/tk_layout.h TKY_CAP: owners of a row group that LDS holds
+UNSTAGED = (4, 2, 0, 0, 0)         # L = 4: one unit a row, ROWS_TILE rows a block
+_unstaged = []
+
+
+def unstaged_case():
+    """(ids, oo, lev, spans, expected_chunks of them): 3 000 one-id documents between two split ones, at UNSTAGED."""
+    if not _unstaged:
+        T, m, o, h, t = UNSTAGED
+        rng = np.random.default_rng(63)
+        oo = np.concatenate([[0], np.cumsum([9] + [1] * 3000 + [9])]).astype(np.int64)
+        ids = rng.integers(0, 2**31 - 1, int(oo[-1])).astype(np.uint32)
+        lev = rng.integers(0, 6, len(ids)).astype(np.uint8)
+        g = np.arange(len(ids), dtype=np.uint64)
+        sp = np.stack([(g * 2 + 1) & 0xFFFFFFFF, (g * 3 + 7) & 0xFFFFFFFF], axis=1).astype(np.uint32)
+        _unstaged.append((ids, oo, lev, sp, expected_chunks(ids, oo, lev, T, m, o, h, t, 0, PAD, FIXED | MASK | SPANS | BYTES, sp)))
+    return _unstaged[0]
+
+
+def most_owners_of_a_row_group(e):
+    """The largest number of documents that start inside one row group of the fill, behind the group's first row: what
+    TkyRowOwners stages unless it is more than OWNERS_CAP.  The shape is csrc/tk_rows.h tky_rows_shape's."""
+    L, W = e["row_len"], e["n_windows"]
+    units = L // 4 if L and L % 4 == 0 else max(L, 1)
+    rb = ROWS_TILE // units if units <= ROWS_TILE else 1
+    dw = e["doc_windows"].astype(np.int64)[:-1]
+    return max((int(np.sum((dw > r0) & (dw < min(r0 + rb, W)))) for r0 in range(0, W, rb)), default=0)
+
+
 def test_the_case_set_holds_what_it_is_for():
+    """From expected_chunks's results alone.  The fill's unstaged branch (more than 1 024 documents start inside one row group)
+    needs one unit a row, L = 4 or L = 1, which no shape of SHAPES has at any multiple_of the tests use: over made_up()'s block of
+    3 000 one-id documents their most are 1 023 documents at L = 8 (T = 6 and 7 at multiple_of 4: 1 024 rows a block), 340 at
+    L = 6, 291 at L = 7, 127 at L = 64 and 15 at L = 512, and no other test of this file has more (L = 16; L = 0 over 5 rows).  The
+    window tests reach it with the same block at T = 4.  unstaged_case() is here for it."""
     seen = set()
+    assert most_owners_of_a_row_group(unstaged_case()[4]) > OWNERS_CAP
+    seen.add("a row group of more than 1 024 documents")
     for shape in SHAPES:
         T, m, o, h, t = shape
         ids, oo, lev, sp, e = case(shape)
@@ -148,7 +186,9 @@ def test_the_case_set_holds_what_it_is_for():
             seen.add("L % 4 != 0")
         if np.all(e["level_counts"] > 0):
             seen.add("a cut at every level")
-    assert seen >= {("range", r) for r in (1, 63, 64, 65, 129)} | {("overlap", o) for o in (0, 1, 63, 64)} | {"L % 4 != 0", "a cut at every level"}
+        assert most_owners_of_a_row_group(e) <= OWNERS_CAP
+    assert seen >= {("range", r) for r in (1, 63, 64, 65, 129)} | {("overlap", o) for o in (0, 1, 63, 64)} | {"L % 4 != 0", "a cut at every level",
+                                                                                                             "a row group of more than 1 024 documents"}
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -218,6 +258,43 @@ def test_all_token_levels_equal_the_window_pass(tk, eng_bench, shape):
                 helpers.assert_array_same(got[k], to_host(view, shp, dty), (shape, level, m, flags, k))
             split = np.diff(got["doc_windows"].astype(np.int64)) > 1
             assert got["level_counts"].tolist() == [int(got["n_windows"] - len(split)) if l == level else 0 for l in range(6)]
+
+
+def test_more_documents_in_a_row_group_than_lds_holds(tk, eng_bench):
+    """The fill's unstaged branch: rows of one unit, 2 048 a block, over one-id documents -- the first row group has more than
+    1 024 of them and reads their starts from global memory, the last one stages its own."""
+    T, m, o, h, t = UNSTAGED
+    ids, oo, lev, sp, exp = unstaged_case()
+    assert exp["row_len"] == 4 and exp["n_split"] == 2
+    d_ids, d_oo = on_device(ids, oo)
+    d_lev, d_sp = dev(lev, np.uint8), dev(sp.reshape(-1), np.uint32)
+    for fl in (FIXED | MASK | SPANS | BYTES, FIXED | MASK | SPANS | BYTES | I64):
+        _, got = chunks_of(eng_bench, d_ids, d_oo, len(ids), d_lev, T, m, o, h, t, 0, fl, d_sp)
+        assert_same({**got, "input_ids": got["input_ids"].astype(np.int32)}, exp, fl)
+
+
+def test_row_longer_than_a_block_tile(tk, eng_bench):
+    """T = 9 001 through the chunk fill: the units of one row are split over blockIdx.y, element by element (L = 9 001) and in units
+    of 4 (L = 9 004).  Every level TOKEN and min_length = c: the chunks are the windows at stride = overlap, and every output the
+    two passes share is compared with the window pass's too, the spans among them."""
+    T, o, h, t = 9001, 100, 2, 3
+    ids, oo, sp = long_row_docs()
+    lev = np.full(len(ids), TOKEN, np.uint8)
+    d_ids, d_oo = on_device(ids, oo)
+    d_lev, d_sp = dev(lev, np.uint8), dev(sp.reshape(-1), np.uint32)
+    flags = FIXED | MASK | SPANS | BYTES
+    for mo in (0, 4):
+        exp = expected_chunks(ids, oo, lev, T, T - h - t, o, h, t, mo, PAD, flags, sp)
+        assert exp["row_len"] == T + 3 * (mo == 4) and exp["lengths"].max() == T and exp["n_split"] > 0
+        for fl in (flags, flags | I64):
+            _, got = chunks_of(eng_bench, d_ids, d_oo, len(ids), d_lev, T, T - h - t, o, h, t, mo, fl, d_sp)
+            assert_same({**got, "input_ids": got["input_ids"].astype(np.int32)}, exp, (mo, fl))
+            wfl = fl & ~BYTES                           # (the two passes number FIXED, I64, MASK and SPANS alike)
+            w = window_fetch(eng_bench.window_from_ids_device(d_ids.data_ptr(), d_oo.data_ptr(), len(oo) - 1, len(ids), T, o, mo, PAD, h, t, wfl,
+                                                              d_sp.data_ptr(), stream()))
+            assert (got["n_windows"], got["n_split"], got["row_len"]) == (w["n_windows"], w["n_split"], w["row_len"])
+            for k in ("input_ids", "mask", "lengths", "window_doc", "window_start", "doc_windows", "spans"):
+                helpers.assert_array_same(got[k], w[k], (mo, fl, k))
 
 
 # ---- the levels kernel ----

@@ -210,15 +210,22 @@ def test_spans_output_on_made_up_spans(tk, eng_bench, shape):
         assert_same(got, exp, (shape, m, flags))
 
 
-def test_row_longer_than_a_block_tile(tk, eng_bench):
-    """T = 9 001: the units of one row are split over blockIdx.y, element by element (L = 9 001) and in units of 4 (L = 9 004)."""
+def long_row_docs():
+    """(ids, oo, spans) of 14 documents around 9 001 ids -- shorter, exactly, one more, more than twice as many --, about 93 000
+    ids, with made-up spans."""
     rng = np.random.default_rng(53)
-    T, s = 9001, 100
     n = [3000, 20000, 0, 5, 9000, 9001, 10, 9002, 20000, 120, 4500, 8998, 1, 1]
     oo = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
     ids = rng.integers(0, 2**31 - 1, int(oo[-1])).astype(np.uint32)
     g = np.arange(len(ids), dtype=np.uint64)
     sp = np.stack([(g * 2 + 1) & 0xFFFFFFFF, (g * 3 + 7) & 0xFFFFFFFF], axis=1).astype(np.uint32)   # index-derived: a wrong source index shows
+    return ids, oo, sp
+
+
+def test_row_longer_than_a_block_tile(tk, eng_bench):
+    """T = 9 001: the units of one row are split over blockIdx.y, element by element (L = 9 001) and in units of 4 (L = 9 004)."""
+    T, s = 9001, 100
+    ids, oo, sp = long_row_docs()
     d_ids, d_oo = on_device(ids, oo)
     d_sp = dev(sp.reshape(-1), np.uint32)
     for m in (0, 4):
