@@ -1,7 +1,7 @@
 // tk_flat_lane.h -- the flat path's lane layout (overview: tk_flat_impl.h): LDS words of a wave, mask algebra, classification, split rules
 #ifndef TK_FLAT_LANE_H
 #define TK_FLAT_LANE_H
-#include "tk_encode_impl.h"
+#include "tk_lookup.h"
 #include "tk_flat_args.h"
 
 #define TKF_WM 0xFFFFFFFFu

@@ -27,7 +27,8 @@
 
 #include "tk_kernels.h"
 #include "tk_wave_hip.h"
-#include "tk_encode_impl.h"
+#include "tk_match.h"
+#include "tk_piece_impl.h"
 #include "tk_long_impl.h"
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -10,7 +10,7 @@
 #define TK_LONG_IMPL_H
 #include <stdint.h>
 
-#include "tk_encode_impl.h"
+#include "tk_piece_impl.h"
 
 #define TKL_THREADS 1024
 #define TKL_WAVES 16

@@ -1,7 +1,8 @@
 // tk_merge_impl.h -- behind the flat kernel (overview: tk_flat_impl.h): the long-piece records, the merge of the queued misses, the memo log
 #ifndef TK_MERGE_IMPL_H
 #define TK_MERGE_IMPL_H
-#include "tk_encode_impl.h"
+#include "tk_match.h"
+#include "tk_piece_impl.h"
 #include "tk_flat_args.h"
 
 // ------------------------------------------------------------------------------------------

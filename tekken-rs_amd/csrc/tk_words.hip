@@ -37,7 +37,7 @@
 #include "tk_dpp_scan.h"
 #include "tk_kernels.h"
 #include "tk_wave_hip.h"
-#include "tk_encode_impl.h"
+#include "tk_match.h"
 
 #define TKW_BLOCK 1024        /* as TKS_BLOCK: 16 waves share one LDS copy of the length table */
 #define TKW_DOCS TK_DECODE_GROUP_DOCS
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(TKW_BLOCK, 8) void tk_words_kernel(TkWordsArgs a) {
 }
 
 // The piece starts under the JSON pattern (the context after tk_ctx_set_pattern(ctx, 1)): one wave per document, piece by
-// piece with the sequential matcher that pass 2 of the encode pipeline runs in that mode (tk_match_end2, tk_encode_impl.h) --
+// piece with the sequential matcher that pass 2 of the encode pipeline runs in that mode (tk_match_end2, tk_match.h) --
 // the split-only instantiation of the encode kernel knows the hard-coded pattern alone.  flags is zeroed by the caller.
 __global__ __launch_bounds__(256) void tk_words_split_json_kernel(TkTablesView t, const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ doc_offs,
                                                                   uint64_t n_docs, uint8_t* __restrict__ flags) {

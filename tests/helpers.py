@@ -66,6 +66,13 @@ def walked_lead_byte_docs():
     return docs
 
 
+def window_cut_docs():
+    """A two-, three- and four-byte char that the END of the per-document path's first 64-byte window cuts, or just does not
+    (tk_encode_impl.h step 1 trims the window to the last whole char, the slide starts the next window on it): the char behind
+    61 .. 64 ASCII letters, then more of it and a CR LF behind a class-O char for the window after the slide."""
+    return [b"a" * k + ch.encode("utf-8") + b" b " + ch.encode("utf-8") * 3 + b"\r\n x" for k in range(61, 65) for ch in ("é", "中", "\U0001f680")]
+
+
 def oracle_for(v):
     import tk_oracle
     return tk_oracle.Oracle(v["tokens"], v["num_special"], v["bos"], v["eos"])

@@ -106,7 +106,9 @@ def test_both_pipelines(tk, test_vocab, monkeypatch):
     the flat one hands documents with very long runs / pieces back and says how many."""
     orc = helpers.oracle_for(test_vocab)
     # (a white-space run across a region end and a long digit run are always handed back; long letter runs are cut: step 4b)
-    docs = helpers.mixed_docs(120, 40, 200, max_len=40000) + helpers.random_unicode_docs(300) + [b"a b" + b" " * 3000 + b"x", b"1" * 2500]
+    # (and a char cut by the end of the per-document path's first window: step 1 of tk_encode_doc, then the slide)
+    docs = (helpers.mixed_docs(120, 40, 200, max_len=40000) + helpers.random_unicode_docs(300) + [b"a b" + b" " * 3000 + b"x", b"1" * 2500] +
+            helpers.window_cut_docs())
     exp = [orc.encode(d, True, True) for d in docs]
     monkeypatch.setenv("TK_PIPELINE", "flat")
     flat = tk.Engine(test_vocab["tokens"], test_vocab["num_special"], test_vocab["bos"], test_vocab["eos"], device=0)
@@ -859,6 +861,9 @@ def test_long_pieces_merged_in_rounds(tk, test_vocab, bench_vocab, monkeypatch):
             b" " * 3000 + b"x", b"!" * 2500, b"a" * 8191 + b"b" + b"a" * 8192, b"hello world " * 50 + b"k" * 2050 + b" and " + b"j" * 3000]
     for n in (66, 129, 257, 2047, 2049, 16383, 16385):
         docs.append(bytes(rng.choice(b"ab") for _ in range(n)))
+    # beyond TK_LONG_MAX no rounds: one wave's cooperative merge with its block minima in scratch memory (more than 512 blocks)
+    rng2 = random.Random(78)
+    docs += [b"a" * 32769, bytes(rng2.choice(letters.encode()) for _ in range(32769))]
     for v in (test_vocab, bench_vocab):
         orc = helpers.oracle_for(v)
         exp = [orc.encode(d, True, True) for d in docs]

@@ -84,6 +84,38 @@ def test_emu_long_single_piece(test_vocab):
         assert g == o.encode(doc, True, True)
 
 
+def test_emu_char_cut_by_first_window(test_vocab):
+    """A multi-byte char across the end of the first 64-byte window (tk_encode_impl.h step 1: the window is trimmed to its last
+    whole char, the slide puts the char at the head of the next one), encode and split only."""
+    import tk_oracle
+    o = helpers.oracle_for(test_vocab)
+    docs = helpers.window_cut_docs()
+    got, _, _ = emu.encode_batch(test_vocab["tokens"], test_vocab["num_special"], 1, 2, docs, True, True)
+    _, starts, _ = emu.encode_batch(test_vocab["tokens"], test_vocab["num_special"], 1, 2, docs, split_only=True)
+    for doc, g, s in zip(docs, got, starts):
+        assert g == o.encode(doc, True, True), doc
+        assert s == tk_oracle.split(doc), doc
+
+
+def test_emu_cooperative_merge_block_minima_in_scratch(test_vocab):
+    """tk_piece_merge_coop keeps its block minima in scratch memory for a piece of more than 32 768 bytes (more than 512 blocks
+    of 64 parts), in registers up to there: one piece of 32 769 letters and its first 32 768.  An `ab` background makes no merge
+    with the test vocabulary; runs of random letters, which it does merge, lie across parts 63 / 64, across the edge of the
+    last full block (32 703 / 32 704) and inside the final partial block."""
+    import random
+    rng = random.Random(5)
+    o = helpers.oracle_for(test_vocab)
+    doc = bytearray((b"ab" * 16385)[:32769])
+    for at in (52, 32692, 32740):
+        doc[at:at + 24] = bytes(rng.choice(b"abcdefghijklmnopqrstuvwxyz") for _ in range(24))
+    # (the emulator's pass 2 has no long list, so the 32 768-byte twin stays with this merge, in its register form, and not with the rounds)
+    for d in (bytes(doc), bytes(doc[:32768])):
+        got, _, n_def = emu.encode_batch(test_vocab["tokens"], test_vocab["num_special"], 1, 2, [d], True, True)
+        assert n_def == 1
+        assert got[0] == o.encode(d, True, True)
+        assert len(got[0]) < len(d) + 2                      # merges happened
+
+
 def test_emu_json_pattern_opt_in(test_vocab):
     """Row f-3: the device's sequential matcher for the JSON pattern of Mistral's tekken.json (tk_match_end2, pass 2),
     on the emulator, id for id against the oracle in the same mode -- golden texts, case mixes, Unicode categories."""

@@ -1,4 +1,4 @@
-"""Differential stress of pass 2 (one wave per long piece, csrc/tk_encode_impl.h tk_piece_coop) against the oracle
+"""Differential stress of pass 2 (one wave per long piece, csrc/tk_piece_impl.h tk_piece_lookup / tk_piece_merge_coop) against the oracle
 (test infrastructure): documents that are ONE piece of 0.5 .. 32 KiB -- random letters, few-letter alphabets, runs --
 so that thousands of dependent merges go through the node arrays in global memory.
     python tools/gpu_longpiece_stress.py [--docs 160] [--seed 5] [--vocab small|bench]"""
