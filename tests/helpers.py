@@ -25,6 +25,70 @@ def small_trained_vocab(n_merges=3000, n_ranks=6000, seed=0x7E44E2):
     return v
 
 
+EDGE_LENGTHS = (2, 3, 4, 7, 8, 9, 14, 15, 16, 17, 31, 32, 33, 63, 64, 65, 128, 254, 255, 256, 300)
+EDGE_FLAVOURS = ("ascii", "mb", "zh_cut", "zh_tail", "e", "rocket")
+EDGE_SPECIALS = ["<unk>", "<s>", "</s>", "", "[/AVAILABLE_TOOLS]", "0123456789abcdef", "é🚀" * 6, "x" * 300]
+EDGE_LONG = 5000                 # the one token far beyond every one-byte length field
+# ranks around the end of the LDS part of the decode kernels' one-byte length table (TKD_L8_LDS = 32768), pairwise different
+# lengths: the last rank of the LDS part holds a token of 255 bytes (the 0xFF escape), the first rank behind it one of 254
+EDGE_HAND = {32764: 16, 32765: 65, 32766: 33, 32767: 255, 32768: 254, 32769: 300, 32770: 17, 32771: 128}
+EDGE_HIGH = {32780: 254, 32781: 255, 32782: 256, 32783: 300, 32784: EDGE_LONG}   # the longest tokens once more, above the split
+
+
+def _edge_valid_mb(n, salt):
+    """n bytes of valid UTF-8 that is not ASCII: ü, 中, 🚀 and a letter in rotation (from `salt`), each time the next that fits."""
+    chars = ["ü".encode(), "中".encode(), "\U0001f680".encode(), bytes([0x61 + salt % 26])]
+    out, k = b"", salt
+    while len(out) < n:
+        out += next(c for c in (chars[(k + j) % 4] for j in range(4)) if len(out) + len(c) <= n)
+        k += 1
+    return out
+
+
+def _edge_token(n, flavour):
+    zh, e, ro = "中".encode(), "é".encode(), "\U0001f680".encode()
+    if flavour == "ascii":
+        return (b" quick brown fox jumps over the lazy dog," * (n // 40 + 1))[:n]
+    if flavour == "mb":
+        return _edge_valid_mb(n, 0)
+    if flavour == "zh_cut":                       # ends inside a character unless n is a multiple of three
+        return (zh * (n // 3 + 1))[:n]
+    if flavour == "zh_tail":                      # begins inside a character
+        return (zh * (n // 3 + 2))[1:1 + n]
+    return ((e if flavour == "e" else ro) * (n // 2 + 1))[:n]
+
+
+def _edge_filler(r):
+    """2..6 bytes, distinct for every rank: the rank in base 94 over '!'..'~'; every third rank of four bytes or more begins with é."""
+    n, q = 2 + r % 5, r // 5
+    lead = "é".encode() if r % 3 == 0 and n >= 4 else b""
+    return lead + bytes(0x21 + (q // 94 ** j) % 94 for j in range(n - len(lead)))
+
+
+@functools.lru_cache(maxsize=None)
+def table_edge_vocab(n_ranks):
+    """A made-up vocabulary for the edges of the decode, spans and words kernels' token tables (they read token bytes only: nothing
+    is trained).  256 byte tokens; every length of EDGE_LENGTHS in every flavour of EDGE_FLAVOURS ("edge": (length, flavour) ->
+    rank); one token of EDGE_LONG bytes ("long"); EDGE_HAND and EDGE_HIGH at their ranks ("mb" text, salted), as far as n_ranks
+    reaches; every other rank short filler.  Specials: EDGE_SPECIALS (0, 16, 18, 36 and 300 bytes among them)."""
+    tokens = [bytes([b]) for b in range(256)]
+    edge = {}
+    for n in EDGE_LENGTHS:
+        for f in EDGE_FLAVOURS:
+            edge[(n, f)] = len(tokens)
+            tokens.append(_edge_token(n, f))
+    long_rank = len(tokens)
+    tokens.append(_edge_valid_mb(EDGE_LONG, 1))
+    placed = {**EDGE_HAND, **EDGE_HIGH}
+    assert n_ranks > len(tokens) and max(placed.values()) <= EDGE_LONG
+    for r in range(len(tokens), n_ranks):
+        tokens.append(_edge_valid_mb(placed[r], 2 + r % 20) if r in placed else _edge_filler(r))
+    assert len(set(tokens)) == len(tokens) == n_ranks
+    return {"tokens": tokens, "num_special": len(EDGE_SPECIALS), "bos": 1, "eos": 2, "specials": list(EDGE_SPECIALS), "edge": edge,
+            "long": long_rank, "hand": {r: n for r, n in EDGE_HAND.items() if r < n_ranks},
+            "high": {r: n for r, n in EDGE_HIGH.items() if r < n_ranks}}
+
+
 EDGE_DOCS = [b"", b" ", b"\n", b"\t", b"   \n\t   ", "\U0001f680".encode(), b"a" * 1000, b"Hello\x00World",
              b"Line1\nLine2\rLine3\r\nLine4", b"a", b"ab", b"'s", b"x's", b" " * 70, b"\n" * 70 + b"x", b"z" * 64,
              b"z" * 65, b"q" * 63 + b" ", ("中" * 40).encode(), ("é" * 33).encode(), b"1" * 100,

@@ -246,6 +246,44 @@ def test_checks_catch_what_the_global_sum_misses(tk, test_vocab):
         eng.close()
 
 
+def test_callers_ids_over_table_edges(tk):
+    """The caller's ids over helpers.table_edge_vocab(33001), the text their concatenation: tokens of 16, 17, 254, 255, 256, 300
+    and 5000 bytes (a length byte of 0xFF sends the kernel to the offsets), ranks on both sides of the LDS part of the length
+    table.  With TK_SPANS_CHECK_BYTES the clean call passes, and one changed byte anywhere in a long token names its document."""
+    v = helpers.table_edge_vocab(33001)
+    ns, toks = v["num_special"], v["tokens"]
+    a, z = ns + 0x61, ns + 0x7A
+    longs = [ns + v["edge"][(n, f)] for n in (15, 16, 17, 254, 255, 256, 300) for f in ("ascii", "zh_cut", "zh_tail", "rocket")]
+    longs += [ns + v["long"]] + [ns + r for r in sorted(v["hand"])] + [ns + r for r in sorted(v["high"])]
+    targets = [v["edge"][(300, "ascii")], 32767, 32769]
+    lists = [[a, z, ns + r, a] for r in targets]                          # (documents 0..2: the ones a byte is changed in)
+    lists += [[t] for t in longs] + [[a, t, 1, z, t, 3] for t in longs] + [longs, longs[::-1], [], [3], [ns + r for r in range(32760, 32776)]]
+    rng = np.random.default_rng(9)
+    pool = np.array(longs + list(range(ns, ns + 256)) + list(range(ns + 32700, ns + 32800)) + [0, 3, 7])
+    lists += [pool[rng.integers(0, len(pool), int(rng.integers(0, 150)))].tolist() for _ in range(40)]
+    ids = np.array([i for x in lists for i in x], np.uint32)
+    oo = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int64)
+    data, offs = pack([b"".join(toks[i - ns] for i in x if i >= ns) for x in lists])
+    eng = tk.Engine(toks, ns, v["bos"], v["eos"], device=0)
+    try:
+        for chk in (0, tk.SPANS_CHECK_COVER, tk.SPANS_CHECK_BYTES):
+            check_spans(v, data, offs, ids, oo, _device_case(tk, eng, data, offs, ids, oo, chk))
+        for doc, r in enumerate(targets):
+            for pos in (0, 15, 16, 254, 299):
+                if pos >= len(toks[r]):                                   # (rank 32767 holds 255 bytes)
+                    continue
+                changed = data.copy()
+                changed[int(offs[doc]) + 2 + pos] ^= 0x01
+                _device_case(tk, eng, changed, offs, ids, oo, tk.SPANS_CHECK_COVER)
+                with pytest.raises(tk.TokenizerError) as e:
+                    _device_case(tk, eng, changed, offs, ids, oo, tk.SPANS_CHECK_BYTES)
+                assert e.value.code == tk.TK_ERR_RUNTIME and e.value.bad_doc == doc, (r, pos, str(e.value))
+                assert "id index 2 " in str(e.value)
+        check_spans(v, data, offs, ids, oo, _device_case(tk, eng, data, offs, ids, oo, tk.SPANS_CHECK_BYTES))
+    finally:
+        eng.close()
+
+
 def test_encode_outputs_outlive_a_spans_call(tk, eng_bench, bench_vocab):
     """tk_token_spans_device on the d_ids / d_out_offsets the encode call returned leaves them valid and unchanged."""
     import torch

@@ -280,6 +280,36 @@ def test_foreign_ids(tk, eng, test_vocab):
     assert e.value.code == tk.TK_ERR_RUNTIME and e.value.bad_doc == 1 and "outside the vocabulary" in str(e.value)
 
 
+def test_foreign_ids_over_table_edges(tk):
+    """The caller's ids over helpers.table_edge_vocab(33001): tokens of 255 bytes and more (a length byte of 0xFF: the length comes
+    from the offsets) and ranks on both sides of the LDS part of the length table, the text their concatenation (so a token of
+    " quick brown fox ..." holds many piece starts) and, for one document, another document's text."""
+    v = helpers.table_edge_vocab(33001)
+    ns, toks = v["num_special"], v["tokens"]
+    a, z = ns + 0x61, ns + 0x20
+    longs = [ns + v["edge"][(n, f)] for n in (16, 17, 254, 255, 256, 300) for f in ("ascii", "mb")]
+    longs += [ns + v["long"]] + [ns + r for r in sorted(v["hand"])] + [ns + r for r in sorted(v["high"])]
+    rows = [[t] for t in longs] + [[a, z, t, 1, z, t, a] for t in longs] + [longs, longs[::-1], [], [3, 7]]
+    rows += [[ns + r for r in range(32760, 32776)], [ns + 32767, z, ns + 32768, z, ns + 32769] * 3]
+    docs = [b"".join(toks[i - ns] for i in r if i >= ns) for r in rows]
+    docs[len(longs)], docs[len(longs) + 1] = docs[len(longs) + 1], docs[len(longs)]          # two documents under each other's ids
+    data, offs = pack(docs)
+    ids = np.array(sum(rows, []), np.uint32)
+    oo = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.uint64)
+    exp = expected_for(v, ids, oo, data, offs)
+    assert exp["n_words"] > 100 and max(exp["per_doc"]) >= 10    # (a word counts where a TOKEN begins on a piece start)
+    e = tk.Engine(toks, ns, v["bos"], v["eos"], device=0)
+    try:
+        assert_words(from_ids(tk, e, ids, oo, data, offs), exp, "table edges")
+        bad = first_unaligned(ids, oo, toks, ns, data, offs, tk_oracle.split)
+        assert bad is not None and bad[0] == 0                     # (a piece starts inside the first long token)
+        with pytest.raises(tk.TokenizerError) as err:
+            from_ids(tk, e, ids, oo, data, offs, checks=tk.WORDS_CHECK_ALIGNED)
+        assert err.value.code == tk.TK_ERR_RUNTIME and err.value.bad_doc == 0
+    finally:
+        e.close()
+
+
 # ---- 5. TK_WORDS_CHECK_ALIGNED ----
 def test_check_aligned_names_the_crossing_token(tk):
     """(That the check passes on encode's own output, with n_words = the oracle's piece count, is part of test_sweep_parity.)"""
