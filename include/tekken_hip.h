@@ -1179,6 +1179,53 @@ int tk_decode_batch_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offs
                            int policy, void* hip_stream, void** d_bytes, void** d_out_offsets, uint64_t* n_bytes,
                            uint64_t* bad_doc);
 
+/* ---- lossy decode: invalid UTF-8 becomes U+FFFD instead of failing the call (no reference equivalent for whole documents; the
+ * reference uses String::from_utf8_lossy for pieces, src/tekkenizer.rs:150) ----
+ * Lossy text of a run of bytes: what python's bytes.decode("utf-8", "replace").encode() and Rust's from_utf8_lossy return
+ * (WHATWG / Unicode "substitution of maximal subparts").  From the left: an ASCII byte is copied; a byte that cannot begin a
+ * sequence (80..BF, C0, C1, F5..FF) becomes EF BF BD; a lead C2..F4 takes the longest prefix of its sequence that is still well
+ * formed (second byte bounded by the lead -- E0: A0..BF, ED: 80..9F, F0: 90..BF, F4: 80..8F, otherwise 80..BF --, later bytes
+ * 80..BF, never past the end of the run), a complete sequence is copied, a truncated prefix of 1..3 bytes becomes ONE EF BF BD,
+ * and the scan goes on behind the prefix.
+ * Lossy decode of a document follows the grouping of tk_decode_batch: every maximal run of non-special ids is lossy-decoded on its
+ * own -- a character never spans a special id, not even one dropped under TK_POLICY_IGNORE, and never a document boundary --,
+ * special runs are handled by the policy as in tk_decode_batch.  A special id under TK_POLICY_RAISE and an id outside the
+ * vocabulary remain errors of the whole call, with the codes and *bad_doc of tk_decode_batch; only the UTF-8 error class is gone.
+ * *n_replaced (optional): U+FFFD written; *first_bad_doc (optional): the first document with one, ~0 for none.
+ * Where every run is valid the strict pipeline's buffers are the result: no kernel is added, no byte moved. */
+int tk_decode_batch_lossy(tk_ctx* ctx, const uint32_t* ids, const uint64_t* id_offsets, uint64_t n_docs, int policy,
+                          tk_text_result* out, uint64_t* bad_doc, uint64_t* n_replaced, uint64_t* first_bad_doc);
+/* Same with ids resident in HBM; outputs are context-owned device buffers valid until the next call on the context. */
+int tk_decode_batch_device_lossy(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_docs, uint64_t n_ids,
+                                 int policy, void* hip_stream, void** d_bytes, void** d_out_offsets, uint64_t* n_bytes,
+                                 uint64_t* bad_doc, uint64_t* n_replaced, uint64_t* first_bad_doc);
+
+/* Streaming decode for generation: all running sequences at once, a few new ids per sequence and step.  Every sequence carries a
+ * uint32 state: bytes 0..2 hold up to three pending bytes, byte 3 their count 0..3; 0 is a fresh sequence (to reuse a slot the
+ * caller zeroes its word).  A step takes a ragged batch of new ids (a sequence may have none) and returns for every sequence the
+ * lossy text of `pending ++ bytes of the new ids` under the grouping above, except that a truncated prefix that reaches the end of
+ * the step's bytes behind a non-special last id is not written: it becomes the new state.  A special id (a dropped one too)
+ * writes an open prefix as one U+FFFD, in front of its own string under TK_POLICY_KEEP.  flags: TK_STREAM_FINAL writes every open
+ * prefix as U+FFFD and leaves the states 0.  For any split of an id sequence into steps, the steps' texts plus the final flush are
+ * the lossy decode of the whole sequence.
+ * d_state (uint32[n_seqs]) is the caller's device memory, rewritten by the step; d_ids / d_id_offsets (uint64[n_seqs + 1]) as in
+ * tk_decode_batch_device.  Outputs: context-owned device buffers, valid until the next stream step or lossy decode on the context.
+ * Errors as tk_decode_batch (TK_ERR_SPECIAL_POLICY, TK_ERR_RUNTIME for an id outside the vocabulary), *bad_seq (optional) the
+ * first such sequence; the state buffer is then untouched.  One lane walks one sequence: a long step is correct and slow --
+ * prefill-sized input belongs in tk_decode_batch_device_lossy. */
+#define TK_STREAM_FINAL 1
+int tk_decode_stream_step_device(tk_ctx* ctx, void* d_state, const void* d_ids, const void* d_id_offsets, uint64_t n_seqs,
+                                 uint64_t n_ids, int policy, int flags, void* hip_stream, void** d_bytes, void** d_out_offsets,
+                                 uint64_t* n_bytes, uint64_t* bad_seq);
+/* Host convenience: state (uint32[n_seqs], read and rewritten), ids and offsets in host memory; release with tk_free_text_result. */
+int tk_decode_stream_step(tk_ctx* ctx, uint32_t* state, const uint32_t* ids, const uint64_t* id_offsets, uint64_t n_seqs, int policy,
+                          int flags, tk_text_result* out, uint64_t* bad_seq);
+/* As tk_last_rowfit_ms, for tools/decode_lossy_time.py: GPU time of the context's last lossy batch decode, from events on its
+ * stream -- the strict pipeline in front, and the repair pass (0 where every run was valid). */
+void tk_last_decode_lossy_ms(const tk_ctx* ctx, float* strict_ms, float* repair_ms);
+/* ... and its counters: U+FFFD written, documents with one, kernels launched behind the strict pipeline (0: the fast path). */
+void tk_last_decode_lossy_stats(const tk_ctx* ctx, uint64_t* n_replaced, uint64_t* n_bad_docs, uint64_t* n_repair_launches);
+
 /* 18-bit wire format of token ids for the multi-GPU gather (no reference equivalent: the reference is one process on a
  * CPU; BASELINE north_star asks for "a single RCCL gather of token-id buffers over xGMI").  The link into the
  * gathering GPU bounds the job, and an id below 2^18 -- every Tekken vocabulary -- travels as 2.25 bytes instead of 4.

@@ -38,6 +38,7 @@ pub const TK_ERR_TOKEN_NOT_FOUND: c_int = -9;
 pub const TK_ERR_SPECIAL_POLICY: c_int = -10;
 
 // the checks of the spans entries (above TK_CHECK_OFFSETS = 1 / TK_CHECK_UTF8 = 2: one word can carry all four)
+pub const TK_STREAM_FINAL: c_int = 1;
 pub const TK_SPANS_CHECK_COVER: c_int = 4;
 pub const TK_SPANS_CHECK_BYTES: c_int = 8;
 // the unit of the units entries' spans
@@ -655,6 +656,22 @@ extern "C" {
     pub fn tk_decode_batch(ctx: *mut TkCtx, ids: *const u32, id_offsets: *const u64, n_docs: u64, policy: c_int,
                            out: *mut TkTextResult, bad_doc: *mut u64) -> c_int;
     pub fn tk_free_text_result(r: *mut TkTextResult);
+    // lossy decode (invalid UTF-8 -> U+FFFD, a run of non-special ids at a time) and the stream step for generation
+    // (state: one u32 per sequence, bytes 0..2 the pending bytes, byte 3 their count; TK_STREAM_FINAL flushes)
+    pub fn tk_decode_batch_lossy(ctx: *mut TkCtx, ids: *const u32, id_offsets: *const u64, n_docs: u64, policy: c_int,
+                                 out: *mut TkTextResult, bad_doc: *mut u64, n_replaced: *mut u64, first_bad_doc: *mut u64) -> c_int;
+    pub fn tk_decode_batch_device_lossy(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_docs: u64, n_ids: u64,
+                                        policy: c_int, hip_stream: *mut c_void, d_bytes: *mut *mut c_void,
+                                        d_out_offsets: *mut *mut c_void, n_bytes: *mut u64, bad_doc: *mut u64,
+                                        n_replaced: *mut u64, first_bad_doc: *mut u64) -> c_int;
+    pub fn tk_decode_stream_step_device(ctx: *mut TkCtx, d_state: *mut c_void, d_ids: *const c_void, d_id_offsets: *const c_void,
+                                        n_seqs: u64, n_ids: u64, policy: c_int, flags: c_int, hip_stream: *mut c_void,
+                                        d_bytes: *mut *mut c_void, d_out_offsets: *mut *mut c_void, n_bytes: *mut u64,
+                                        bad_seq: *mut u64) -> c_int;
+    pub fn tk_decode_stream_step(ctx: *mut TkCtx, state: *mut u32, ids: *const u32, id_offsets: *const u64, n_seqs: u64,
+                                 policy: c_int, flags: c_int, out: *mut TkTextResult, bad_seq: *mut u64) -> c_int;
+    pub fn tk_last_decode_lossy_ms(ctx: *const TkCtx, strict_ms: *mut f32, repair_ms: *mut f32);
+    pub fn tk_last_decode_lossy_stats(ctx: *const TkCtx, n_replaced: *mut u64, n_bad_docs: *mut u64, n_repair_launches: *mut u64);
     pub fn tk_ctx_set_pattern(ctx: *mut TkCtx, mode: c_int) -> c_int;
 
     // node level: every GPU of the node behind one call (north star: documents sharded across the GPUs, one RCCL

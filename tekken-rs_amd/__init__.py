@@ -31,6 +31,7 @@ CHECK_OFFSETS, CHECK_UTF8 = 1, 2   # tk_encode_batch_device_ex
 SPANS_CHECK_COVER, SPANS_CHECK_BYTES = 4, 8   # the spans entries (tk_token_spans_device, tk_encode_batch_*spans)
 UNIT_BYTE, UNIT_CHAR, UNIT_UTF16 = 0, 1, 2   # the unit of the units entries' spans (tk_token_spans_units_device)
 _UNITS = {"byte": UNIT_BYTE, "char": UNIT_CHAR, "utf16": UNIT_UTF16}   # the offsets_unit keyword of the Tekkenizer methods
+STREAM_FINAL = 1   # tk_decode_stream_step[_device] flags: write every open prefix as U+FFFD, leave the states 0
 DENSE_PAD_LEFT, DENSE_TRUNC_LEFT, DENSE_FIXED, DENSE_I64, DENSE_MASK = 1, 2, 4, 8, 16   # tk_dense_opts.flags (the dense entries)
 SEQPACK_I64, SEQPACK_POSITIONS, SEQPACK_SEGMENTS, SEQPACK_CU_SEQLENS, SEQPACK_DROP_LAST = 1, 2, 4, 8, 16   # tk_seqpack_opts.flags (the packed entries)
 WINDOW_FIXED, WINDOW_I64, WINDOW_MASK, WINDOW_SPANS = 1, 2, 4, 8   # tk_window_opts.flags (the window entries)
@@ -336,6 +337,21 @@ def lib():
     L.tk_decode_batch_device.restype = ctypes.c_int
     L.tk_decode_batch_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, ctypes.POINTER(vp),
                                          ctypes.POINTER(vp), u64p, u64p]
+    if hasattr(L, "tk_decode_batch_lossy"):   # lossy decode and the stream step (a library built before them lacks all six)
+        L.tk_decode_batch_lossy.restype = ctypes.c_int
+        L.tk_decode_batch_lossy.argtypes = [vp, u32p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(_TextResult), u64p, u64p, u64p]
+        L.tk_decode_batch_device_lossy.restype = ctypes.c_int
+        L.tk_decode_batch_device_lossy.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, vp, ctypes.POINTER(vp),
+                                                   ctypes.POINTER(vp), u64p, u64p, u64p, u64p]
+        L.tk_decode_stream_step_device.restype = ctypes.c_int
+        L.tk_decode_stream_step_device.argtypes = [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, vp,
+                                                   ctypes.POINTER(vp), ctypes.POINTER(vp), u64p, u64p]
+        L.tk_decode_stream_step.restype = ctypes.c_int
+        L.tk_decode_stream_step.argtypes = [vp, u32p, u32p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_TextResult), u64p]
+        L.tk_last_decode_lossy_ms.restype = None
+        L.tk_last_decode_lossy_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+        L.tk_last_decode_lossy_stats.restype = None
+        L.tk_last_decode_lossy_stats.argtypes = [vp, u64p, u64p, u64p]
     L.tk_tokenizer_decode_batch.restype = ctypes.c_int
     L.tk_tokenizer_decode_batch.argtypes = [vp, u32p, u64p, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(_TextResult), u64p]
     L.tk_last_timing.restype = ctypes.c_int
@@ -616,6 +632,56 @@ def _take_result(res):
     offs = np.ctypeslib.as_array(res.offsets, shape=(D + 1,)).copy()
     lib().tk_free_result(ctypes.byref(res))
     return ids, offs
+
+
+class DecodeStream:
+    """Streaming decode for generation (tk_decode_stream_step_device): n_seqs running sequences, one uint32 state word each in a
+    device buffer (.state: a torch int32 tensor; bytes 0..2 up to three pending bytes, byte 3 their count).  A step takes the new
+    ids of every sequence (a sequence may have none) and returns only complete characters: the open tail of a character waits in
+    the state for the next step, invalid bytes become U+FFFD as in decode_batch(errors="replace").  One lane walks one sequence:
+    prefill-sized input belongs in decode_batch."""
+
+    def __init__(self, engine, n_seqs, policy=SpecialTokenPolicy.Ignore, text=False):
+        import torch
+        self._eng, self.n_seqs, self.policy, self._text = engine, int(n_seqs), policy, text
+        self.state = torch.zeros(max(self.n_seqs, 1), dtype=torch.int32, device="cuda")[:self.n_seqs]
+
+    def step_device(self, ids_ptr, offs_ptr, n_ids, flags=0, stream=None):
+        """The new ids (uint32) and their offsets (uint64[n_seqs + 1]) in HBM -> (bytes view, offsets view), context-owned."""
+        import torch
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        return self._eng.decode_stream_step_device(self.state.data_ptr() if self.n_seqs else 0, ids_ptr, offs_ptr, self.n_seqs, n_ids,
+                                                   self.policy, flags, st)
+
+    def step(self, id_lists, flags=0):
+        """The new ids of every sequence (n_seqs lists) -> list of bytes (str with text=True)."""
+        import torch
+        if len(id_lists) != self.n_seqs:
+            raise TokenizerError(TK_ERR_INVALID_ARG, "DecodeStream.step: one id list per sequence (%d)" % self.n_seqs)
+        offs = np.zeros(self.n_seqs + 1, np.int64)
+        if id_lists:
+            offs[1:] = np.cumsum([len(x) for x in id_lists])
+        flat = [i for x in id_lists for i in x]
+        n_ids = len(flat)
+        d_ids = torch.from_numpy(np.array(flat or [0], dtype=np.uint32).view(np.int32)).cuda()
+        d_offs = torch.from_numpy(offs).cuda()
+        v_b, v_o = self.step_device(d_ids.data_ptr(), d_offs.data_ptr(), n_ids, flags)
+        oo = torch.as_tensor(v_o, device="cuda").cpu().numpy()
+        raw = torch.as_tensor(v_b, device="cuda").cpu().numpy().tobytes() if int(oo[-1]) else b""
+        out = [raw[int(oo[d]):int(oo[d + 1])] for d in range(self.n_seqs)]
+        return [b.decode("utf-8", "replace") for b in out] if self._text else out
+
+    def finish(self):
+        """Flushes every open prefix as U+FFFD (TK_STREAM_FINAL) and leaves the states 0."""
+        return self.step([[] for _ in range(self.n_seqs)], STREAM_FINAL)
+
+    def reset(self, rows=None):
+        """Zeroes the state of the given slots (None: all): a slot reused in continuous batching starts fresh."""
+        if rows is None:
+            self.state.zero_()
+        elif len(rows):
+            import torch
+            self.state[torch.as_tensor(list(rows), dtype=torch.long, device="cuda")] = 0
 
 
 class DeviceView:
@@ -1814,45 +1880,132 @@ class Engine:
         if rc != TK_OK:
             raise self._err(rc)
 
-    def decode_batch(self, ids, offs, policy=SpecialTokenPolicy.Ignore):
-        """Batch Tekkenizer::decode on the GPU: (uint32 ids, uint64 offsets[D+1]) -> (uint8 bytes, uint64 offsets[D+1])."""
+    @staticmethod
+    def _lossy(errors):
+        if errors not in ("strict", "replace"):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "errors must be 'strict' or 'replace', not %r" % (errors,))
+        return errors == "replace"
+
+    def decode_batch(self, ids, offs, policy=SpecialTokenPolicy.Ignore, errors="strict"):
+        """Batch Tekkenizer::decode on the GPU: (uint32 ids, uint64 offsets[D+1]) -> (uint8 bytes, uint64 offsets[D+1]).
+        errors="replace": a run that is not valid UTF-8 is decoded as python's errors="replace" does it (U+FFFD; tk_decode_batch_lossy)
+        instead of failing the call; self.n_replaced then holds the U+FFFD written, self.first_bad_doc the first document with one
+        (None: none)."""
+        lossy = self._lossy(errors)
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         res = _TextResult()
         bad = ctypes.c_uint64(0)
         ibuf = ids if len(ids) else np.zeros(1, np.uint32)
-        rc = lib().tk_decode_batch(self._h, _p(ibuf, ctypes.c_uint32), _p(offs, ctypes.c_uint64), len(offs) - 1, int(policy),
-                                   ctypes.byref(res), ctypes.byref(bad))
+        if lossy:
+            nrep, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            rc = _need("tk_decode_batch_lossy")(self._h, _p(ibuf, ctypes.c_uint32), _p(offs, ctypes.c_uint64), len(offs) - 1, int(policy),
+                                                ctypes.byref(res), ctypes.byref(bad), ctypes.byref(nrep), ctypes.byref(first))
+        else:
+            rc = lib().tk_decode_batch(self._h, _p(ibuf, ctypes.c_uint32), _p(offs, ctypes.c_uint64), len(offs) - 1, int(policy),
+                                       ctypes.byref(res), ctypes.byref(bad))
         if rc != TK_OK:
             e = self._err(rc)
             e.bad_doc = int(bad.value)
             raise e
+        if lossy:
+            self._set_lossy(nrep, first)
         n, D = int(res.n_bytes), int(res.n_docs)
         data = np.ctypeslib.as_array(res.bytes, shape=(max(n, 1),))[:n].copy()
         oo = np.ctypeslib.as_array(res.offsets, shape=(D + 1,)).copy()
         lib().tk_free_text_result(ctypes.byref(res))
         return data, oo
 
-    def decode_docs(self, id_lists, policy=SpecialTokenPolicy.Ignore):
+    n_replaced = 0           # of the last decode with errors="replace" on this engine: U+FFFD written ...
+    first_bad_doc = None     # ... and the first document with one
+
+    def _set_lossy(self, nrep, first):
+        self.n_replaced = int(nrep.value)
+        self.first_bad_doc = None if first.value == 0xFFFFFFFFFFFFFFFF else int(first.value)
+
+    def decode_docs(self, id_lists, policy=SpecialTokenPolicy.Ignore, errors="strict"):
         offs = np.zeros(len(id_lists) + 1, np.uint64)
         if id_lists:
             offs[1:] = np.cumsum([len(x) for x in id_lists], dtype=np.uint64)
         ids = np.array([i for x in id_lists for i in x], dtype=np.uint32)
-        data, oo = self.decode_batch(ids, offs, policy)
+        data, oo = self.decode_batch(ids, offs, policy, errors)
         raw = data.tobytes()
         return [raw[int(oo[d]):int(oo[d + 1])] for d in range(len(id_lists))]
 
-    def decode_batch_device(self, d_ids_ptr, d_offs_ptr, n_docs, n_ids, policy=SpecialTokenPolicy.Ignore, stream=0):
-        """ids resident in HBM -> (bytes view uint8[n_bytes], offsets view int64[n_docs+1]) context-owned."""
+    def decode_batch_device(self, d_ids_ptr, d_offs_ptr, n_docs, n_ids, policy=SpecialTokenPolicy.Ignore, stream=0, errors="strict"):
+        """ids resident in HBM -> (bytes view uint8[n_bytes], offsets view int64[n_docs+1]) context-owned.  errors="replace" as in
+        decode_batch (tk_decode_batch_device_lossy): where every run is valid the views are the strict entry's own buffers."""
+        lossy = self._lossy(errors)
         d_b, d_o, n, bad = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0), ctypes.c_uint64(0)
-        rc = lib().tk_decode_batch_device(self._h, ctypes.c_void_p(d_ids_ptr), ctypes.c_void_p(d_offs_ptr), n_docs, n_ids,
-                                          int(policy), ctypes.c_void_p(stream), ctypes.byref(d_b), ctypes.byref(d_o),
-                                          ctypes.byref(n), ctypes.byref(bad))
+        if lossy:
+            nrep, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            rc = _need("tk_decode_batch_device_lossy")(self._h, ctypes.c_void_p(d_ids_ptr), ctypes.c_void_p(d_offs_ptr), n_docs, n_ids,
+                                                       int(policy), ctypes.c_void_p(stream), ctypes.byref(d_b), ctypes.byref(d_o),
+                                                       ctypes.byref(n), ctypes.byref(bad), ctypes.byref(nrep), ctypes.byref(first))
+        else:
+            rc = lib().tk_decode_batch_device(self._h, ctypes.c_void_p(d_ids_ptr), ctypes.c_void_p(d_offs_ptr), n_docs, n_ids,
+                                              int(policy), ctypes.c_void_p(stream), ctypes.byref(d_b), ctypes.byref(d_o),
+                                              ctypes.byref(n), ctypes.byref(bad))
         if rc != TK_OK:
             e = self._err(rc)
             e.bad_doc = int(bad.value)
             raise e
+        if lossy:
+            self._set_lossy(nrep, first)
         return DeviceView(d_b.value, int(n.value), "|u1"), DeviceView(d_o.value, n_docs + 1, "<i8")
+
+    def last_decode_lossy(self):
+        """tk_last_decode_lossy_ms / _stats: GPU time of the strict pipeline and of the repair pass of the last lossy batch decode
+        on this context, its counters, and the kernels launched behind the strict pipeline (0: the fast path)."""
+        a, b = ctypes.c_float(0), ctypes.c_float(0)
+        x, y, z = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _need("tk_last_decode_lossy_ms")(self._h, ctypes.byref(a), ctypes.byref(b))
+        _need("tk_last_decode_lossy_stats")(self._h, ctypes.byref(x), ctypes.byref(y), ctypes.byref(z))
+        return {"strict_ms": a.value, "repair_ms": b.value, "n_replaced": int(x.value), "n_bad_docs": int(y.value),
+                "repair_launches": int(z.value)}
+
+    def decode_stream_step_device(self, d_state_ptr, d_ids_ptr, d_offs_ptr, n_seqs, n_ids, policy=SpecialTokenPolicy.Ignore, flags=0,
+                                  stream=0):
+        """tk_decode_stream_step_device: one step of streaming decode over states, ids and offsets in HBM -> (bytes view, offsets
+        view int64[n_seqs + 1]), context-owned.  An error carries .bad_seq and leaves the states untouched."""
+        d_b, d_o, n, bad = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = _need("tk_decode_stream_step_device")(self._h, ctypes.c_void_p(d_state_ptr), ctypes.c_void_p(d_ids_ptr),
+                                                   ctypes.c_void_p(d_offs_ptr), n_seqs, n_ids, int(policy), int(flags),
+                                                   ctypes.c_void_p(stream), ctypes.byref(d_b), ctypes.byref(d_o), ctypes.byref(n),
+                                                   ctypes.byref(bad))
+        if rc != TK_OK:
+            e = self._err(rc)
+            e.bad_seq = e.bad_doc = int(bad.value)
+            raise e
+        return DeviceView(d_b.value, int(n.value), "|u1"), DeviceView(d_o.value, n_seqs + 1, "<i8")
+
+    def decode_stream_step(self, state, id_lists, policy=SpecialTokenPolicy.Ignore, flags=0):
+        """tk_decode_stream_step: state (uint32[n_seqs] numpy, rewritten in place) and the new ids of every sequence in host
+        memory -> list of bytes."""
+        if state.dtype != np.uint32 or not state.flags["C_CONTIGUOUS"] or len(state) != len(id_lists):
+            raise TokenizerError(TK_ERR_INVALID_ARG, "decode_stream_step: state must be a contiguous uint32 array, one word per sequence")
+        offs = np.zeros(len(id_lists) + 1, np.uint64)
+        if id_lists:
+            offs[1:] = np.cumsum([len(x) for x in id_lists], dtype=np.uint64)
+        ids = np.array([i for x in id_lists for i in x] or [0], dtype=np.uint32)
+        sbuf = state if len(state) else np.zeros(1, np.uint32)
+        res = _TextResult()
+        bad = ctypes.c_uint64(0)
+        rc = _need("tk_decode_stream_step")(self._h, _p(sbuf, ctypes.c_uint32), _p(ids, ctypes.c_uint32), _p(offs, ctypes.c_uint64),
+                                            len(id_lists), int(policy), int(flags), ctypes.byref(res), ctypes.byref(bad))
+        if rc != TK_OK:
+            e = self._err(rc)
+            e.bad_seq = e.bad_doc = int(bad.value)
+            raise e
+        n = int(res.n_bytes)
+        raw = np.ctypeslib.as_array(res.bytes, shape=(max(n, 1),))[:n].tobytes()
+        oo = np.ctypeslib.as_array(res.offsets, shape=(len(id_lists) + 1,)).copy()
+        lib().tk_free_text_result(ctypes.byref(res))
+        return [raw[int(oo[d]):int(oo[d + 1])] for d in range(len(id_lists))]
+
+    def decode_stream(self, n_seqs, policy=SpecialTokenPolicy.Ignore, text=False):
+        """A DecodeStream over n_seqs running sequences (text: its steps return str, not bytes)."""
+        return DecodeStream(self, n_seqs, policy, text)
 
     def last_timing(self):
         a, b = ctypes.c_float(0), ctypes.c_float(0)
@@ -2736,10 +2889,12 @@ class Tekkenizer:
             out = {k: v.cpu().numpy() if torch.is_tensor(v) else v for k, v in out.items()}
         return out
 
-    def decode_batch_padded(self, input_ids, lengths=None, policy=SpecialTokenPolicy.Ignore, pad_id=None, padding_side="right"):
+    def decode_batch_padded(self, input_ids, lengths=None, policy=SpecialTokenPolicy.Ignore, pad_id=None, padding_side="right",
+                            errors="strict"):
         """Batch decode of dense rows (tk_ragged_from_dense_device + tk_decode_batch_device): input_ids [B, L], int32 or int64, a
         torch tensor on the tokenizer's GPU or a numpy array -> list of str.  lengths (per row, optional): without them the run of
-        pad_id (None: self.pad_id()) at the padded end of every row is dropped.  Errors as decode_batch (.bad_doc)."""
+        pad_id (None: self.pad_id()) at the padded end of every row is dropped.  Errors as decode_batch (.bad_doc); errors="replace"
+        as in decode_batch (self.n_replaced)."""
         eng = self._device_engine()
         import torch
         pad = self.pad_id() if pad_id is None else int(pad_id)
@@ -2757,7 +2912,9 @@ class Tekkenizer:
         stream = torch.cuda.current_stream().cuda_stream
         p_ids, p_oo, n = eng.ragged_from_dense_device(t.data_ptr() if D * L else 0, D, L, flags, d_len.data_ptr() if d_len is not None and D else 0,
                                                       pad, stream)
-        v_bytes, v_offs = eng.decode_batch_device(p_ids, p_oo, D, n, policy, stream)
+        v_bytes, v_offs = eng.decode_batch_device(p_ids, p_oo, D, n, policy, stream, errors)
+        if errors == "replace":
+            self.n_replaced = eng.n_replaced
         oo = torch.as_tensor(v_offs, device="cuda").cpu().numpy()
         total = int(oo[-1])
         raw = torch.as_tensor(v_bytes, device="cuda").cpu().numpy().tobytes() if total else b""
@@ -2964,12 +3121,25 @@ class Tekkenizer:
         """Tekkenizer::vocab (src/tekkenizer.rs:348-350): the piece string of every id."""
         return self._strs(lib().tk_tokenizer_vocab)
 
-    def decode_batch(self, id_lists, policy=SpecialTokenPolicy.Ignore):
-        """Batch decode on the GPU: list of id lists -> list of str (an addition; the reference decodes one at a time)."""
+    def decode_batch(self, id_lists, policy=SpecialTokenPolicy.Ignore, errors="strict"):
+        """Batch decode on the GPU: list of id lists -> list of str (an addition; the reference decodes one at a time).
+        errors="replace": invalid UTF-8 becomes U+FFFD as in python's bytes.decode (a run of non-special ids at a time: a character
+        never spans a special id); self.n_replaced then holds the U+FFFD written by the last such call."""
         eng = self.engine()
         if eng is None:
             raise TokenizerError(TK_ERR_NO_DEVICE, "tokenizer was created without a device (host-only object)")
-        return [b.decode("utf-8") for b in eng.decode_docs(id_lists, policy)]
+        out = [b.decode("utf-8") for b in eng.decode_docs(id_lists, policy, errors)]
+        if errors == "replace":
+            self.n_replaced = eng.n_replaced
+        return out
+
+    n_replaced = 0           # U+FFFD written by the last decode_batch / decode_batch_padded with errors="replace"
+
+    def decode_stream(self, n_seqs, policy=SpecialTokenPolicy.Ignore):
+        """A DecodeStream over n_seqs running sequences for generation: .step(id_lists) -> list of str with only complete
+        characters (the open tail of a character waits for the next step), .step_device(ids_ptr, offs_ptr, n_ids) -> device
+        views, .finish() flushes, .reset(rows) zeroes slots, .state is the device state buffer."""
+        return self._device_engine().decode_stream(n_seqs, policy, text=True)
 
     def _piece(self, fn, *args):
         text = ctypes.c_void_p()

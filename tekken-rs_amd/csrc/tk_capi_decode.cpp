@@ -22,8 +22,8 @@ int token_tables(tk_ctx* c) {
     return rc != TK_OK ? rc : upload(c, c->t_len8, l8.data(), l8.size());
 }
 
-static int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, int policy,
-                      hipStream_t s, uint64_t* n_bytes, uint64_t* bad_doc) {
+int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, int policy,
+               hipStream_t s, uint64_t* n_bytes, uint64_t* bad_doc, uint64_t* utf8_bad) {
     if (policy < TK_POLICY_IGNORE || policy > TK_POLICY_RAISE) { c->err = "invalid policy"; return TK_ERR_INVALID_ARG; }
     if (policy == TK_POLICY_KEEP && !c->have_specials) { c->err = "TK_POLICY_KEEP needs tk_ctx_set_special_tokens first"; return TK_ERR_INVALID_ARG; }
     TK_HIP(c, c->dec_lens.reserve((n_docs + 1) * 4));
@@ -82,6 +82,7 @@ static int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
     a.out_bytes = (uint8_t*)c->dec_bytes.p;
     a.run_bits = (uint32_t*)c->dec_bits.p;
     TK_HIP(c, hipMemsetAsync(c->dec_bits.p, 0, (total / 32 + 4) * 4, s));
+    if (n_docs == 0) TK_HIP(c, hipMemsetAsync(c->dec_offs.p, 0, 8, s));   // (no group writes the offsets' one entry: the total, 0)
     TK_HIP(c, tk_launch_decode_emit(a, s));
     TK_HIP(c, tk_launch_decode_validate(a, s));
     TK_HIP(c, hipEventRecord(c->ev[2], s));
@@ -89,6 +90,10 @@ static int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
     TK_HIP(c, hipStreamSynchronize(s));
     (void)hipEventElapsedTime(&c->pipeline_ms, c->ev[0], c->ev[2]);
     c->encode_ms = 0.f;
+    if (utf8_bad) {                // the lossy entries: an invalid run is theirs to repair
+        *utf8_bad = err[2];
+        err[2] = ~0ull;
+    }
     if (err[0] != ~0ull || err[1] != ~0ull || err[2] != ~0ull) {
         // Some document makes the reference return Err.  The GPU found WHICH documents; the class of the
         // error of the first one is decided by walking that single document's groups in the reference's
@@ -127,7 +132,7 @@ static int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_off
                     }
                     run.append((const char*)h.blob.data() + h.offs[r], h.offs[r + 1] - h.offs[r]);
                 }
-                if (!tekken::utf8_valid((const uint8_t*)run.data(), run.size())) {
+                if (!utf8_bad && !tekken::utf8_valid((const uint8_t*)run.data(), run.size())) {
                     c->err = "FromUtf8Error: invalid utf-8 sequence (document " + std::to_string(first) + ")";
                     return TK_ERR_RUNTIME;
                 }

@@ -181,6 +181,19 @@ struct NoiseBufs {
     float ms[3] = {0.f, 0.f, 0.f}; // selection | counts and scans | fill kernel
 };
 
+// lossy decode (tk_decode_lossy.hip).  The repair pass: the lossy text and its offsets, the tiles' counts and their scan, the
+// per-document "has a replacement" flags, the two counters, the scan workspace.  The stream step: the step's text, its offsets
+// (n_seqs + 1 words, and the two error words right behind them: ONE host read), the lengths, the counter; the host entry's copies of
+// the state, the ids and their offsets.
+struct DecodeLossyBufs {
+    DevBuf bytes, offs, tcnt, toffs, flags, stat, bsum;
+    DevBuf s_bytes, s_offs, s_lens, s_stat, s_bsum, s_state, s_in_ids, s_in_offs;
+    Event ev[2];                   // around the repair pass of the last lossy call (tk_last_decode_lossy_ms), created at the first one
+    float strict_ms = 0.f, repair_ms = 0.f;
+    uint64_t n_replaced = 0, n_bad_docs = 0;
+    uint32_t repair_launches = 0;  // kernels the last lossy call launched behind the strict pipeline (0: the fast path)
+};
+
 struct tk_ctx {
     int device = 0;
     std::mutex mu;
@@ -217,6 +230,7 @@ struct tk_ctx {
     SpecialsBufs specials;
     FimBufs fim;
     NoiseBufs noise;
+    DecodeLossyBufs lossy;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy
@@ -340,6 +354,11 @@ int run_words(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint6
               const uint64_t* d_doc_offs, uint64_t n_bytes, int checks, const tk_words_opts* o, hipStream_t s, tk_words* out, uint64_t* bad);
 // tk_capi_decode.cpp: the decode kernels' tables (also what the spans kernel reads), built at the first call that needs them
 int token_tables(tk_ctx* c);
+// ... and the strict decode pipeline over ids on the device: the text ends in c->dec_bytes, its offsets in c->dec_offs, the run
+// starts in c->dec_bits.  utf8_bad (the lossy entries): a run that is not valid UTF-8 is no error; the first document with one
+// goes to *utf8_bad (~0: none), every other error is reported as without it
+int run_decode(tk_ctx* c, const uint32_t* d_ids, const uint64_t* d_id_offs, uint64_t n_docs, uint64_t n_ids, int policy,
+               hipStream_t s, uint64_t* n_bytes, uint64_t* bad_doc, uint64_t* utf8_bad = nullptr);
 template <class A> static inline void token_args(const tk_ctx* c, A& a) {   // ... as the decode and spans kernels take them
     a.tok_blob = (const uint8_t*)c->t_blob.p; a.tok_offs = (const uint32_t*)c->t_offs.p;
     a.tok_inline = (const uint8_t*)c->t_inline.p; a.tok_len8 = (const uint8_t*)c->t_len8.p;

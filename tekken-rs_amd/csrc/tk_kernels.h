@@ -118,6 +118,44 @@ hipError_t tk_launch_decode_grouplen(const TkDecodeArgs& a, hipStream_t s);   //
 hipError_t tk_launch_decode_emit(const TkDecodeArgs& a, hipStream_t s);
 hipError_t tk_launch_decode_validate(const TkDecodeArgs& a, hipStream_t s);
 
+// ---- lossy decode (tk_decode_lossy.hip): the repair pass behind the strict pipeline, and the stream step ----
+#define TK_LOSSY_TILE 4096u        /* raw text bytes of a block's tile */
+#define TK_LOSSY_MAX_BLOCKS 2048u  /* grid cap of the two repair kernels (grid-stride beyond) */
+struct TkLossyArgs {
+    const uint8_t* bytes;      // the raw text of the batch (the emit kernel's output; readable 64 bytes past n_bytes)
+    uint64_t n_bytes;
+    const uint64_t* offs;      // [n_docs + 1] the raw text's document offsets
+    uint64_t n_docs;
+    const uint32_t* run_bits;  // the emit kernel's run starts, (n_bytes / 32 + 4) words
+    uint32_t* tile_cnt;        // [n_tiles] written by the counts kernel
+    const uint64_t* tile_offs; // [n_tiles + 1] their exclusive scan
+    uint8_t* out_bytes;        // the lossy text
+    uint64_t* out_offs;        // [n_docs + 1] its document offsets
+    uint32_t* bad_flags;       // [n_docs] zeroed: set for a document with a replacement
+    unsigned long long* stat;  // [0] U+FFFD written, [1] documents with one
+};
+hipError_t tk_launch_decode_lossy_counts(const TkLossyArgs& a, hipStream_t s);
+hipError_t tk_launch_decode_lossy_write(const TkLossyArgs& a, hipStream_t s);
+struct TkStreamArgs {
+    uint32_t* state;           // [n_seqs] the open prefix of every sequence (include/tekken_hip.h), rewritten by the write kernel
+    const uint32_t* ids;       // the step's new ids, ragged
+    const uint64_t* id_offs;   // [n_seqs + 1]
+    uint64_t n_seqs;
+    uint32_t* lens;            // [n_seqs] text bytes of the step, written by the count kernel
+    const uint64_t* out_offs;  // [n_seqs + 1] their exclusive scan
+    uint8_t* out_bytes;
+    unsigned long long* err;   // [0] first id index with a Raise-policy special token (or ~0), [1] first one outside the vocabulary
+    unsigned long long* stat;  // [0] U+FFFD written
+    const uint8_t* tok_blob;
+    const uint32_t* tok_offs;
+    const uint8_t* sp_blob;
+    const uint32_t* sp_offs;
+    uint32_t n_ranks, num_special;
+    int policy, flags;         // TK_POLICY_*, TK_STREAM_*
+};
+hipError_t tk_launch_decode_stream_count(const TkStreamArgs& a, hipStream_t s);
+hipError_t tk_launch_decode_stream_write(const TkStreamArgs& a, hipStream_t s);
+
 // ---- per-token byte spans (tk_spans.hip) ----
 struct TkSpansArgs {
     const uint32_t* ids;       // [n_ids] packed token ids of all documents
