@@ -35,6 +35,7 @@ extern "C" {
 #define TK_ERR_BASE64 (-8)           /* -> TokenizerError::Base64          (errors.rs:33-34) */
 #define TK_ERR_TOKEN_NOT_FOUND (-9)  /* -> TokenizerError::TokenNotFound   (errors.rs:49-50) */
 #define TK_ERR_SPECIAL_POLICY (-10)  /* -> TokenizerError::SpecialTokenPolicy (errors.rs:53-54) */
+#define TK_ERR_AUDIO (-11)           /* -> TokenizerError::Audio           (errors.rs; src/audio.rs:421, src/tekkenizer.rs:731) */
 
 #define TK_POLICY_IGNORE 0  /* SpecialTokenPolicy::Ignore  (src/special_tokens.rs:128-136) */
 #define TK_POLICY_KEEP 1    /* SpecialTokenPolicy::Keep  */
@@ -1285,6 +1286,84 @@ int tk_last_stats(const tk_ctx* ctx, uint64_t* n_long_docs, uint64_t* n_handed_b
 int tk_split_batch(tk_ctx* ctx, const uint8_t* bytes, const uint64_t* doc_offsets, uint64_t n_docs,
                    uint8_t* out_is_start);
 
+/* ---- audio: the ids of a clip, and the log-mel features its [AUDIO] positions stand for (src/audio.rs, src/tekkenizer.rs:697-760) ----
+ * The reference turns a clip into [BEGIN_AUDIO] [AUDIO]*N by integer frame arithmetic and executes no DSP; the features are the
+ * Whisper-style log-mel spectrogram that Voxtral's preprocessing computes from the same configuration fields.
+ * Config A = (sampling_rate sr, frame_rate fr, num_mel_bins M, hop_length H, window_size W, chunk_length_s: optional).
+ *   1. Padding (audio.rs:439-463), a clip of n samples: with chunk_length_s, cf = (usize)(chunk_length_s * sr) and
+ *      n' = ceil_div(n, cf) * cf (n = 0 stays 0); without, n' = max(n, W).  The padding is zeros at the end.
+ *   2. Frames (audio.rs:562-577): T = n' / H where H divides n', else ceil(n' as f64 / H as f64 - 1.0), evaluated in double as the
+ *      reference writes it (it equals floor(n' / H) wherever both were compared).
+ *   3. Tokens: per = (usize)(sr as f64 / fr / H as f64), N = ceil(T as f64 / per as f64); the ids are [BEGIN_AUDIO] + [AUDIO] * N.
+ *      per == 0 is TK_ERR_INVALID_CONFIG (the reference would divide by zero), and so is cf == 0.
+ *   4. Segments: with chunks a segment is one chunk of cf samples and has T_s = T(cf) frames; without, the whole padded clip is
+ *      the one segment.  Each segment is transformed on its own: reflection never reaches into a neighbour.
+ *   5. Features of a segment x[0 .. L), L > W / 2: the centred STFT torch.stft(x, W, H, window=hann_window(W), center=True,
+ *      pad_mode="reflect") with the last frame dropped.  w[i] = 0.5 - 0.5 cos(2 pi i / W) (periodic Hann); frame t < T_s reads
+ *      p[tH + i], i < W, p[j] = x[r(j - W/2)], r(q) = -q for q < 0, 2(L-1) - q for q >= L, q otherwise; power = |X_k|^2, k < F =
+ *      W/2 + 1; mel[m] = sum_k FB[k][m] power[k] with FB the reference's mel_filter_bank(F, M, 0, sr/2, sr) (audio.rs:684-748:
+ *      Slaney scale and normalisation, built in double, kept as f32); Lg = log10(max(mel, 1e-10)); Lg = max(Lg, Lmax - 8), Lmax
+ *      the maximum of Lg over the segment, or opts.log_mel_max where that is finite; feature = (Lg + 4) / 4, float32.
+ *   6. Layout: the segments of all clips back to back in clip order; segment s is [M][T_s] row-major at element M * frame_off[s]
+ *      (under a chunked config the whole output is a dense [S, M, T]).  clip_seg[c] .. clip_seg[c+1]: the segments of clip c.
+ *   7. The zero padding is never materialised.  NaN / Inf samples propagate as IEEE arithmetic makes them (a NaN that reaches a
+ *      segment's maximum is dropped by the maximum, as fmaxf does).  The transform is an exact-f32 product: no bf16 / fp16 operand.
+ *      A clip's features do not depend on what else is in the batch, nor on the stream.
+ *   8. tk_audio_set_config refuses (TK_ERR_INVALID_CONFIG) what the transform cannot do -- the loader keeps accepting what the
+ *      reference accepts --: W odd, W < 4, W > 2048, H == 0, H > W, M == 0, M > 256, sr == 0, fr <= 0, chunk_length_s <= 0, per == 0,
+ *      cf == 0 and a chunked config with cf <= W / 2.  The log-mel entries refuse (TK_ERR_INVALID_ARG, nothing written, an earlier
+ *      result stays readable) an unknown flag (checks or opts), a NULL required argument, sample offsets that do not start at 0,
+ *      decrease or do not end at n_samples (they are read on the host, which sizes the output from them: TK_CHECK_OFFSETS is
+ *      accepted and changes nothing), more than 2^32 - 16 clips or segments, an output beyond 2^36 elements; and with TK_ERR_AUDIO
+ *      a context without an audio config ("Audio encoder not configured").  A failed allocation is TK_ERR_RUNTIME.
+ *      n_clips == 0 and clips without a segment are valid. */
+typedef struct tk_audio_config {
+    uint64_t sampling_rate;
+    double frame_rate;
+    uint64_t num_mel_bins, hop_length, window_size;
+    double chunk_length_s;         /* valid where has_chunk_length != 0 */
+    uint32_t has_chunk_length, pad;
+} tk_audio_config;
+/* Steps 1-4 for n_clips clips of n_samples[c] samples: padded[c] = n', n_frames[c] = the sum of T_s over the clip's segments,
+ * n_tokens[c] = N, n_segments[c].  Any output may be NULL.  Pure host arithmetic, which the other audio entries use too.
+ * TK_ERR_INVALID_CONFIG: sr == 0, H == 0, W == 0, M == 0, fr <= 0, chunk_length_s <= 0 (what the reference's constructors refuse),
+ * per == 0, cf == 0. */
+int tk_audio_layout(const tk_audio_config* cfg, const uint64_t* n_samples, uint64_t n_clips, uint64_t* padded, uint64_t* n_frames,
+                    uint64_t* n_tokens, uint64_t* n_segments);
+/* Builds the transform's tables for cfg -- the [W][2F] matrix of w[i] cos(2 pi i k / W) | -w[i] sin(2 pi i k / W), computed in double
+ * and rounded once, and the filter bank as one (first_bin, n_bins, weights) run per mel filter -- and uploads them.  A refused
+ * config leaves the context's earlier one in place. */
+int tk_audio_set_config(tk_ctx* ctx, const tk_audio_config* cfg);
+typedef struct tk_logmel_opts { float log_mel_max; /* NaN (or +-Inf): the per-segment maximum */ uint32_t flags; /* none defined: 0 */ } tk_logmel_opts;
+typedef struct tk_logmel { float* features; uint64_t* frame_off; /* n_segments + 1 */ uint64_t* clip_seg; /* n_clips + 1 */
+                           uint64_t n_clips, n_segments, n_frames, n_mel; } tk_logmel;
+/* d_samples: float32, the clips back to back, unpadded; d_sample_offsets: n_clips + 1 uint64.  opts may be NULL (the per-segment
+ * maximum).  out: device pointers of buffers the context owns, apart from every other pass's, valid until the next log-mel call
+ * on the context.  The work is enqueued on hip_stream and the call returns after the stream has drained. */
+int tk_audio_logmel_device(tk_ctx* ctx, const void* d_samples, const void* d_sample_offsets, uint64_t n_clips, uint64_t n_samples,
+                           int checks, const tk_logmel_opts* opts, void* hip_stream, tk_logmel* out);
+/* Host in / host out: out's buffers are pinned host memory, released with tk_free_logmel. */
+int tk_audio_logmel(tk_ctx* ctx, const float* samples, const uint64_t* sample_offsets, uint64_t n_clips, const tk_logmel_opts* opts,
+                    tk_logmel* out);
+void tk_free_logmel(tk_logmel* out);
+/* The frames of a tile of the product kernel: tests place segment lengths around its multiples. */
+uint32_t tk_audio_frame_tile(void);
+/* GPU time of the context's last log-mel call from events on its stream: ms[0] the product kernel, ms[1] the clamp kernel (0
+ * with a fixed log_mel_max: it is not launched).  Both 0 where the call was refused. */
+void tk_last_logmel_ms(const tk_ctx* ctx, float ms[2]);
+
+/* ---- audio parts in chat rows: the ragged input of the join pass, built on the device ----
+ * The join pass treats a part as "control id, then ids", so an audio part is control id [BEGIN_AUDIO] in front of N times [AUDIO].
+ * Per part p the splice emits the part's own ids ids[offs[p] .. offs[p+1]) followed by part_tokens[p] copies of fill_id, with
+ * new offsets: counts, one scan and a fill kernel.  d_part_tokens: n_parts uint32 (0 for a text part).  d_id_offsets is NOT
+ * checked.  TK_ERR_INVALID_ARG, nothing written, an earlier result stays readable: a NULL required argument, n_parts >= 2^32 - 16.
+ * out: device pointers of buffers the context owns, apart from every other pass's, valid until the next splice on the context. */
+typedef struct tk_ragged { uint32_t* ids; uint64_t* offsets; uint64_t n_parts, n_ids; } tk_ragged;
+int tk_audio_splice_device(tk_ctx* ctx, const void* d_ids, const void* d_id_offsets, uint64_t n_parts, uint64_t n_ids,
+                           const void* d_part_tokens, uint32_t fill_id, void* hip_stream, tk_ragged* out);
+/* How many splice calls on the context got as far as their buffers (tests: a batch without audio never does). */
+uint64_t tk_audio_splice_calls(const tk_ctx* ctx);
+
 /* ------------------------------------------------------------------------------------------
  * Tokenizer level: the host-side mirror of tekken::tekkenizer::Tekkenizer, exported so that
  * non-C++ hosts (the Rust shim, Python tests) can drive loader + encode + decode.
@@ -1353,6 +1432,17 @@ int tk_tokenizer_id_to_byte_piece(tk_tokenizer* t, uint32_t id, int policy, uint
  * and whether the object came from a TK_TABLE_CACHE_DIR side file (row f-2) rather than from parsing the JSON. */
 const char* tk_tokenizer_json_pattern(const tk_tokenizer* t);
 int tk_tokenizer_from_cache(const tk_tokenizer* t);
+/* Audio (src/tekkenizer.rs:697-760).  has_audio: the tekken.json carried an `audio` object (has_audio_support).  audio_config /
+ * audio_ids: TK_ERR_AUDIO "Audio encoder not configured" without one.  encode_audio is the reference's signature minus the
+ * waveform copy: a clip of n_samples samples at clip_rate -> *ids = [BEGIN_AUDIO] + [AUDIO] * N (malloc'ed, tk_free_ids) and
+ * *padded_samples = n' (optional); a clip_rate other than the config's is TK_ERR_AUDIO "Resampling not yet implemented", as in
+ * the reference (audio.rs:415-424).  A device-backed tokenizer has its engine context configured (tk_audio_set_config) at
+ * construction where the transform can do the config. */
+int tk_tokenizer_has_audio(const tk_tokenizer* t);
+int tk_tokenizer_audio_config(tk_tokenizer* t, tk_audio_config* out);
+int tk_tokenizer_audio_ids(tk_tokenizer* t, uint32_t* audio_id, uint32_t* begin_audio_id);
+int tk_tokenizer_encode_audio(tk_tokenizer* t, uint64_t n_samples, uint64_t clip_rate, uint32_t** ids, size_t* n_ids,
+                              uint64_t* padded_samples);
 /* The engine context behind the tokenizer (NULL for host-only objects). */
 tk_ctx* tk_tokenizer_ctx(tk_tokenizer* t);
 /* The validated rank table (for building an oracle beside it in tests). */

@@ -36,6 +36,7 @@ pub const TK_ERR_NO_DEVICE: c_int = -4;
 pub const TK_ERR_INVALID_ARG: c_int = -5;
 pub const TK_ERR_TOKEN_NOT_FOUND: c_int = -9;
 pub const TK_ERR_SPECIAL_POLICY: c_int = -10;
+pub const TK_ERR_AUDIO: c_int = -11;
 
 // the checks of the spans entries (above TK_CHECK_OFFSETS = 1 / TK_CHECK_UTF8 = 2: one word can carry all four)
 pub const TK_STREAM_FINAL: c_int = 1;
@@ -52,6 +53,42 @@ pub const TK_DENSE_TRUNC_LEFT: u32 = 2;
 pub const TK_DENSE_FIXED: u32 = 4;
 pub const TK_DENSE_I64: u32 = 8;
 pub const TK_DENSE_MASK: u32 = 16;
+// audio (include/tekken_hip.h "audio"): the config of the tekken.json, the log-mel options and result, a ragged result
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct TkAudioConfig {
+    pub sampling_rate: u64,
+    pub frame_rate: f64,
+    pub num_mel_bins: u64,
+    pub hop_length: u64,
+    pub window_size: u64,
+    pub chunk_length_s: f64, // valid where has_chunk_length != 0
+    pub has_chunk_length: u32,
+    pub pad: u32,
+}
+#[repr(C)]
+pub struct TkLogmelOpts {
+    pub log_mel_max: f32, // NaN: the per-segment maximum
+    pub flags: u32,
+}
+#[repr(C)]
+pub struct TkLogmel {
+    pub features: *mut f32,
+    pub frame_off: *mut u64, // n_segments + 1
+    pub clip_seg: *mut u64,  // n_clips + 1
+    pub n_clips: u64,
+    pub n_segments: u64,
+    pub n_frames: u64,
+    pub n_mel: u64,
+}
+#[repr(C)]
+pub struct TkRagged {
+    pub ids: *mut u32,
+    pub offsets: *mut u64,
+    pub n_parts: u64,
+    pub n_ids: u64,
+}
+
 #[repr(C)]
 pub struct TkDenseOpts {
     pub max_length: u32,
@@ -673,6 +710,29 @@ extern "C" {
     pub fn tk_last_decode_lossy_ms(ctx: *const TkCtx, strict_ms: *mut f32, repair_ms: *mut f32);
     pub fn tk_last_decode_lossy_stats(ctx: *const TkCtx, n_replaced: *mut u64, n_bad_docs: *mut u64, n_repair_launches: *mut u64);
     pub fn tk_ctx_set_pattern(ctx: *mut TkCtx, mode: c_int) -> c_int;
+    // audio: the ids of a clip ([BEGIN_AUDIO] + [AUDIO] * N), the log-mel features of a batch of clips, the splice of audio parts
+    pub fn tk_tokenizer_from_file(path: *const c_char, device_id: c_int, out: *mut *mut TkTokenizer) -> c_int;
+    pub fn tk_tokenizer_destroy(t: *mut TkTokenizer);
+    pub fn tk_tokenizer_last_error(t: *const TkTokenizer) -> *const c_char;
+    pub fn tk_tokenizer_ctx(t: *mut TkTokenizer) -> *mut TkCtx;
+    pub fn tk_tokenizer_has_audio(t: *const TkTokenizer) -> c_int;
+    pub fn tk_tokenizer_audio_config(t: *mut TkTokenizer, out: *mut TkAudioConfig) -> c_int;
+    pub fn tk_tokenizer_audio_ids(t: *mut TkTokenizer, audio_id: *mut u32, begin_audio_id: *mut u32) -> c_int;
+    pub fn tk_tokenizer_encode_audio(t: *mut TkTokenizer, n_samples: u64, clip_rate: u64, ids: *mut *mut u32, n_ids: *mut usize,
+                                     padded_samples: *mut u64) -> c_int;
+    pub fn tk_audio_layout(cfg: *const TkAudioConfig, n_samples: *const u64, n_clips: u64, padded: *mut u64, n_frames: *mut u64,
+                           n_tokens: *mut u64, n_segments: *mut u64) -> c_int;
+    pub fn tk_audio_set_config(ctx: *mut TkCtx, cfg: *const TkAudioConfig) -> c_int;
+    pub fn tk_audio_logmel_device(ctx: *mut TkCtx, d_samples: *const c_void, d_sample_offsets: *const c_void, n_clips: u64, n_samples: u64,
+                                  checks: c_int, opts: *const TkLogmelOpts, hip_stream: *mut c_void, out: *mut TkLogmel) -> c_int;
+    pub fn tk_audio_logmel(ctx: *mut TkCtx, samples: *const f32, sample_offsets: *const u64, n_clips: u64, opts: *const TkLogmelOpts,
+                           out: *mut TkLogmel) -> c_int;
+    pub fn tk_free_logmel(out: *mut TkLogmel);
+    pub fn tk_audio_frame_tile() -> u32;
+    pub fn tk_last_logmel_ms(ctx: *const TkCtx, ms: *mut f32);
+    pub fn tk_audio_splice_device(ctx: *mut TkCtx, d_ids: *const c_void, d_id_offsets: *const c_void, n_parts: u64, n_ids: u64,
+                                  d_part_tokens: *const c_void, fill_id: u32, hip_stream: *mut c_void, out: *mut TkRagged) -> c_int;
+    pub fn tk_audio_splice_calls(ctx: *const TkCtx) -> u64;
 
     // node level: every GPU of the node behind one call (north star: documents sharded across the GPUs, one RCCL
     // gather of the id buffers over xGMI); SURVEY section 8b `ctx_create(.., device_ids[], n_devices, ..)`

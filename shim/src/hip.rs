@@ -10,13 +10,14 @@ pub enum HipError {
     InvalidConfig(String),
     TokenNotFound(String),
     SpecialTokenPolicy(String),
+    Audio(String),
     Tokenizers(String),
 }
 
 impl std::fmt::Display for HipError {
     fn fmt(&self, f: &mut std::fmt::Formatter<'_>) -> std::fmt::Result {
         match self {
-            HipError::InvalidConfig(m) | HipError::TokenNotFound(m) | HipError::SpecialTokenPolicy(m) | HipError::Tokenizers(m) => f.write_str(m),
+            HipError::InvalidConfig(m) | HipError::TokenNotFound(m) | HipError::SpecialTokenPolicy(m) | HipError::Audio(m) | HipError::Tokenizers(m) => f.write_str(m),
         }
     }
 }
@@ -28,6 +29,7 @@ fn map_err(rc: c_int, msg: *const std::os::raw::c_char) -> HipError {
         TK_ERR_INVALID_CONFIG | TK_ERR_INVALID_ARG => HipError::InvalidConfig(msg),
         TK_ERR_TOKEN_NOT_FOUND => HipError::TokenNotFound(msg),
         TK_ERR_SPECIAL_POLICY => HipError::SpecialTokenPolicy(msg),
+        TK_ERR_AUDIO => HipError::Audio(msg),
         _ => HipError::Tokenizers(msg), // runtime / no device / invalid UTF-8
     }
 }
@@ -244,6 +246,88 @@ impl HipEngine {
 impl Drop for HipEngine {
     fn drop(&mut self) {
         unsafe { tk_ctx_destroy(self.ctx) }
+    }
+}
+
+/// The host mirror of `Tekkenizer` for the audio surface (src/tekkenizer.rs:697-760): `has_audio_support`, `audio_config`,
+/// `encode_audio`, and the log-mel features of a batch of clips on the tokenizer's GPU.
+pub struct HipTekkenizer {
+    t: *mut TkTokenizer,
+}
+unsafe impl Send for HipTekkenizer {}
+
+/// `AudioEncoding` (src/audio.rs:476-479): the ids and the clip padded as the reference pads it.
+pub struct HipAudioEncoding {
+    pub tokens: Vec<u32>,
+    pub audio: Vec<f32>,
+    pub sampling_rate: usize,
+}
+
+impl HipTekkenizer {
+    pub fn from_file(path: &str, device: i32) -> Result<Self, HipError> {
+        let c = std::ffi::CString::new(path).map_err(|e| HipError::InvalidConfig(e.to_string()))?;
+        let mut t: *mut TkTokenizer = std::ptr::null_mut();
+        let rc = unsafe { tk_tokenizer_from_file(c.as_ptr(), device, &mut t) };
+        if rc != TK_OK {
+            return Err(map_err(rc, unsafe { tk_tokenizer_last_error(std::ptr::null()) }));
+        }
+        Ok(Self { t })
+    }
+    fn err(&self, rc: c_int) -> HipError {
+        map_err(rc, unsafe { tk_tokenizer_last_error(self.t) })
+    }
+    pub fn has_audio_support(&self) -> bool {
+        unsafe { tk_tokenizer_has_audio(self.t) != 0 }
+    }
+    pub fn audio_config(&self) -> Option<TkAudioConfig> {
+        let mut a = TkAudioConfig::default();
+        if unsafe { tk_tokenizer_audio_config(self.t, &mut a) } == TK_OK { Some(a) } else { None }
+    }
+    /// `Tekkenizer::encode_audio`: `[BEGIN_AUDIO] + [AUDIO] * N` and the padded clip; a clip at another rate is
+    /// `Audio("Resampling not yet implemented")`, a tokenizer without audio `Audio("Audio encoder not configured")`.
+    pub fn encode_audio(&self, samples: &[f32], sampling_rate: usize) -> Result<HipAudioEncoding, HipError> {
+        let (mut ids, mut n, mut padded) = (std::ptr::null_mut::<u32>(), 0usize, 0u64);
+        let rc = unsafe { tk_tokenizer_encode_audio(self.t, samples.len() as u64, sampling_rate as u64, &mut ids, &mut n, &mut padded) };
+        if rc != TK_OK {
+            return Err(self.err(rc));
+        }
+        let tokens = unsafe { std::slice::from_raw_parts(ids, n).to_vec() };
+        unsafe { tk_free_ids(ids) };
+        let mut audio = samples.to_vec();
+        audio.resize(padded as usize, 0.0);
+        Ok(HipAudioEncoding { tokens, audio, sampling_rate })
+    }
+    /// The log-mel features of a batch of clips (tk_audio_logmel): `(features, frame_off [S + 1], clip_seg [n + 1], n_mel)`;
+    /// segment s is `[n_mel][T_s]` row-major at element `n_mel * frame_off[s]`.
+    pub fn audio_features(&self, clips: &[&[f32]]) -> Result<(Vec<f32>, Vec<u64>, Vec<u64>, u64), HipError> {
+        let ctx = unsafe { tk_tokenizer_ctx(self.t) };
+        let mut offs: Vec<u64> = vec![0];
+        let mut flat: Vec<f32> = Vec::new();
+        for c in clips {
+            flat.extend_from_slice(c);
+            offs.push(flat.len() as u64);
+        }
+        let opts = TkLogmelOpts { log_mel_max: f32::NAN, flags: 0 };
+        let mut r = TkLogmel { features: std::ptr::null_mut(), frame_off: std::ptr::null_mut(), clip_seg: std::ptr::null_mut(),
+                               n_clips: 0, n_segments: 0, n_frames: 0, n_mel: 0 };
+        let rc = unsafe { tk_audio_logmel(ctx, flat.as_ptr(), offs.as_ptr(), clips.len() as u64, &opts, &mut r) };
+        if rc != TK_OK {
+            return Err(map_err(rc, unsafe { tk_last_error(ctx) }));
+        }
+        let out = unsafe {
+            let f = std::slice::from_raw_parts(r.features as *const f32, (r.n_mel * r.n_frames) as usize).to_vec();
+            let fo = std::slice::from_raw_parts(r.frame_off as *const u64, r.n_segments as usize + 1).to_vec();
+            let cs = std::slice::from_raw_parts(r.clip_seg as *const u64, r.n_clips as usize + 1).to_vec();
+            let m = r.n_mel;
+            tk_free_logmel(&mut r);
+            (f, fo, cs, m)
+        };
+        Ok(out)
+    }
+}
+impl Drop for HipTekkenizer {
+    fn drop(&mut self) {
+        unsafe { tk_tokenizer_destroy(self.t) }
     }
 }
 

@@ -74,6 +74,7 @@ TK_ERR_JSON = -7
 TK_ERR_BASE64 = -8
 TK_ERR_TOKEN_NOT_FOUND = -9
 TK_ERR_SPECIAL_POLICY = -10
+TK_ERR_AUDIO = -11
 
 
 class TokenizerError(Exception):
@@ -81,7 +82,7 @@ class TokenizerError(Exception):
     KIND = {TK_ERR_INVALID_CONFIG: "InvalidConfig", TK_ERR_RUNTIME: "Tokenizers", TK_ERR_INVALID_UTF8: "Tokenizers",
             TK_ERR_NO_DEVICE: "Tokenizers", TK_ERR_INVALID_ARG: "InvalidConfig", TK_ERR_IO: "Io", TK_ERR_JSON: "Json",
             TK_ERR_BASE64: "Base64", TK_ERR_TOKEN_NOT_FOUND: "TokenNotFound",
-            TK_ERR_SPECIAL_POLICY: "SpecialTokenPolicy"}
+            TK_ERR_SPECIAL_POLICY: "SpecialTokenPolicy", TK_ERR_AUDIO: "Audio"}
 
     def __init__(self, code, message):
         self.code = code
@@ -250,6 +251,25 @@ class _Words(ctypes.Structure):
 
 
 _LIB = None
+
+
+class _AudioConfig(ctypes.Structure):
+    _fields_ = [("sampling_rate", ctypes.c_uint64), ("frame_rate", ctypes.c_double), ("num_mel_bins", ctypes.c_uint64),
+                ("hop_length", ctypes.c_uint64), ("window_size", ctypes.c_uint64), ("chunk_length_s", ctypes.c_double),
+                ("has_chunk_length", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
+class _LogmelOpts(ctypes.Structure):
+    _fields_ = [("log_mel_max", ctypes.c_float), ("flags", ctypes.c_uint32)]
+
+
+class _Logmel(ctypes.Structure):
+    _fields_ = [("features", ctypes.c_void_p), ("frame_off", ctypes.c_void_p), ("clip_seg", ctypes.c_void_p), ("n_clips", ctypes.c_uint64),
+                ("n_segments", ctypes.c_uint64), ("n_frames", ctypes.c_uint64), ("n_mel", ctypes.c_uint64)]
+
+
+class _Ragged(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("n_parts", ctypes.c_uint64), ("n_ids", ctypes.c_uint64)]
 
 
 def build(force=False):
@@ -554,6 +574,34 @@ def lib():
     L.tk_tokenizer_rank_table.restype = ctypes.c_int
     L.tk_tokenizer_rank_table.argtypes = [vp, ctypes.POINTER(u8p), ctypes.POINTER(u32p), u32p]
     _LIB = L
+    if hasattr(L, "tk_audio_logmel_device"):   # (audio: libraries built before it still load through TK_HIP_LIB)
+        acp, lop, lmp, rgp = ctypes.POINTER(_AudioConfig), ctypes.POINTER(_LogmelOpts), ctypes.POINTER(_Logmel), ctypes.POINTER(_Ragged)
+        L.tk_audio_layout.restype = ci
+        L.tk_audio_layout.argtypes = [acp, u64p, u64, u64p, u64p, u64p, u64p]
+        L.tk_audio_set_config.restype = ci
+        L.tk_audio_set_config.argtypes = [vp, acp]
+        L.tk_audio_logmel_device.restype = ci
+        L.tk_audio_logmel_device.argtypes = [vp, vp, vp, u64, u64, ci, lop, vp, lmp]
+        L.tk_audio_logmel.restype = ci
+        L.tk_audio_logmel.argtypes = [vp, ctypes.POINTER(ctypes.c_float), u64p, u64, lop, lmp]
+        L.tk_free_logmel.restype = None
+        L.tk_free_logmel.argtypes = [lmp]
+        L.tk_audio_frame_tile.restype = ctypes.c_uint32
+        L.tk_audio_frame_tile.argtypes = []
+        L.tk_last_logmel_ms.restype = None
+        L.tk_last_logmel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float * 2)]
+        L.tk_audio_splice_device.restype = ci
+        L.tk_audio_splice_device.argtypes = [vp, vp, vp, u64, u64, vp, ctypes.c_uint32, vp, rgp]
+        L.tk_audio_splice_calls.restype = u64
+        L.tk_audio_splice_calls.argtypes = [vp]
+        L.tk_tokenizer_has_audio.restype = ci
+        L.tk_tokenizer_has_audio.argtypes = [vp]
+        L.tk_tokenizer_audio_config.restype = ci
+        L.tk_tokenizer_audio_config.argtypes = [vp, acp]
+        L.tk_tokenizer_audio_ids.restype = ci
+        L.tk_tokenizer_audio_ids.argtypes = [vp, u32p, u32p]
+        L.tk_tokenizer_encode_audio.restype = ci
+        L.tk_tokenizer_encode_audio.argtypes = [vp, u64, u64, ctypes.POINTER(u32p), ctypes.POINTER(ctypes.c_size_t), u64p]
     if hasattr(L, "tk_noise_replace_device"):   # (masked-LM and span-corruption rows: libraries built before them still load through TK_HIP_LIB)
         nop = ctypes.POINTER(_NoiseOpts)
         for mode, st in (("replace", _NoiseReplace), ("spans", _NoiseSpans)):
@@ -614,7 +662,7 @@ def _torch_wrap(view, copy):
         return None
     cai = view.__cuda_array_interface__
     if 0 in cai["shape"]:     # (nothing behind the pointer to look at)
-        return torch.empty(cai["shape"], dtype={"<i4": torch.int32, "<i8": torch.int64, "|u1": torch.uint8}[cai["typestr"]], device="cuda")
+        return torch.empty(cai["shape"], dtype={"<i4": torch.int32, "<i8": torch.int64, "|u1": torch.uint8, "<f4": torch.float32}[cai["typestr"]], device="cuda")
     t = torch.as_tensor(view, device="cuda")
     return t.clone() if copy else t
 
@@ -1070,6 +1118,90 @@ class NoiseSpansResult(_LayoutResult):
 _NOISE = {"replace": (_NoiseReplace, NoiseReplaceResult), "spans": (_NoiseSpans, NoiseSpansResult)}
 
 
+class LogmelResult(_LayoutResult):
+    """What tk_audio_logmel_device returns (tk_logmel): raw device pointers of context-owned buffers, valid until the next log-mel
+    call on the context.  features_ptr: float32, segment s is [n_mel, T_s] at element n_mel * frame_off[s]; frame_off_ptr: uint64
+    [n_segments + 1]; clip_seg_ptr: uint64 [n_clips + 1].  views(): (features float32 [n_mel * n_frames], frame_off as int64,
+    clip_seg as int64)."""
+    STRUCT, PASS = _Logmel, "logmel"
+    OUTPUTS = (("features", "<f4", lambda r: (r.n_mel * r.n_frames,), np.float32, False),
+               ("frame_off", "<i8", lambda r: (r.n_segments + 1,), np.uint64, False),
+               ("clip_seg", "<i8", lambda r: (r.n_clips + 1,), np.uint64, False))
+    COUNTS = ("n_clips", "n_segments", "n_frames", "n_mel")
+    DICT_COUNTS = ("n_clips", "n_segments", "n_frames", "n_mel")
+
+
+class RaggedResult(_LayoutResult):
+    """What tk_audio_splice_device returns (tk_ragged): ids_ptr uint32 [n_ids], offsets_ptr uint64 [n_parts + 1], context-owned, valid
+    until the next splice on the context.  views(): (ids as int32, offsets as int64)."""
+    STRUCT, PASS = _Ragged, "ragged"
+    OUTPUTS = (("ids", "<i4", lambda r: (r.n_ids,), np.uint32, False), ("offsets", "<i8", lambda r: (r.n_parts + 1,), np.uint64, False))
+    COUNTS = ("n_parts", "n_ids")
+    DICT_COUNTS = ("n_ids",)
+
+
+class Audio:
+    """A clip: .audio_array float32 [n] and .sampling_rate (reference src/audio.rs:212-217)."""
+
+    def __init__(self, samples, sampling_rate):
+        self.audio_array = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        self.sampling_rate = int(sampling_rate)
+
+    def __len__(self):
+        return len(self.audio_array)
+
+    @classmethod
+    def from_wav(cls, path_or_bytes):
+        """A PCM WAV file (a path, or its bytes) through the stdlib `wave` module: 8 / 16 / 24 / 32-bit samples scaled by
+        2^(bits - 1) (8-bit is unsigned around 128), the channels averaged.  Deviation from the reference: it divides integer PCM
+        by i32::MAX whatever the bit depth (audio.rs Audio::from_file), which scales 16-bit audio by 2^-16 and pushes speech under
+        the 1e-10 floor of the log-mel features."""
+        import io
+        import wave
+        src = io.BytesIO(bytes(path_or_bytes)) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else os.fspath(path_or_bytes)
+        try:
+            with wave.open(src, "rb") as w:
+                ch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
+                raw = w.readframes(n)
+        except (wave.Error, EOFError) as e:
+            raise TokenizerError(TK_ERR_AUDIO, "WAV: %s" % (e,))
+        if width == 1:
+            x = (np.frombuffer(raw, np.uint8).astype(np.float64) - 128.0) / 128.0
+        elif width == 2:
+            x = np.frombuffer(raw, "<i2").astype(np.float64) / 32768.0
+        elif width == 3:
+            b = np.frombuffer(raw, np.uint8).reshape(-1, 3).astype(np.int32)
+            v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+            x = (v - ((v & 0x800000) << 1)).astype(np.float64) / 8388608.0
+        elif width == 4:
+            x = np.frombuffer(raw, "<i4").astype(np.float64) / 2147483648.0
+        else:
+            raise TokenizerError(TK_ERR_AUDIO, "WAV: %d-byte samples" % width)
+        x = x[:len(x) // ch * ch].reshape(-1, ch).mean(axis=1) if ch > 1 else x
+        return cls(x.astype(np.float32), rate)
+
+
+def _audio_config_struct(cfg):
+    """An audio config (a dict with the fields of tk_audio_config; chunk_length_s None or absent: none) as the C struct."""
+    if isinstance(cfg, _AudioConfig):
+        return cfg
+    cl = cfg.get("chunk_length_s")
+    return _AudioConfig(int(cfg["sampling_rate"]), float(cfg["frame_rate"]), int(cfg["num_mel_bins"]), int(cfg["hop_length"]),
+                        int(cfg["window_size"]), float(cl) if cl is not None else 0.0, 1 if cl is not None else 0, 0)
+
+
+def audio_layout(cfg, n_samples):
+    """tk_audio_layout: the host arithmetic of a batch of clips -> (padded, n_frames, n_tokens, n_segments), uint64 [n_clips] each."""
+    st = _audio_config_struct(cfg)
+    n = np.ascontiguousarray(n_samples, dtype=np.uint64).reshape(-1)
+    out = [np.zeros(max(len(n), 1), np.uint64) for _ in range(4)]
+    nb = n if len(n) else np.zeros(1, np.uint64)
+    rc = _need("tk_audio_layout")(ctypes.byref(st), _p(nb, ctypes.c_uint64), len(n), *[_p(o, ctypes.c_uint64) for o in out])
+    if rc != TK_OK:
+        raise TokenizerError(rc, "audio config: a zero or negative field, or no whole frame per token")
+    return tuple(o[:len(n)] for o in out)
+
+
 class Engine:
     """Engine-level context: the replacement for CoreBPE (reference src/tekkenizer.rs:125, 384-386)."""
 
@@ -1108,6 +1240,50 @@ class Engine:
         rc = _need(name)(self._h, *args)
         if rc != TK_OK:
             raise self._err(rc)
+
+    def audio_set_config(self, cfg):
+        """tk_audio_set_config: builds and uploads the log-mel tables for cfg (a dict with the fields of tk_audio_config)."""
+        st = _audio_config_struct(cfg)
+        self._call("tk_audio_set_config", ctypes.byref(st))
+
+    @staticmethod
+    def _logmel_opts(log_mel_max, flags):
+        return _LogmelOpts(float("nan") if log_mel_max is None else float(log_mel_max), int(flags))
+
+    def audio_logmel_device(self, d_samples_ptr, d_offs_ptr, n_clips, n_samples, log_mel_max=None, checks=0, stream=0, flags=0):
+        """tk_audio_logmel_device: float32 samples of all clips back to back (unpadded) and their uint64 offsets [n_clips + 1] in
+        HBM -> a LogmelResult (context-owned device buffers); the definition is in include/tekken_hip.h.  log_mel_max None: the
+        per-segment maximum."""
+        o, r = self._logmel_opts(log_mel_max, flags), _Logmel()
+        self._call("tk_audio_logmel_device", ctypes.c_void_p(d_samples_ptr or None), ctypes.c_void_p(d_offs_ptr or None), n_clips, n_samples,
+                   int(checks), ctypes.byref(o), ctypes.c_void_p(stream), ctypes.byref(r))
+        return LogmelResult(r)
+
+    def audio_logmel(self, samples, offs, log_mel_max=None, flags=0):
+        """tk_audio_logmel, host in / host out: a dict of numpy arrays (features float32 [n_mel * n_frames], frame_off uint64,
+        clip_seg uint64) and the counts."""
+        x = np.ascontiguousarray(samples, dtype=np.float32)
+        oo = np.ascontiguousarray(offs, dtype=np.uint64)
+        o, r = self._logmel_opts(log_mel_max, flags), _Logmel()
+        xb = x if len(x) else np.zeros(1, np.float32)
+        self._call("tk_audio_logmel", _p(xb, ctypes.c_float), _p(oo, ctypes.c_uint64), len(oo) - 1, ctypes.byref(o), ctypes.byref(r))
+        return LogmelResult.take(r)[1]
+
+    def last_logmel_ms(self):
+        """(product kernel, clamp kernel) GPU milliseconds of the context's last log-mel call."""
+        ms = (ctypes.c_float * 2)()
+        _need("tk_last_logmel_ms")(self._h, ctypes.byref(ms))
+        return tuple(float(v) for v in ms)
+
+    def audio_splice_device(self, d_ids_ptr, d_id_offs_ptr, n_parts, n_ids, d_part_tokens_ptr, fill_id, stream=0):
+        """tk_audio_splice_device: per part its own ids, then part_tokens[p] copies of fill_id -> a RaggedResult (context-owned)."""
+        r = _Ragged()
+        self._call("tk_audio_splice_device", ctypes.c_void_p(d_ids_ptr or None), ctypes.c_void_p(d_id_offs_ptr or None), n_parts, n_ids,
+                   ctypes.c_void_p(d_part_tokens_ptr or None), int(fill_id), ctypes.c_void_p(stream), ctypes.byref(r))
+        return RaggedResult(r)
+
+    def audio_splice_calls(self):
+        return int(_need("tk_audio_splice_calls")(self._h))
 
     def encode_batch(self, data, offs, add_bos=True, add_eos=True, validate_utf8=False):
         """Host buffers in, host buffers out: (ids uint32[T], out_offsets uint64[D+1])."""
@@ -2171,6 +2347,102 @@ class Tekkenizer:
     def _err(self, rc):
         return TokenizerError(rc, lib().tk_tokenizer_last_error(self._h).decode())
 
+    # ---- audio (reference src/tekkenizer.rs:697-760) ----
+    @property
+    def has_audio_support(self):
+        return bool(_need("tk_tokenizer_has_audio")(self._h))
+
+    @property
+    def audio_config(self):
+        """The AudioConfig of the loaded tekken.json as a dict (chunk_length_s None where it has none); None without audio."""
+        if not self.has_audio_support:
+            return None
+        st = _AudioConfig()
+        rc = _need("tk_tokenizer_audio_config")(self._h, ctypes.byref(st))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return {"sampling_rate": int(st.sampling_rate), "frame_rate": float(st.frame_rate), "num_mel_bins": int(st.num_mel_bins),
+                "hop_length": int(st.hop_length), "window_size": int(st.window_size),
+                "chunk_length_s": float(st.chunk_length_s) if st.has_chunk_length else None}
+
+    def _audio_ids(self):
+        a, b = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = _need("tk_tokenizer_audio_ids")(self._h, ctypes.byref(a), ctypes.byref(b))
+        if rc != TK_OK:
+            raise self._err(rc)
+        return a.value, b.value
+
+    @property
+    def audio_token_id(self):
+        return self._audio_ids()[0]
+
+    @property
+    def begin_audio_token_id(self):
+        return self._audio_ids()[1]
+
+    def _audio_count(self, audio):
+        """(ids, padded samples) of one clip: tk_tokenizer_encode_audio."""
+        ids = ctypes.POINTER(ctypes.c_uint32)()
+        n, padded = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        rc = _need("tk_tokenizer_encode_audio")(self._h, len(audio.audio_array), int(audio.sampling_rate), ctypes.byref(ids), ctypes.byref(n),
+                                                ctypes.byref(padded))
+        if rc != TK_OK:
+            raise self._err(rc)
+        out = np.ctypeslib.as_array(ids, shape=(n.value,)).copy()
+        lib().tk_free_ids(ids)
+        return out, int(padded.value)
+
+    def encode_audio(self, audio):
+        """Tekkenizer::encode_audio (src/tekkenizer.rs:728-735): (ids, the padded clip) -- [BEGIN_AUDIO] + [AUDIO] * N."""
+        ids, padded = self._audio_count(audio)
+        x = np.zeros(padded, np.float32)
+        x[:len(audio.audio_array)] = audio.audio_array
+        return ids.tolist(), Audio(x, audio.sampling_rate)
+
+    def _audio_features(self, eng, audios):
+        """The clips go up once; -> (LogmelResult, the device samples, kept alive with it)."""
+        import torch
+        lens = [len(a.audio_array) for a in audios]
+        offs = np.zeros(len(audios) + 1, np.int64)
+        if audios:
+            offs[1:] = np.cumsum(lens)
+        flat = np.concatenate([a.audio_array for a in audios]) if int(offs[-1]) else np.zeros(1, np.float32)
+        d_x, d_o = torch.from_numpy(flat).cuda(), torch.from_numpy(offs).cuda()
+        r = eng.audio_logmel_device(d_x.data_ptr(), d_o.data_ptr(), len(audios), int(offs[-1]), checks=CHECK_OFFSETS,
+                                    stream=torch.cuda.current_stream().cuda_stream)
+        return r
+
+    def _feature_tensors(self, r, copy=True):
+        """features of a LogmelResult: [S, M, T] under a chunked config, else a list of [M, T_s] views of one tensor."""
+        import torch
+        v = r.views()
+        flat = _torch_wrap(v[0], copy)
+        fo = _torch_wrap(v[1], True).cpu().numpy().astype(np.uint64)
+        cs = _torch_wrap(v[2], True).cpu().numpy().astype(np.uint64)
+        M = r.n_mel
+        if self.audio_config["chunk_length_s"] is not None:
+            T = int(fo[1] - fo[0]) if r.n_segments else 0
+            feats = flat.reshape(r.n_segments, M, T) if r.n_segments else torch.empty((0, M, 0), dtype=torch.float32, device="cuda")
+        else:
+            feats = [flat[M * int(fo[k]):M * int(fo[k + 1])].reshape(M, int(fo[k + 1] - fo[k])) for k in range(r.n_segments)]
+        return feats, fo, cs
+
+    def encode_audio_batch(self, audios, return_features=True, copy=True):
+        """encode_audio over a batch of clips -> {"ids": uint32 [N] the clips' ids back to back, "offsets": uint64 [n + 1],
+        "tokens_per_clip": the [AUDIO] count of each, "features": the log-mel features on the tokenizer's GPU ([S, M, T] float32
+        under a chunked config, else a list of [M, T_i] views; None without return_features), "frame_off": uint64 [S + 1],
+        "clip_seg": uint64 [n + 1]}.  The definition of the features is in include/tekken_hip.h."""
+        per = [self._audio_count(a)[0] for a in audios]
+        offs = np.zeros(len(audios) + 1, np.uint64)
+        if audios:
+            offs[1:] = np.cumsum([len(x) for x in per], dtype=np.uint64)
+        out = {"ids": np.concatenate(per).astype(np.uint32) if per else np.zeros(0, np.uint32), "offsets": offs,
+               "tokens_per_clip": np.array([len(x) - 1 for x in per], np.uint64), "features": None, "frame_off": None, "clip_seg": None}
+        if return_features:
+            r = self._audio_features(self._device_engine(), audios)
+            out["features"], out["frame_off"], out["clip_seg"] = self._feature_tensors(r, copy)
+        return out
+
     def set_honour_pattern(self, honour=True):
         """Opt-in (row f-3): use the `pattern` of the loaded tekken.json instead of ignoring it like the reference does."""
         rc = lib().tk_tokenizer_set_honour_pattern(self._h, int(bool(honour)))
@@ -2748,14 +3020,24 @@ class Tekkenizer:
     CHAT_ROLES = {"user": ("[INST]", "[/INST]", False), "system": ("[SYSTEM_PROMPT]", "[/SYSTEM_PROMPT]", False),
                   "assistant": (None, "</s>", True)}
 
-    def _parts_of(self, convs):
-        """Conversations of (ctrl, text, label) parts -> (data, offs, part_ctrl, part_flags, conv_offs) as the join entries take them."""
+    def _parts_of(self, convs, audio=None):
+        """Conversations of (ctrl, text, label) parts -> (data, offs, part_ctrl, part_flags, conv_offs) as the join entries take them.
+        audio: a list that receives (part index, clip) of every part whose text is an Audio -- such a part gets the control id
+        [BEGIN_AUDIO], no text and no label --; None: the caller takes no audio parts."""
         names, texts, ctrl, pf, conv = {}, [], [], [], [0]
         for parts in convs:
             for part in parts:
                 if len(part) != 3:
                     raise TokenizerError(TK_ERR_INVALID_ARG, "encode_conversations: a part is (ctrl, text, label)")
                 c, text, label = part
+                if isinstance(text, Audio):
+                    if audio is None:
+                        raise TokenizerError(TK_ERR_INVALID_ARG, "audio parts are taken by encode_conversations and encode_chat only")
+                    audio.append((len(texts), text))
+                    ctrl.append(self.begin_audio_token_id)
+                    pf.append(0)
+                    texts.append(b"")
+                    continue
                 if isinstance(c, str):
                     if c not in names:
                         names[c] = self.get_control_token(c)      # (TokenNotFound for an unknown name)
@@ -2792,13 +3074,52 @@ class Tekkenizer:
         if return_tensors not in ("pt", "np"):
             raise TokenizerError(TK_ERR_INVALID_ARG, "encode_conversations: unknown return_tensors value")
         flags = (JOIN_LABELS if return_labels else 0) | (JOIN_PART_INDEX if return_part_index else 0)
-        parts = self._parts_of(convs)
+        audio = []
+        parts = self._parts_of(convs, audio)
+        if audio:
+            return self._conversations_audio(eng, parts, audio, ignore_index, flags, return_tensors, copy)
         if return_tensors == "np":
             r = eng.encode_parts_join(*parts, ignore_index=ignore_index, flags=flags)
             return {"input_ids": r["ids"], "offsets": r["offsets"], "labels": r["labels"], "part_index": r["part_index"],
                     "n_labelled": r["n_labelled"]}
         t = self._join_device(eng, parts, ignore_index, flags)[0].tensors(copy)
         return {"input_ids": t["ids"], "offsets": t["offsets"], "labels": t["labels"], "part_index": t["part_index"], "n_labelled": t["n_labelled"]}
+
+    def _conversations_audio(self, eng, parts, audio, ignore_index, flags, return_tensors, copy):
+        """encode_conversations with audio parts: encode the part texts, splice N times [AUDIO] behind every audio part
+        (tk_audio_splice_device), join; the clips' log-mel features beside it.  The result gains "audio_features" (as
+        encode_audio_batch's features), "audio_frame_off", "audio_clip_seg" and "audio_positions": the (start, N) of each [AUDIO]
+        run in input_ids, in clip order."""
+        import torch
+        data, offs, ctrl, pf, conv = parts
+        n_parts = len(ctrl)
+        tokens = np.zeros(max(n_parts, 1), np.uint32)
+        for p, clip in audio:
+            tokens[p] = len(self._audio_count(clip)[0]) - 1
+        d_bytes, d_offs, stream = _upload(data, offs)
+        up = [torch.from_numpy(x).cuda() for x in (ctrl.view(np.int32), pf.view(np.int32), conv.astype(np.int64), tokens.view(np.int32))]
+        ids_ptr, oo_ptr, n_ids = eng.encode_batch_device(d_bytes.data_ptr(), d_offs.data_ptr(), n_parts, len(data), False, False, stream,
+                                                         checks=CHECK_OFFSETS)
+        sp = eng.audio_splice_device(ids_ptr, oo_ptr, n_parts, n_ids, up[3].data_ptr(), self.audio_token_id, stream)
+        soffs = _torch_wrap(sp.views()[1], True).cpu().numpy().astype(np.int64)
+        res = eng.join_from_ids_device(sp.ids_ptr, sp.offsets_ptr, n_parts, sp.n_ids, up[0].data_ptr(), up[1].data_ptr(), up[2].data_ptr(),
+                                       len(conv) - 1, ignore_index, flags, CHECK_PARTS, stream)
+        t = res.tensors(copy)
+        out = {"input_ids": t["ids"], "offsets": t["offsets"], "labels": t["labels"], "part_index": t["part_index"], "n_labelled": t["n_labelled"]}
+        # a part's place in the joined stream: its spliced ids start behind the control ids of the parts up to and including it
+        has_ctrl = np.cumsum(ctrl != JOIN_NONE)
+        out["audio_positions"] = [(int(soffs[p]) + int(has_ctrl[p]), int(tokens[p])) for p, _ in audio]
+        r = self._audio_features(eng, [clip for _, clip in audio])
+        out["audio_features"], out["audio_frame_off"], out["audio_clip_seg"] = self._feature_tensors(r, copy)
+        if return_tensors == "np":
+            for k in ("input_ids", "offsets", "labels", "part_index"):
+                if out[k] is not None:
+                    out[k] = out[k].cpu().numpy()
+            out["input_ids"] = out["input_ids"].view(np.uint32)
+            out["offsets"] = out["offsets"].view(np.uint64)
+            if out["part_index"] is not None:
+                out["part_index"] = out["part_index"].view(np.uint32)
+        return out
 
     def _chat_parts(self, conversations, roles, add_bos):
         table = dict(self.CHAT_ROLES)
@@ -2810,7 +3131,22 @@ class Tekkenizer:
                 if m["role"] not in table:
                     raise TokenizerError(TK_ERR_INVALID_ARG, "encode_chat: no entry in roles for %r" % (m["role"],))
                 opn, close, train = table[m["role"]]
-                parts.append((opn, m["content"], (False, bool(train))))
+                content = m["content"]
+                if isinstance(content, (Audio, list, tuple)):
+                    # content items: text and clips in order.  The open control id stays in front (a part of its own where a
+                    # clip comes first); a clip is a part of its own and never labelled
+                    items = [content] if isinstance(content, Audio) else list(content)
+                    for k, it in enumerate(items):
+                        if isinstance(it, Audio):
+                            if k == 0 and opn is not None:
+                                parts.append((opn, "", False))
+                            parts.append((None, it, False))
+                        else:
+                            parts.append((opn if k == 0 else None, it, (False, bool(train))))
+                    if not items:
+                        parts.append((opn, "", (False, bool(train))))
+                else:
+                    parts.append((opn, content, (False, bool(train))))
                 if close is not None:
                     parts.append((close, "", bool(train)))
             convs.append(parts)

@@ -10,7 +10,11 @@
 #include <sstream>
 #include <unordered_set>
 
+#include "tk_audio_tables.h"
 #include "tk_engine.h"
+
+// The loader alone (the sanitizer build of tests/fuzz) links without the engine's audio pass: a weak reference, null there.
+extern "C" int tk_audio_set_config(tk_ctx* ctx, const tk_audio_config* cfg) __attribute__((weak));
 
 namespace tekken {
 
@@ -378,19 +382,22 @@ TokenizerError parse_model_data(const char* json, size_t len, ModelData& out) {
 
     const JVal* au = root.get("audio");
     out.has_audio = false;
+    memset(&out.audio, 0, sizeof(out.audio));
     if (au && au->kind != JVal::Null) {
-        // AudioConfig / AudioSpectrogramConfig (reference src/audio.rs:17-22, 85-91): shape only
+        // AudioConfig / AudioSpectrogramConfig (reference src/audio.rs:17-22, 85-91): the six numbers are kept as they stand
         if (au->kind != JVal::Obj) return mk(TK_ERR_JSON, "invalid type: expected struct AudioConfig");
-        uint64_t tmp;
-        if (!get_usize(au->get("sampling_rate"), tmp)) return mk(TK_ERR_JSON, "missing or invalid field `sampling_rate`");
+        tk_audio_config& a = out.audio;
+        if (!get_usize(au->get("sampling_rate"), a.sampling_rate)) return mk(TK_ERR_JSON, "missing or invalid field `sampling_rate`");
         if (!get_f64(au->get("frame_rate"))) return mk(TK_ERR_JSON, "missing or invalid field `frame_rate`");
+        a.frame_rate = au->get("frame_rate")->d;
         const JVal* ec = au->get("audio_encoding_config");
         if (!ec || ec->kind != JVal::Obj) return mk(TK_ERR_JSON, "missing or invalid field `audio_encoding_config`");
-        if (!get_usize(ec->get("num_mel_bins"), tmp) || !get_usize(ec->get("hop_length"), tmp) ||
-            !get_usize(ec->get("window_size"), tmp))
+        if (!get_usize(ec->get("num_mel_bins"), a.num_mel_bins) || !get_usize(ec->get("hop_length"), a.hop_length) ||
+            !get_usize(ec->get("window_size"), a.window_size))
             return mk(TK_ERR_JSON, "missing or invalid field in `audio_encoding_config`");
         const JVal* cl = au->get("chunk_length_s");
         if (cl && cl->kind != JVal::Null && !get_f64(cl)) return mk(TK_ERR_JSON, "invalid type for `chunk_length_s`");
+        if (cl && cl->kind != JVal::Null) { a.has_chunk_length = 1; a.chunk_length_s = cl->d; }
         out.has_audio = true;
     }
     return TokenizerError();
@@ -416,7 +423,7 @@ Tekkenizer::~Tekkenizer() {
 // Tekkenizer::new, reference src/tekkenizer.rs:71-191 (checks in the same order)
 Tekkenizer* Tekkenizer::create(const std::vector<TokenInfo>& vocab_in, const std::vector<SpecialTokenInfo>& special_tokens,
                                const std::string& /*pattern: ignored, src/tekkenizer.rs:74*/, uint64_t vocab_size,
-                               uint64_t num_special_tokens, const std::string& version, bool has_audio, int device_id,
+                               uint64_t num_special_tokens, const std::string& version, const tk_audio_config* audio, int device_id,
                                TokenizerError& err) {
     err = TokenizerError();
     if (vocab_size > vocab_in.size() + num_special_tokens) {  // :80-87
@@ -491,18 +498,19 @@ Tekkenizer* Tekkenizer::create(const std::vector<TokenInfo>& vocab_in, const std
         blob.insert(blob.end(), by_rank[r]->begin(), by_rank[r]->end());
         offs[r + 1] = (uint32_t)blob.size();
     }
-    return assemble(std::move(all), std::move(blob), std::move(offs), vocab_size, num_special_tokens, version, has_audio, device_id, err);
+    return assemble(std::move(all), std::move(blob), std::move(offs), vocab_size, num_special_tokens, version, audio, device_id, err);
 }
 
 Tekkenizer* Tekkenizer::assemble(std::vector<SpecialTokenInfo>&& all, std::vector<uint8_t>&& blob, std::vector<uint32_t>&& offs,
-                                 uint64_t vocab_size, uint64_t num_special_tokens, const std::string& version, bool has_audio,
+                                 uint64_t vocab_size, uint64_t num_special_tokens, const std::string& version, const tk_audio_config* audio,
                                  int device_id, TokenizerError& err) {
     Tekkenizer* t = new Tekkenizer();
     t->vocab_size_ = vocab_size;
     t->num_special_tokens_ = num_special_tokens;
     t->version_ = version;
     t->special_tokens_ = std::move(all);
-    t->has_audio_ = has_audio;
+    t->has_audio_ = audio != nullptr;
+    if (audio) t->audio_ = *audio;
     t->blob_ = std::move(blob);
     t->offs_ = std::move(offs);
     const std::vector<SpecialTokenInfo>& all_ref = t->special_tokens_;
@@ -518,7 +526,7 @@ Tekkenizer* Tekkenizer::assemble(std::vector<SpecialTokenInfo>&& all, std::vecto
             else t->vocab_[i] = "<?>";
         }
     }
-    if (has_audio) {  // :158-178
+    if (audio) {  // :158-178
         if (!t->special_tokens_map_.count("[AUDIO]")) {
             err = mk(TK_ERR_TOKEN_NOT_FOUND, "Audio token not found");
             delete t;
@@ -529,6 +537,8 @@ Tekkenizer* Tekkenizer::assemble(std::vector<SpecialTokenInfo>&& all, std::vecto
             delete t;
             return nullptr;
         }
+        t->audio_id_ = (uint32_t)t->special_tokens_map_["[AUDIO]"];
+        t->begin_audio_id_ = (uint32_t)t->special_tokens_map_["[BEGIN_AUDIO]"];
     }
     if (device_id >= 0) {
         uint32_t bos = 0, eos = 0;
@@ -552,6 +562,9 @@ Tekkenizer* Tekkenizer::assemble(std::vector<SpecialTokenInfo>&& all, std::vecto
             delete t;
             return nullptr;
         }
+        // the log-mel tables, where the transform can do the config (one it refuses stays loadable, as in the reference: the
+        // log-mel entries then report that no config is set)
+        if (audio && tk_audio_set_config) (void)tk_audio_set_config(t->ctx_, audio);
     }
     return t;
 }
@@ -567,7 +580,7 @@ Tekkenizer* Tekkenizer::from_json(const char* json, size_t len, int device_id, T
     }
     const std::vector<SpecialTokenInfo> sp = md.has_special_tokens ? md.special_tokens : deprecated_special_tokens();
     Tekkenizer* t = create(md.vocab, sp, md.config.pattern, md.config.default_vocab_size, md.config.default_num_special_tokens, v,
-                           md.has_audio, device_id, err);
+                           md.has_audio ? &md.audio : nullptr, device_id, err);
     if (t) t->pattern_ = md.config.pattern;
     return t;
 }
@@ -580,7 +593,7 @@ Tekkenizer* Tekkenizer::from_json(const char* json, size_t len, int device_id, T
 // key is 128 bits over length + content, the file carries magic, version, key, sizes and a tail marker, and anything
 // that does not check out falls back to the JSON.
 #define TK_MODEL_MAGIC 0x4D4B5454u /* "TTKM" */
-#define TK_MODEL_VERSION 3u   /* 2: config.pattern is kept (set_honour_pattern after a cached load); 3: payload checksum */
+#define TK_MODEL_VERSION 4u   /* 2: config.pattern is kept (set_honour_pattern after a cached load); 3: payload checksum; 4: the audio config and ids */
 
 static void content_key(const std::string& c, uint64_t key[2]) {
     uint64_t a = 0xCBF29CE484222325ull ^ c.size(), b = 0x9E3779B97F4A7C15ull + c.size();
@@ -609,6 +622,8 @@ struct ModelHead {
     uint64_t vocab_size, num_special_tokens, n_special, n_ranks, blob_bytes, strings_bytes;
     uint32_t has_audio, version_len;
     uint32_t pattern_len, pad;
+    tk_audio_config audio;                   // as loaded (has_audio != 0)
+    uint32_t audio_id, begin_audio_id;       // checked against what assemble derives
 };
 }  // namespace
 
@@ -635,6 +650,7 @@ bool Tekkenizer::save_model_cache(const std::string& path, const uint64_t key[2]
     h.n_ranks = offs_.size() - 1; h.blob_bytes = offs_.back(); h.strings_bytes = strings.size();
     h.has_audio = has_audio_ ? 1 : 0; h.version_len = (uint32_t)version_.size();
     h.pattern_len = (uint32_t)pattern_.size();
+    if (has_audio_) { h.audio = audio_; h.audio.pad = 0; h.audio_id = audio_id_; h.begin_audio_id = begin_audio_id_; }
     const uint32_t tail = TK_MODEL_MAGIC;
     // the payload checksum goes in front of the tail marker: a flipped bit anywhere makes the file "not check out"
     uint64_t sum = tk_sum64(key[0] ^ key[1], &h, sizeof(h));
@@ -696,8 +712,13 @@ Tekkenizer* Tekkenizer::load_model_cache(const std::string& path, const uint64_t
     }
     if (q + h.pattern_len != strings.size() || all.size() != h.num_special_tokens) return nullptr;
     const std::string pattern = strings.substr(q, h.pattern_len);
-    Tekkenizer* t = assemble(std::move(all), std::move(blob), std::move(offs), h.vocab_size, h.num_special_tokens, version, h.has_audio != 0,
-                             device_id, err);
+    Tekkenizer* t = assemble(std::move(all), std::move(blob), std::move(offs), h.vocab_size, h.num_special_tokens, version,
+                             h.has_audio ? &h.audio : nullptr, device_id, err);
+    if (t && h.has_audio && (t->audio_id_ != h.audio_id || t->begin_audio_id_ != h.begin_audio_id)) {   // does not check out: the JSON
+        delete t;
+        err = TokenizerError();
+        return nullptr;
+    }
     if (t) { t->pattern_ = pattern; t->from_cache_ = true; }
     return t;
 }
@@ -1061,6 +1082,44 @@ extern "C" int tk_tokenizer_id_to_byte_piece(tk_tokenizer* h, uint32_t id, int p
     tekken::TokenizerError e = h->t->id_to_byte_piece(id, (tekken::SpecialTokenPolicy)policy, s);
     if (!e.ok()) return finish(h, e);
     return export_str(h, s, (char**)bytes, len);
+}
+
+// ---- audio (src/tekkenizer.rs:697-760) ----
+static const char* kNoAudio = "Audio encoder not configured";
+extern "C" int tk_tokenizer_has_audio(const tk_tokenizer* h) { return h && h->t->has_audio(); }
+extern "C" int tk_tokenizer_audio_config(tk_tokenizer* h, tk_audio_config* out) {
+    if (!h || !out) return TK_ERR_INVALID_ARG;
+    if (!h->t->has_audio()) return tk_tokenizer_fail(h, TK_ERR_AUDIO, kNoAudio);
+    *out = h->t->audio_config();
+    return TK_OK;
+}
+extern "C" int tk_tokenizer_audio_ids(tk_tokenizer* h, uint32_t* audio_id, uint32_t* begin_audio_id) {
+    if (!h || !audio_id || !begin_audio_id) return TK_ERR_INVALID_ARG;
+    if (!h->t->has_audio()) return tk_tokenizer_fail(h, TK_ERR_AUDIO, kNoAudio);
+    *audio_id = h->t->audio_token_id();
+    *begin_audio_id = h->t->begin_audio_token_id();
+    return TK_OK;
+}
+// AudioEncoder::encode (audio.rs:555-591) without the waveform: resample (refused), pad, frames, tokens
+extern "C" int tk_tokenizer_encode_audio(tk_tokenizer* h, uint64_t n_samples, uint64_t clip_rate, uint32_t** ids, size_t* n_ids,
+                                         uint64_t* padded_samples) {
+    if (!h || !ids || !n_ids) return TK_ERR_INVALID_ARG;
+    if (!h->t->has_audio()) return tk_tokenizer_fail(h, TK_ERR_AUDIO, kNoAudio);
+    const tk_audio_config a = h->t->audio_config();
+    if (clip_rate != a.sampling_rate) return tk_tokenizer_fail(h, TK_ERR_AUDIO, "Resampling not yet implemented");
+    // (tk_audio_layout's arithmetic for one clip, from the header it is made of: the loader links without the engine)
+    const uint64_t per = tk_audio_config_sane(a) ? tk_audio_per_token(a) : 0, cf = a.has_chunk_length && per ? tk_audio_chunk_frames(a) : 0;
+    if (per == 0 || (a.has_chunk_length && cf == 0))
+        return tk_tokenizer_fail(h, TK_ERR_INVALID_CONFIG, "audio config: a zero or negative field, or no whole frame per token");
+    const uint64_t padded = tk_audio_padded(a, cf, n_samples), n_tok = tk_audio_tokens(tk_audio_frames(a, padded), per);
+    uint32_t* v = (uint32_t*)malloc((size_t)(n_tok + 1) * sizeof(uint32_t));
+    if (!v) return tk_tokenizer_fail(h, TK_ERR_RUNTIME, "out of memory");
+    v[0] = h->t->begin_audio_token_id();
+    for (uint64_t i = 0; i < n_tok; ++i) v[1 + i] = h->t->audio_token_id();
+    *ids = v;
+    *n_ids = (size_t)(n_tok + 1);
+    if (padded_samples) *padded_samples = padded;
+    return TK_OK;
 }
 
 extern "C" tk_ctx* tk_tokenizer_ctx(tk_tokenizer* h) { return h ? h->t->ctx() : nullptr; }

@@ -49,13 +49,14 @@ struct TekkenConfig {
     std::string version;
 };
 
-// reference src/config.rs:73-82 (audio is only checked for presence / shape: out of scope)
+// reference src/config.rs:73-82 (audio: the AudioConfig of src/audio.rs:85-91 as the C ABI carries it)
 struct ModelData {
     std::vector<TokenInfo> vocab;
     bool has_special_tokens = false;
     std::vector<SpecialTokenInfo> special_tokens;
     TekkenConfig config;
     bool has_audio = false;
+    tk_audio_config audio = {};
 };
 
 class Tekkenizer {
@@ -67,7 +68,7 @@ public:
     // Tekkenizer::new (src/tekkenizer.rs:71-191)
     static Tekkenizer* create(const std::vector<TokenInfo>& vocab, const std::vector<SpecialTokenInfo>& special_tokens,
                               const std::string& pattern, uint64_t vocab_size, uint64_t num_special_tokens,
-                              const std::string& version, bool has_audio, int device_id, TokenizerError& err);
+                              const std::string& version, const tk_audio_config* audio /* null: none */, int device_id, TokenizerError& err);
 
     // src/tekkenizer.rs:378-405
     TokenizerError encode(const char* text, size_t len, bool add_bos, bool add_eos, std::vector<uint32_t>& out);
@@ -94,6 +95,12 @@ public:
     TokenizerError unk_id(uint32_t& id) const { return get_control_token("<unk>", id); }
     const std::vector<std::string>& vocab() const { return vocab_; }
 
+    // src/tekkenizer.rs:737-760
+    bool has_audio() const { return has_audio_; }
+    const tk_audio_config& audio_config() const { return audio_; }
+    uint32_t audio_token_id() const { return audio_id_; }
+    uint32_t begin_audio_token_id() const { return begin_audio_id_; }
+
     tk_ctx* ctx() { return ctx_; }
     // row f-3 (opt-in): honour the JSON `pattern` the file carried.  Only the pattern of Mistral's tekken.json is known
     // to the matcher; any other string is refused.  honour = false restores the reference's behaviour (pattern ignored).
@@ -108,7 +115,7 @@ private:
     Tekkenizer() = default;
     // second half of `create`: everything after the rank table is validated (also the entry of the model cache)
     static Tekkenizer* assemble(std::vector<SpecialTokenInfo>&& all, std::vector<uint8_t>&& blob, std::vector<uint32_t>&& offs,
-                                uint64_t vocab_size, uint64_t num_special_tokens, const std::string& version, bool has_audio,
+                                uint64_t vocab_size, uint64_t num_special_tokens, const std::string& version, const tk_audio_config* audio,
                                 int device_id, TokenizerError& err);
     bool save_model_cache(const std::string& path, const uint64_t key[2]) const;
     static Tekkenizer* load_model_cache(const std::string& path, const uint64_t key[2], int device_id, TokenizerError& err);
@@ -125,6 +132,8 @@ private:
     std::vector<uint8_t> blob_;                                  // rank table: bytes of rank i
     std::vector<uint32_t> offs_;
     bool has_audio_ = false;
+    tk_audio_config audio_ = {};                                 // src/tekkenizer.rs:757 audio_config
+    uint32_t audio_id_ = 0, begin_audio_id_ = 0;                 // [AUDIO] / [BEGIN_AUDIO] (:158-178)
     std::string pattern_;                                        // config.pattern as loaded (ignored unless opted in)
     bool from_cache_ = false;
 };

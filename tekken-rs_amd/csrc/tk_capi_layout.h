@@ -3,8 +3,8 @@
 // entries are made, the sizing of a tensor of rows (the refusals, and the counts / scan / one read of the window, chunk and pair
 // passes), what the window and chunk passes share beyond that, and the three entries around a pass (ids on the device | text on the
 // device | text on the host) written once.
-// (tk_capi_words.cpp, tk_capi_specials.cpp, tk_capi_fim.cpp and tk_capi_noise.cpp take the descriptions of tk_words / tk_specials /
-// tk_fim / tk_noise_replace / tk_noise_spans from here
+// (tk_capi_words.cpp, tk_capi_specials.cpp, tk_capi_fim.cpp, tk_capi_noise.cpp and tk_capi_audio.cpp take the descriptions of
+// tk_words / tk_specials / tk_fim / tk_noise_replace / tk_noise_spans / tk_logmel / tk_ragged from here
 // and have entries of their own: they take the text, or stand in front of encode.)
 #ifndef TK_CAPI_LAYOUT_H
 #define TK_CAPI_LAYOUT_H
@@ -126,6 +126,15 @@ template <class F> static inline void layout_outputs(tk_words& r, uint64_t, uint
     f(r.word_ids, r.n_ids * 4, true);
     f(r.doc_words, (r.n_docs + 1) * 8, true);
     f(r.word_first, r.n_words * 4, r.word_first != nullptr);
+}
+template <class F> static inline void layout_outputs(tk_logmel& r, uint64_t, uint64_t, F&& f) {
+    f(r.features, r.n_mel * r.n_frames * 4, true);
+    f(r.frame_off, (r.n_segments + 1) * 8, true);
+    f(r.clip_seg, (r.n_clips + 1) * 8, true);
+}
+template <class F> static inline void layout_outputs(tk_ragged& r, uint64_t, uint64_t, F&& f) {
+    f(r.ids, r.n_ids * 4, true);
+    f(r.offsets, (r.n_parts + 1) * 8, true);
 }
 
 // tk_free_<pass>: every block back to the pinned pool, the struct zeroed

@@ -194,6 +194,21 @@ struct DecodeLossyBufs {
     uint32_t repair_launches = 0;  // kernels the last lossy call launched behind the strict pipeline (0: the fast path)
 };
 
+// the audio pass (tk_audio.hip).  The config and its device tables (tk_audio_set_config: the DFT matrix, the filter bank's runs);
+// the log-mel outputs (features, frame_off, clip_seg), the segments, tiles and per-segment maxima, the host entry's copies of
+// the samples and their offsets; the splice's outputs (ids, offsets) and its counts and scan workspace
+struct AudioBufs {
+    bool have_config = false;
+    tk_audio_config cfg = {};
+    uint32_t W = 0, F = 0, M = 0;
+    DevBuf dft, fb_first, fb_count, fb_start, fb_weights;
+    DevBuf feat, frame_off, clip_seg, segs, tiles, seg_max, in_samples, in_offs;
+    DevBuf sp_ids, sp_offs, sp_cnt, sp_bsum;
+    uint64_t n_splice_calls = 0;
+    Event ev[3];                   // the stages of the last log-mel call (tk_last_logmel_ms), created at the first one
+    float ms[2] = {0.f, 0.f};      // product kernel | clamp kernel
+};
+
 struct tk_ctx {
     int device = 0;
     std::mutex mu;
@@ -231,6 +246,7 @@ struct tk_ctx {
     FimBufs fim;
     NoiseBufs noise;
     DecodeLossyBufs lossy;
+    AudioBufs audio;
     DevBuf staging, counts, out_ids, out_offs, block_sums, defer_list, scratch, in_bytes, in_offs, dbg;
     DevBuf counters;               // TKC_DEVICE_WORDS words: tk_counters.h
     PinBuf<uint32_t> h_pin;        // TKC_PIN_WORDS pinned host words: the per-batch device counters land here with ONE copy

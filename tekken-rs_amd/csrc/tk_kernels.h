@@ -624,6 +624,52 @@ hipError_t tk_launch_noise_drop(const TkNoiseArgs& a, hipStream_t s);      // KS
 hipError_t tk_launch_noise_lens(const TkNoiseArgs& a, hipStream_t s);      // in_len, tg_len, stat[0..2]
 hipError_t tk_launch_noise_fill(const TkNoiseArgs& a, hipStream_t s);      // the outputs (behind the two document scans and the host read)
 
+// ---- audio: log-mel features and the splice of audio parts (tk_audio.hip) ----
+#define TKA_BLOCK 256
+#define TKA_FRAMES 64u         /* frames of a block's tile: two 32-frame MFMA tiles a wave */
+#define TKA_ROUND_BINS 128u    /* bins of a round: 32 a wave */
+struct TkaSegment {            // one segment, as the host lays it out (tk_audio_layout's arithmetic)
+    uint64_t start;            // its first sample in the packed clips
+    uint64_t valid;            // the samples of it the clip has; the rest, up to len, are zero padding that is never read
+    uint64_t len;              // L: its samples with the padding (reflection is about L - 1)
+    uint64_t out;              // its first element in the features: M * frame_off[s]
+    uint32_t frames, pad;      // T_s
+};
+struct TkaTile { uint32_t seg, t0; };   // a block's tile: frames t0 .. t0 + TKA_FRAMES of segment seg
+struct TkLogmelArgs {
+    const float* samples;      // the clips back to back, unpadded
+    const TkaSegment* segs;    // [n_segs]
+    const TkaTile* tiles;      // [n_tiles]
+    uint32_t n_tiles, n_segs;
+    uint32_t W, H, F, M;       // window, hop, bins W / 2 + 1, mel filters
+    const float* dft;          // [W][2 F]: tk_audio_tables.h
+    const uint32_t *fb_first, *fb_count, *fb_start;   // [M]
+    const float* fb_weights;
+    float* out;                // the features
+    uint32_t* seg_max;         // [n_segs] bit patterns of the largest max(mel, 1e-10) (zeroed by the caller); null with a fixed maximum
+    float fixed_max;           // log_mel_max where seg_max is null
+    uint32_t staged;           // the tile's samples go to LDS (set by the launcher: they fit)
+    uint32_t lds_samples;      // floats of LDS for them (set by the launcher)
+    // the clamp kernel
+    const uint64_t* frame_off; // [n_segs + 1]
+    uint64_t n_elems;          // M * frame_off[n_segs]
+};
+hipError_t tk_launch_logmel(const TkLogmelArgs& a, hipStream_t s);         // L = log10(max(mel, 1e-10)), or the feature with a fixed maximum; no tile: nothing is launched
+hipError_t tk_launch_logmel_clamp(const TkLogmelArgs& a, hipStream_t s);   // (max(L, Lmax - 8) + 4) / 4 in place
+struct TkSpliceArgs {
+    const uint32_t* ids;       // [n_ids]
+    const uint64_t* id_offs;   // [n_parts + 1]
+    const uint32_t* part_tokens;   // [n_parts] copies of fill_id behind the part's ids
+    uint64_t n_parts, n_ids;
+    uint32_t fill_id;
+    uint32_t* counts;          // [n_parts] the new lengths, clamped to 2^32 - 1 (tk_launch_splice_counts)
+    const uint64_t* out_offs;  // [n_parts + 1] their exclusive scan
+    uint32_t* out_ids;
+    uint64_t n_out;
+};
+hipError_t tk_launch_splice_counts(const TkSpliceArgs& a, hipStream_t s);
+hipError_t tk_launch_splice_fill(const TkSpliceArgs& a, hipStream_t s);    // n_out == 0: nothing is launched
+
 // max document length over the deferred documents (atomicMax into *d_out, which must be zeroed)
 hipError_t tk_launch_defer_maxlen(const uint32_t* defer_list, uint32_t n, const uint64_t* doc_offs, uint32_t* d_out,
                                   hipStream_t s);
